@@ -15,6 +15,12 @@ RCCL and no steady-state collective.
 Other workloads of SURVEY §8(d) come from the same script: `--classes 7 --height 448 --width 800 --batch 32`
 (config 4), `--height 1024 --width 1024 --batch 8` (config 5), `--arch simple --classes 7 --height 256 --width 256`
 (SimpleUNet, §8(f) row 3).
+
+A plain run sets up, warms up, times exactly --steps steps once and prints the JSON line.  `--full` adds what else the
+line can carry: the median of three timed loops, the roofline of the dominant kernel from a profiled loop, the CPU
+baseline with the parity of the measured mode, the PCIe-inclusive leg and the other precisions as legs.
+`--dump-outputs DIR` writes the masks the last timed step returned as DIR/mask.npy (float32), so that two builds can be
+compared output for output on the same seeded frames.
 """
 from __future__ import annotations
 
@@ -36,6 +42,7 @@ DTYPES = {"exact": "f16 (MFMA operands split hi+lo, 3 MFMAs per product, f32 acc
           "fast": "f16"}
 MFMA_F16_PEAK_TFLOPS = 2500.0                       # dense fp16 MFMA, MI355X_MICROARCH.md chip table
 HBM_PEAK_GBS = 8000.0
+DUMP_LIMIT_BYTES = 64 << 20                         # --dump-outputs: all ranks' files together
 
 
 def algorithmic_gflop(arch, C, H, W):
@@ -199,6 +206,18 @@ def _parity(oracle, logits, mask, ref_logits, ref_masks, n_frames, gpu_model):
             "range_status": int(gpu_model.status())}
 
 
+def dump_output(out_dir, name, t, budget_bytes):
+    """DIR/<name>.npy: tensor `t` (what the timed path returned) as float32.  An output larger than `budget_bytes` is
+    replaced by a fixed, seeded sample of its elements (flattened, in index order): the same sample in every run."""
+    import numpy as np
+    a = t.cpu().numpy().astype(np.float32)
+    n = (budget_bytes - 4096) // a.itemsize            # (4 KB left for the .npy header)
+    if a.size > n:
+        a = a.ravel()[np.sort(np.random.default_rng(0).integers(0, a.size, n))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def measured_traffic(kernel, workload_key):
     """HBM bytes per launch of `kernel` from the committed rocprofv3 --pmc passes, but only from a file that was
     recorded for THIS build (same source hash) and workload; otherwise None plus the reason."""
@@ -343,7 +362,7 @@ def run_rank(args) -> int:
             model.profile(True)
         t0 = time.perf_counter()
         for _ in range(steps):
-            model.segment(x)
+            y = model.segment(x)
         sync()
         own = time.perf_counter() - t0                  # this rank alone, before waiting for the others
         barrier(); sync()
@@ -351,25 +370,28 @@ def run_rank(args) -> int:
         recs = model.profile_read() if profile else []
         if profile:
             model.profile(False)
-        return max_over_ranks(dt), own, recs
+        return max_over_ranks(dt), own, recs, y
 
     if world > 1:
         barrier()                                       # first collective: sets the communicator up, untimed
     model = make_model(args.precision, timed_bcast=True)
-    # `value`: no per-launch events in the timed region.  The timed loop (W warm-up + exactly K steps between barriers) runs
-    # three times; the median sample is reported (boxes of the pool and even consecutive loops differ by a few percent),
-    # all three are printed.
-    samples = [timed(model, args.steps, args.warmup if i == 0 else 1, profile=False) for i in range(1 if dry else 3)]
-    dt, own_dt, _ = sorted(samples, key=lambda t: t[0])[len(samples) // 2]
+    # `value`: no per-launch events in the timed region.  The timed loop is W warm-up + exactly K steps between barriers;
+    # with --full it runs three times and the median sample is reported (boxes of the pool and even consecutive loops
+    # differ by a few percent), all three are printed.
+    samples = [timed(model, args.steps, args.warmup if i == 0 else 1, profile=False)
+               for i in range(3 if args.full and not dry else 1)]
+    dt, own_dt, _, _ = sorted(samples, key=lambda t: t[0])[len(samples) // 2]
     fps = B * world * args.steps / dt
     gflop = algorithmic_gflop(arch, C, H, W)
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, "mask" if world == 1 else f"mask_rank{rank}", samples[-1][3], DUMP_LIMIT_BYTES // world)
 
     # ---- roofline of the dominant kernel: a second, short loop with one HIP event per launch boundary, recorded on
     # the launch stream by the engine (unetpp_profile_*); its per-step time is reported next to the un-profiled one
     roofline, agg, prof_ms, executed_gflop = None, {}, None, None
-    if not dry:
+    if args.full and not dry:
         psteps = max(2, min(args.steps, 10))
-        pdt, _, recs = timed(model, psteps, 1, profile=True)
+        pdt, _, recs, _ = timed(model, psteps, 1, profile=True)
         prof_ms = pdt / psteps * 1e3
         executed_gflop = sum(r[2] for r in recs) / psteps / B / 1e9        # flops of the launches the engine really made
         for name, ms, fl, by in recs:
@@ -443,7 +465,7 @@ def run_rank(args) -> int:
 
     ref_cache = {}
     # ---- CPU baseline + parity of the measured mode on the same frames (rank 0, N=1 only)
-    if rank == 0 and world == 1 and args.cpu_frames > 0 and not dry:
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0 and not dry:
         base, parity = cpu_baseline(sd, syn, arch, C, H, W, args.cpu_frames, model, torch, ref=ref_cache)
         out["cpu_baseline"] = base
         out["parity"] = parity
@@ -453,7 +475,7 @@ def run_rank(args) -> int:
     # ---- informational: the PCIe-inclusive rate (never `value`): pinned uint8 BGR frames -> H2D -> engine (BGR->RGB,
     # /255 fused) -> uint8 masks -> D2H into pinned memory, two engines on two streams so copies overlap compute.
     # With N ranks every rank feeds its own GPU at the same time (what decides >= 6x at 8 GPUs is this host side).
-    if not args.no_e2e_leg and not dry:
+    if args.full and not args.no_e2e_leg and not dry:
         try:                                                # informational: a failure here must not cost the headline line
             ma, mb = model, make_model(args.precision)
             eng = [ma, mb]
@@ -491,13 +513,13 @@ def run_rank(args) -> int:
             out["end_to_end"] = {"error": f"{type(exc).__name__}: {exc}"}
 
     # ---- informational second leg: the other precision mode on the same workload
-    if not args.no_fast_leg and world == 1 and not dry:
+    if args.full and not args.no_fast_leg and world == 1 and not dry:
         del model
         legs = {}
         for other in [p for p in ("exact", "exact8", "fast") if p != args.precision]:
             try:                                            # a leg is informational: its failure must not cost the headline line
                 m2 = make_model(other)
-                dt2, _, _ = timed(m2, args.steps, args.warmup, profile=False)
+                dt2, _, _, _ = timed(m2, args.steps, args.warmup, profile=False)
                 leg = {"precision": other, "dtype": DTYPES[other], "value": B * args.steps / dt2, "unit": "frames/s",
                        "ms_per_step": dt2 / args.steps * 1e3}
                 if rank == 0 and args.cpu_frames > 0:
@@ -534,9 +556,14 @@ def main() -> int:
     ap.add_argument("--precision", default="exact", choices=["exact", "exact8", "fast"])
     ap.add_argument("--micro-batch", type=int, default=0)
     ap.add_argument("--streams", type=int, default=1)
-    ap.add_argument("--cpu-frames", type=int, default=16, help="frames timed on the CPU baseline (0 = skip)")
-    ap.add_argument("--no-fast-leg", action="store_true")
-    ap.add_argument("--no-e2e-leg", action="store_true", help="skip the PCIe-inclusive informational leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also the median of three timed loops, roofline, CPU baseline + parity, PCIe-inclusive leg and "
+                         "the other precisions (a plain run times the --steps steps once and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--cpu-frames", type=int, default=16, help="frames timed on the CPU baseline with --full (0 = skip)")
+    ap.add_argument("--no-fast-leg", action="store_true", help="with --full: skip the other precisions")
+    ap.add_argument("--no-e2e-leg", action="store_true", help="with --full: skip the PCIe-inclusive informational leg")
     ap.add_argument("--no-engine", action="store_true",
                     help="control-flow rehearsal on CPU (gloo, no GPU, nothing computed, value = null): launcher tests only")
     args = ap.parse_args()
@@ -547,6 +574,9 @@ def main() -> int:
     args.classes = args.classes or (7 if simple else 3)
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         return 2
     if args.gpus > 1 and "RANK" not in os.environ:
         return launch_ranks(args)

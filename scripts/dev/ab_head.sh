@@ -7,7 +7,7 @@ cd "$(dirname "$0")/../.."
 for round in 1 2; do
   for tree in . build/ab_old; do
     for prec in exact exact8; do
-      (cd $tree && python bench.py "$@" --precision $prec --no-e2e-leg --no-fast-leg --cpu-frames 0 2>/dev/null | python -c "
+      (cd $tree && python bench.py --full "$@" --precision $prec --no-e2e-leg --no-fast-leg --cpu-frames 0 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print('$tree', '$prec', ['%.4f' % t for t in d['ms_per_step_samples']])")
     done

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/../.."
 one() {
   for tree in . build/ab_old; do
-    (cd $tree && python bench.py "$@" --no-e2e-leg --no-fast-leg --cpu-frames 0 2>/dev/null | python -c "
+    (cd $tree && python bench.py --full "$@" --no-e2e-leg --no-fast-leg --cpu-frames 0 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print('$tree', '$*', ['%.4f' % t for t in d['ms_per_step_samples']])")
   done

@@ -11,9 +11,9 @@ run() {
   OUT=$ROOT/gpurun_out/${TAG}_$name
   mkdir -p $OUT
   cd $ROOT
-  python3 bench.py --steps 20 --warmup 5 "$@" > profiles/${TAG}_${name}_bench.json 2> $OUT/bench.err
+  python3 bench.py --full --steps 20 --warmup 5 "$@" > profiles/${TAG}_${name}_bench.json 2> $OUT/bench.err
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --steps 10 --warmup 3 --cpu-frames 0 --no-fast-leg --no-e2e-leg "$@" > $ROOT/profiles/${TAG}_${name}_bench_under_rocprof.json 2> $OUT/stats.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --full --steps 10 --warmup 3 --cpu-frames 0 --no-fast-leg --no-e2e-leg "$@" > $ROOT/profiles/${TAG}_${name}_bench_under_rocprof.json 2> $OUT/stats.err
   cd $ROOT
   cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) profiles/${TAG}_${name}_kernel_stats.csv
   echo "$name done" >> $ROOT/gpurun_out/${TAG}_configs_progress.txt

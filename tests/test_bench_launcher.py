@@ -51,3 +51,16 @@ def test_failing_rank_ends_the_job():
             {"UNETPP_BENCH_FAIL_RANK": "1", "UNETPP_BENCH_TIMEOUT": "120"})
     assert r.returncode != 0
     assert "rank exit codes" in r.stderr
+
+
+def test_plain_run_times_exactly_steps_and_dumps_outputs(tmp_path):
+    r = run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-engine", "--batch", "2", "--height", "16", "--width", "16",
+             "--dump-outputs", str(tmp_path / "out")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.splitlines()[-1])
+    assert d["steps"] == 3 and len(d["ms_per_step_samples"]) == 1      # one timed loop of exactly --steps steps
+    assert d["ms_per_step"] >= 2.0                                     # the stand-in engine sleeps 2 ms per step
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    import numpy as np
+    mask = np.load(tmp_path / "out" / "mask.npy")
+    assert mask.dtype == np.float32 and mask.shape == (2, 16, 16)

@@ -245,11 +245,8 @@ def test_exact8_probabilities_and_rules(torch_cuda, syn, oracle):
         assert not (diff & (d > 2 * perr + 1e-7)).any(), key
 
 
-def test_exact8_rejects_what_it_does_not_support(torch_cuda, syn, monkeypatch):
+def test_unknown_precision_is_rejected(torch_cuda):
     from unet_amd.nested_unet import NestedUNet
-    monkeypatch.setenv("UNETPP_NO_WS", "1")
-    with pytest.raises(RuntimeError, match="UNETPP_NO_WS"):
-        NestedUNet(3, precision="exact8", max_batch=1, max_hw=(32, 32)).to("cuda:0")._ensure_engine(1, 32, 32)
     with pytest.raises(ValueError):
         NestedUNet(3, precision="exact4")
 

@@ -524,17 +524,23 @@ def test_determinism_side_stream_and_threads(torch_cuda, syn):
         assert len(outs) == 5 and all(torch.equal(o, a) for o in outs)
 
 
-def test_small_grid_tiles_are_bitwise_the_same(torch_cuda, syn, monkeypatch):
-    """The lock-step kernel (fast mode; exact mode with UNETPP_NO_WS=1) runs small batches' pool-free layers with 8-row
-    tiles (twice the workgroups) and large ones with 16-row tiles; a frame's logits must not depend on which tile
-    height computed it."""
+def test_lock_step_small_grid_tiles_are_bitwise_the_same(torch_cuda, syn, monkeypatch):
+    """The lock-step kernel (every conv of fast mode; SimpleUNet's two-source decoder convs in exact mode) runs small
+    batches' pool-free layers with 8-row tiles (twice the workgroups) and large ones with 16-row tiles; a frame's logits
+    must not depend on which tile height computed it.  (UNETPP_KSPLIT=1: the wave-specialised layers of exact mode keep one
+    launch plan for every batch size, so the tile height is the only thing that changes.)"""
     torch = torch_cuda
-    monkeypatch.setenv("UNETPP_NO_WS", "1")
+    from unet_amd.nested_unet import SimpleUNet
+    monkeypatch.setenv("UNETPP_KSPLIT", "1")
     B, H, W = 16, 256, 256
     frames = syn.make_frames_u8(B, H, W, "smooth", 31)
     x = torch.from_numpy(syn.frames_to_chw_f32(frames)).cuda()
-    for prec in ("exact", "fast"):
-        m, _ = make_model(3, True, 2, prec, syn, B, (H, W))
+    simple = SimpleUNet(num_classes=7, max_batch=B, max_hw=(H, W)).to("cuda:0")
+    simple.load_state_dict(syn.make_simple_state_dict(7, 3, 2), strict=True)
+    fast, _ = make_model(3, True, 2, "fast", syn, B, (H, W))
+    # a lock-step layer whose tile count crosses the CU count between 1 and 16 frames: exact SimpleUNet dec3.0 (256
+    # channels at 64x64: 32 -> 512 tiles); fast conv1_3.conv2 (64 channels at 128x128: 32 -> 512)
+    for prec, m, layer in (("exact", simple.eval(), "dec3.0"), ("fast", fast, "conv1_3.conv2")):
         m(x[:1])                                   # creates the engine
         m.profile(True)
         one = m(x[:1])
@@ -547,9 +553,7 @@ def test_small_grid_tiles_are_bitwise_the_same(torch_cuda, syn, monkeypatch):
         m.profile(False)
         pick = lambda names, layer: next(n for n in names if n.startswith(layer + "|"))
         rows = lambda n: int(n.split("<")[1].split(",")[3])          # the MW template argument
-        # a lock-step layer whose tile count crosses the CU count between 1 and 16 frames: exact conv2_2.conv2 (128
-        # channels at 64x64: 16 -> 256 tiles); fast conv1_3.conv2 (64 channels at 128x128: 32 -> 512)
-        layer = "conv2_2.conv2" if prec == "exact" else "conv1_3.conv2"
+        assert "conv3x3_bias_relu_kernel<" in pick(names_1, layer), prec
         assert rows(pick(names_1, layer)) == 1 and rows(pick(names_b, layer)) == 2
         assert torch.equal(one, full[:1]), prec
 
@@ -660,13 +664,14 @@ def test_config5_1024_batch8_against_reference_fixture(torch_cuda, syn, oracle):
     assert model.status() == 0
 
 
-@pytest.mark.parametrize("env", [{"UNETPP_NO_WS": "1"}, {"UNETPP_NO_UPF": "1"}, {"UNETPP_NO_C0F": "1"}, {"UNETPP_TAPMM": "none"},
-                                 {"UNETPP_TAPMM": "3"}, {"UNETPP_NO_WS": "1", "UNETPP_NO_UPF": "1", "UNETPP_TAPMM": "none"}])
+@pytest.mark.parametrize("env", [{"UNETPP_KSPLIT": "1"}, {"UNETPP_TAPMM": "2"}, {"UNETPP_KSPLIT": "2"}, {"UNETPP_TAPMM": "none"},
+                                 {"UNETPP_TAPMM": "3"}, {"UNETPP_TAPMM": "none", "UNETPP_KSPLIT": "1"}])
 def test_alternative_kernel_paths_agree(env, torch_cuda, syn, oracle, monkeypatch):
-    """Every fusion has a switch that restores the separate kernels (read when an engine is created; used for A/B
-    measurements): lock-step instead of wave-specialised Cout=32 kernels, separate level-0 upsample, unfused first block,
-    decoder conv1 without the low-resolution GEMM / with it at level 3 only.  Each combination must pass the same parity
-    bar as the default path and agree with it to rounding (the summation order differs, the arithmetic does not)."""
+    """The two switches read when an engine is created pick between live plans of the exact-mode path: UNETPP_TAPMM which
+    decoder levels take the low-resolution GEMM (the others interpolate their up channels in the wave-specialised loader),
+    UNETPP_KSPLIT the split-K of small launches (this 96x160 batch of 2 splits levels 3-4 by default; "1" = no split, "2" =
+    two-way splits at most).  Each plan must pass the same parity bar as the default path and agree with it to rounding
+    (the summation order differs, the arithmetic does not)."""
     torch = torch_cuda
     frames = syn.make_frames_u8(2, 96, 160, "smooth", 41)
     x = torch.from_numpy(syn.frames_to_chw_f32(frames)).cuda()

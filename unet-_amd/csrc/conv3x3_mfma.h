@@ -77,7 +77,7 @@ struct ConvArgs {
   float t_cable, t_tape, bg_margin, ct_margin;
   unsigned* status;      // engine's sticky range flags (ST_*), see range_flag
   // fused first ConvBlock (conv3x3_ws.h, C0F): the caller's input tensor and conv0_0.conv1's packed weights
-  const float* zinit;    // ZINIT: [N][Cout/32][H*W][32] fp32 accumulator start values (tapmm_ws.h), else unused
+  const float* zinit;    // conv3x3_ws.h: [N][Cout/32][H*W][32] fp32 accumulator start values (tapmm_ws.h), or nullptr
   const void* raw_in;    // float32 [N,3,H,W] (raw_fmt 0) or uint8 [N,H,W,3] BGR (raw_fmt 1)
   int raw_fmt;
   const half_t* c1w;     // [half 2][plane 2][lane 64][8]: A fragments of v_mfma_f32_16x16x32_f16, see conv0_pack_kernel
@@ -127,7 +127,7 @@ __device__ __forceinline__ void apply_rule(int rule, float p0, float p1, float p
   }
 }
 
-template <int P, int KC, int NW, int MW, int WAVES, bool SINGLE = false, bool UPF = false>
+template <int P, int KC, int NW, int MW, int WAVES, bool UPF = false>
 struct ConvCfg {
   static constexpr int NT = WAVES * 64;
   static constexpr int TH = WAVES * MW, TW = 32, HALO_W = TW + 2, NHALO = (TH + 2) * HALO_W;
@@ -144,12 +144,7 @@ struct ConvCfg {
   static constexpr int HALO_ITERS = (HALO_PIECES + WAVES - 1) / WAVES;   // DMA pieces per wave and chunk
   static constexpr int SLAB_BYTES = P * 9 * KC * BN * 2;
   static constexpr int BUF_BYTES = HALO_BYTES + SLAB_BYTES;
-  // Stage buffers per workgroup: two (the next chunk loads under this chunk's MFMAs; one workgroup per CU in exact
-  // mode), or with SINGLE one, so that two workgroups fit a CU.  The load, matrix and epilogue phases of a single
-  // workgroup's lock-stepped waves do not overlap each other (measured: they add up); those of two workgroups do.
-  // It pays where HBM is not the limit anyway: the fused-head conv, which reads x0_4a and writes one byte per pixel
-  // (265 -> 221 us); the other full-resolution convs already run at the HBM rate and stay double-buffered.
-  static constexpr int STAGES = SINGLE ? 1 : 2;
+  // Two stage buffers per workgroup: the next chunk loads under this chunk's MFMAs.
   // UPF (fused bilinear upsample, see the kernel): the low-res pixels one chunk of `up` channels is interpolated
   // from -- at most TH/2+2 rows x 18 columns (checked for every tile origin and size up to 4096) of P*32-byte
   // records -- staged by LDS-DMA two chunks ahead, double buffered.
@@ -158,7 +153,7 @@ struct ConvCfg {
   static constexpr int LS_PIECES = (LS_PX * LS_REC + 1023) / 1024;
   static constexpr int LS_BYTES = UPF ? LS_PIECES * 1024 : 0;
   static constexpr int LS_ITERS = (LS_PIECES + WAVES - 1) / WAVES;
-  static constexpr int LDS_BYTES = STAGES * BUF_BYTES + 2 * LS_BYTES;
+  static constexpr int LDS_BYTES = 2 * BUF_BYTES + 2 * LS_BYTES;
   static constexpr int SLAB_PIECES = SLAB_BYTES / 1024;   // one LDS-DMA wave-instruction = 1 KiB
   static_assert(U == 2 || U == 4, "unit count per pixel");
   static_assert(SLAB_BYTES % 1024 == 0, "slab must be a whole number of 1 KiB DMA pieces");
@@ -362,23 +357,18 @@ __device__ __forceinline__ void pack_store_rows8(const float (&v)[16], half_t* d
 constexpr int HEAD_MAX_CLASSES = 16;
 constexpr int HEAD_FUSED_MAX_CLASSES = 8;   // the fused head keeps all logits in registers
 
-// the exact-mode fused-head kernel runs single-staged, two workgroups per CU (see ConvCfg::STAGES)
-template <int P, bool HEAD> constexpr bool conv_single_stage() { return HEAD && P == 2; }
-
 // UPF = fused bilinear upsample (reference unetpp.py:76,112-116: cat([skip, self.up(low)])): the second source `in1`
 // is then the LOW-resolution tensor [N][C1/16][H/2][W/2][P][16] itself; the loader interpolates each chunk's halo
 // image from it (align_corners=True: src = dst*(in-1)/(out-1), same arithmetic as upsample2x_kernel) instead of
 // fetching a materialised `up` tensor: per tile and chunk, <= 10 x 18 low-res pixel records arrive by LDS-DMA two
 // chunks ahead, and while chunk c multiplies, the waves build chunk c+1's halo image from them (VALU + ds_write
 // beside the MFMAs).  The `up` tensor is never written or read: -2.4 GB of the 12.7 GB step at level 0.
-// ZINIT: the accumulators of a tile start from a.zinit (the low-resolution half of a decoder conv, tapmm_ws.h)
-// instead of zero; K then runs over the skip channels only.
-template <int P, int KC, int NW, int MW, int WAVES, bool POOL, bool HEAD = false, bool UPF = false, bool ZINIT = false>
-__global__ __launch_bounds__(WAVES * 64, (conv_single_stage<P, HEAD>() ? 2 : 1))
+template <int P, int KC, int NW, int MW, int WAVES, bool POOL, bool HEAD = false, bool UPF = false>
+__global__ __launch_bounds__(WAVES * 64, 1)
 void conv3x3_bias_relu_kernel(ConvArgs a) {
   touch_kernarg_lines<ConvArgs>();
-  using C = ConvCfg<P, KC, NW, MW, WAVES, conv_single_stage<P, HEAD>(), UPF>;
-  static_assert(!UPF || (!POOL && !HEAD && KC == 16 && MW == 2 && !conv_single_stage<P, HEAD>()), "fused upsample: plain 16-row tiles only");
+  using C = ConvCfg<P, KC, NW, MW, WAVES, UPF>;
+  static_assert(!UPF || (!POOL && !HEAD && KC == 16 && MW == 2), "fused upsample: plain 16-row tiles only");
   constexpr int NT = C::NT, TH = C::TH, TW = C::TW, HALO_W = C::HALO_W;
   constexpr int KG = C::KG, BN = C::BN, PPP = C::PPP;
   constexpr int ITERS = C::HALO_ITERS;
@@ -510,7 +500,7 @@ void conv3x3_bias_relu_kernel(ConvArgs a) {
     else if (!UPF) blds16(rsrc1, voff1[it], (c - nch0) * (KC / 16) * (int)plane_bytes1, dst);
   };
   // UPF: staging piece `it` of this wave for up-chunk c -> staging buffer (c & 1)
-  const int ls_base = C::STAGES * C::BUF_BYTES;
+  const int ls_base = 2 * C::BUF_BYTES;
   auto ls_dma_one = [&](int c, int it) {
     const int piece = wave + it * WAVES;
     if (C::LS_PIECES % WAVES != 0 && piece >= C::LS_PIECES) return;
@@ -632,41 +622,23 @@ void conv3x3_bias_relu_kernel(ConvArgs a) {
   for (int it = 0; it < ITERS; ++it) halo_dma_one(0, 0, it);
 #pragma unroll
   for (int p = 0; p < DMA_PER_WAVE; ++p) slab_dma_one(0, C::HALO_BYTES, p);
-  constexpr int STAGES = C::STAGES;
-  if (STAGES == 2) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
 
-  int g = 0;   // global chunk counter: chunk g lives in stage buffer g & 1 (two stages) or 0 (one)
+  int g = 0;   // global chunk counter: chunk g lives in stage buffer g & 1
   for (;;) {
 #pragma unroll
     for (int m = 0; m < MW; ++m)
 #pragma unroll
-      for (int j = 0; j < NW; ++j) {
-        if (ZINIT) {      // lane = pixel, registers 4q..4q+3 = channels 8q + 4h + (0..3) of the 32-block: four 16-byte loads
-          typedef __attribute__((ext_vector_type(4))) float f32x4;
-          const int gy = cur_y0 + wave * MW + m, gx = cur_x0 + (lane & 31);
-          const bool in = gy < H && gx < W;
-          const float* zp = a.zinit + (((size_t)cur_n * (a.Cout >> 5) + ((cur_ct * BN + j * 32) >> 5)) * ((size_t)H * W) + (size_t)gy * W + gx) * 32 + 4 * (lane >> 5);
+      for (int j = 0; j < NW; ++j)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-            if (in) z4 = *(const f32x4*)(zp + 8 * q);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[m][j][4 * q + i] = z4[i];
-          }
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[m][j][r] = 0.f;
-        }
-      }
+        for (int r = 0; r < 16; ++r) acc[m][j][r] = 0.f;
 
     const int next_tile = tile + (int)gridDim.x;
     const bool have_next = next_tile < total_tiles;
     for (int c = 0; c < a.nchunks; ++c, ++g) {
-      char* cur = smem + (STAGES == 2 ? (g & 1) : 0) * C::BUF_BYTES;
-      const int nxt_halo = (STAGES == 2 ? ((g & 1) ^ 1) : 0) * C::BUF_BYTES;
+      char* cur = smem + (g & 1) * C::BUF_BYTES;
+      const int nxt_halo = ((g & 1) ^ 1) * C::BUF_BYTES;
       const int nxt_slab = nxt_halo + C::HALO_BYTES;
       const bool last = c + 1 == a.nchunks;
       const bool more = !last || have_next;
@@ -693,10 +665,6 @@ void conv3x3_bias_relu_kernel(ConvArgs a) {
       constexpr int SPREAD = (NW == 1) ? UNETPP_SPREAD_NW1 : NSTEPS - 1;
       constexpr int HPS = (ITERS + SPREAD - 1) / SPREAD;          // halo items issued per step
       constexpr int DPS = (DMA_PER_WAVE + SPREAD - 1) / SPREAD;   // DMA pieces issued per step
-      if (STAGES == 1) {      // the chunk's requests went out after the previous chunk's MFMAs (or in the prologue)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-      }
       Frag f0, f1;
       load_frags(f0, halo, slab, 0);
 #pragma unroll
@@ -704,7 +672,7 @@ void conv3x3_bias_relu_kernel(ConvArgs a) {
         Frag& fc = (st & 1) ? f1 : f0;
         Frag& fn = (st & 1) ? f0 : f1;
         if (st + 1 < NSTEPS) load_frags(fn, halo, slab, st + 1);
-        if (STAGES == 2 && more) {
+        if (more) {
 #pragma unroll
           for (int k = st * HPS; k < (st + 1) * HPS; ++k)
             if (k < ITERS) halo_dma_one(pc, nxt_halo, k);
@@ -725,18 +693,8 @@ void conv3x3_bias_relu_kernel(ConvArgs a) {
         run_mfma(fc);
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (STAGES == 2) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces have landed
-        __syncthreads();
-      } else {
-        __syncthreads();                                    // every wave has read its last fragments: the stage is free
-        if (more) {
-#pragma unroll
-          for (int k = 0; k < ITERS; ++k) halo_dma_one(pc, 0, k);
-#pragma unroll
-          for (int k = 0; k < DMA_PER_WAVE; ++k) slab_dma_one(pc, C::HALO_BYTES, k);
-        }
-      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces have landed
+      __syncthreads();
     }
 
     // ---- epilogue straight from registers: scale, bias, ReLU, fp16 (hi/lo) packing, one

@@ -11,7 +11,7 @@
 //                         pixels, K = Cup, 9*Cout "virtual channels", raw fp32 accumulators (weights pre-scaled by the
 //                         layer's per-channel power of two, hi/lo split operands, 3 MFMAs per product as everywhere)
 //   2. upsum_kernel       Z[p][co] = sum_{tap: p+tap inside} bilinear(Y[.][tap*Cout + co])(p + tap)   fp32, align_corners=True
-//   3. conv3x3_bias_relu_kernel<..., ZINIT>  over the skip channels only, accumulators initialised with Z
+//   3. conv3x3_ws_kernel  over the skip channels only, accumulators initialised with Z (ConvArgs::zinit)
 //
 // Flops: 9*Cout*(Cs + Cup) per pixel -> 9*Cout*Cs + 9*Cout*Cup/4: half for Cup = 2 Cs (UNet++ decoder), -26 % of the
 // whole network.  The zero padding is that of the reference: up(low) is zero outside the high-res image, so a tap that

@@ -65,6 +65,7 @@ struct ConvLayer {
   half_t* tapw = nullptr;       // tapmm: packed weights of the up channels
   bool c0f = false;             // conv0_0.conv2 computing conv0_0.conv1 itself from the caller's input (conv3x3_ws.h, C0F)
   bool upf = false;             // in2 is the LOW-resolution tensor: the loader does the bilinear x2 itself (no `up` tensor)
+  bool ws = false;              // runs in the wave-specialised kernel (conv3x3_ws.h), else the lock-step one: fixes the weight layout too
   size_t w_off = 0, b_off = 0;  // float offsets inside the canonical blob payload
   int KC = 16, NW = 1, MW = 2, WAVES = 8;
   int nchunks = 1;
@@ -140,14 +141,9 @@ struct unetpp_engine {
   std::map<std::tuple<int, int, int>, void*> resize_tabs;
   half_t* c1w = nullptr;          // fused first block: conv0_0.conv1 as MFMA A fragments (conv0_pack_kernel)
   int c0f_conv1 = -1;             // index of conv0_0.conv1 in `convs` when the first block is fused, else -1
-  int ws_max_cout = 512;          // largest Cout the 8-row wave-specialised tiles are used for (UNETPP_WS_MAX_COUT; measured: every layer gains 1-8 %)
-  bool ws64 = true;               // ... and for the Cout = 64 layers (UNETPP_NO_WS64=1: the lock-step kernel there)
-  bool ws_cat = false;            // ... and for convs over two full-resolution sources (exact8; UNETPP_WS_CAT=1: in exact too)
-  bool use_ws = true;             // exact-mode convs in the wave-specialised kernel (UNETPP_NO_WS=1: the lock-step one)
   unsigned* d_status = nullptr;   // sticky range flags (UNETPP_STATUS_*), one word inside the arena
   int ksplit_max = 16, ksplit_min_chunks = 4, ksplit_gate = 4;      // split-K of small launches (UNETPP_KSPLIT=max[,min chunks]; 1 = off)
   int t_kpart = -1, t_kcnt = -1;  // per slot: partial sums and arrival counters of the split tiles
-  bool pair9 = true;              // EXACT8: ninth taps of consecutive chunks share an MFMA (UNETPP_NO_PAIR9=1: off; read at create)
   bool kcnt_dirty = false;        // a forward returned early: its split launches may have left counters behind
 };
 
@@ -237,15 +233,15 @@ hipError_t allow_full_lds(const void* kernel, int device) {
   return st;
 }
 
-template <int P, int KC, int NW, int MW, int WAVES, bool POOL, bool HEAD, bool UPF = false, bool ZINIT = false>
+template <int P, int KC, int NW, int MW, int WAVES, bool POOL, bool HEAD, bool UPF = false>
 hipError_t launch_conv_k(const LaunchCtx& cx, const ConvArgs& a, hipStream_t s) {
-  using C = ConvCfg<P, KC, NW, MW, WAVES, conv_single_stage<P, HEAD>(), UPF>;
+  using C = ConvCfg<P, KC, NW, MW, WAVES, UPF>;
   const int lds = C::LDS_BYTES + a.Cout * 8 + (HEAD ? ((a.head_C * 33 * 4 + 15) / 16) * 16 : 0);
   // persistent workgroups: as many as are resident at once, each walks tiles blockIdx, +grid, ...
   const int total = a.N * a.tiles_x * a.tiles_y * a.nct;
   const int per_cu = std::max(1, std::min(2, (160 * 1024) / lds));
   dim3 grid((unsigned)std::min(total, cx.num_cus * per_cu));
-  auto k = conv3x3_bias_relu_kernel<P, KC, NW, MW, WAVES, POOL, HEAD, UPF, ZINIT>;
+  auto k = conv3x3_bias_relu_kernel<P, KC, NW, MW, WAVES, POOL, HEAD, UPF>;
   hipError_t st = allow_full_lds((const void*)k, cx.device);
   if (st != hipSuccess) return st;
   hipLaunchKernelGGL(k, grid, dim3(C::NT), lds, s, a);
@@ -311,21 +307,22 @@ hipError_t launch_ws(const LaunchCtx& cx, int P, bool x8, const ConvArgs& a, boo
 
 template <int P, int KC, int NW, int MW, int WAVES>
 hipError_t launch_conv_cfg(const LaunchCtx& cx, const ConvArgs& a, bool pool, bool head, bool upf, hipStream_t s) {
-  if constexpr (NW == 1 && MW == 2 && KC == 16) {      // fused upsample: built for the narrow full-resolution tiles
-    if (upf) return (pool || head) ? hipErrorInvalidValue : launch_conv_k<P, KC, NW, MW, WAVES, false, false, true>(cx, a, s);
+  if (a.zinit) return hipErrorInvalidValue;     // accumulator start values (tapmm_ws.h): the wave-specialised kernel only
+  if constexpr (P == 2) {      // exact: only SimpleUNet's two-source decoder convs run here, with nothing fused
+    if (pool || head || upf) return hipErrorInvalidValue;
+  } else {
+    if constexpr (NW == 1 && MW == 2 && KC == 16) {      // fused upsample: built for the narrow full-resolution tiles
+      if (upf) return (pool || head) ? hipErrorInvalidValue : launch_conv_k<P, KC, NW, MW, WAVES, false, false, true>(cx, a, s);
+    }
+    if (upf) return hipErrorInvalidValue;
+    if constexpr (NW == 1) {
+      if (head) return launch_conv_k<P, KC, NW, MW, WAVES, false, true>(cx, a, s);
+    }
+    if constexpr (MW == 2) {     // the fused 2x2 pool needs both rows of a window in one wave
+      if (pool) return launch_conv_k<P, KC, NW, MW, WAVES, true, false>(cx, a, s);
+    }
+    if (pool) return hipErrorInvalidValue;
   }
-  if (upf) return hipErrorInvalidValue;
-  if constexpr (P == 2 && NW == 2 && MW == 2 && KC == 16) {     // accumulators start from the low-resolution half (tapmm_ws.h)
-    if (a.zinit) return (pool || head) ? hipErrorInvalidValue : launch_conv_k<P, KC, NW, MW, WAVES, false, false, false, true>(cx, a, s);
-  }
-  if (a.zinit) return hipErrorInvalidValue;
-  if constexpr (NW == 1) {
-    if (head) return launch_conv_k<P, KC, NW, MW, WAVES, false, true>(cx, a, s);
-  }
-  if constexpr (MW == 2) {     // the fused 2x2 pool needs both rows of a window in one wave
-    if (pool) return launch_conv_k<P, KC, NW, MW, WAVES, true, false>(cx, a, s);
-  }
-  if (pool) return hipErrorInvalidValue;
   return launch_conv_k<P, KC, NW, MW, WAVES, false, false>(cx, a, s);
 }
 
@@ -337,7 +334,6 @@ hipError_t launch_conv(const LaunchCtx& cx, int P, const ConvLayer& L, int mw, c
   CASE(1, 32, 2, 2, 8)
   CASE(1, 16, 2, 2, 8)
   CASE(1, 16, 4, 2, 8)
-  CASE(2, 16, 1, 2, 8)
   CASE(2, 16, 2, 2, 8)
   CASE(1, 16, 2, 1, 8)
   CASE(1, 32, 2, 1, 8)
@@ -466,9 +462,9 @@ struct Builder {
 };
 
 void build_nested(unetpp_engine* e, Builder& b) {
-  // exact mode: the first ConvBlock runs as ONE launch from the caller's tensor (no input copy, no conv0_0.conv1 launch,
-  // no x0_0a tensor): conv3x3_ws.h, C0F.  UNETPP_NO_C0F=1 keeps the three launches (A/B measurements).
-  const bool c0f = e->P == 2 && e->use_ws && !getenv("UNETPP_NO_C0F");
+  // exact modes: the first ConvBlock runs as ONE launch from the caller's tensor (no input copy, no conv0_0.conv1 launch,
+  // no x0_0a tensor): conv3x3_ws.h, C0F.
+  const bool c0f = e->P == 2;
   if (!c0f) { Op cv; cv.kind = OP_CONVERT; e->ops.push_back(cv); }
   e->t_in8 = b.tensor("in8", 8, 0, c0f);            // fused first block: neither the fp16 input copy nor x0_0a exists
   int x[5], xa[5], pooled[4], up[4], d[4], da[4];
@@ -488,13 +484,7 @@ void build_nested(unetpp_engine* e, Builder& b) {
     char nm[32], tn[32];
     snprintf(tn, sizeof tn, "x%d_%d", l, 4 - l);
     const int low = l == 3 ? x[4] : d[l + 1];
-    // Level 0 (Cout = 32: narrow tiles, HBM co-bound): the decoder conv interpolates its `up` channels itself from
-    // the low-res tensor (conv3x3_mfma.h, UPF) -- no upsample launch, no `up` tensor.  UNETPP_NO_UPF=1 keeps the
-    // separate kernel (A/B measurements).
-    // (EXACT8: every level that does not take the low-resolution GEMM below interpolates in its loader -- the separate
-    // upsample kernel and the two-source loader do not know the 8-bit planes)
-    const bool upf = e->x8 || (!getenv("UNETPP_NO_UPF") && (l == 0 || (l == 1 && e->P == 2 && e->ws64 && NB[1] <= e->ws_max_cout && !getenv("UNETPP_NO_UPF1"))));      // level 1: only the wave-specialised kernel has the fused loader for Cout = 64 (layer_uses_ws)
-    // Levels 2-3 (exact mode): the up channels are multiplied at LOW resolution and interpolated afterwards
+    // Levels 2-3 (exact modes): the up channels are multiplied at LOW resolution and interpolated afterwards
     // (tapmm_ws.h: half the flops of the layer); UNETPP_TAPMM=levels overrides, e.g. "" (off) or "123".
     const char* tl = getenv("UNETPP_TAPMM");
     // (the GEMM's 128-wide virtual-channel tiles need 9 * Cout % 128 == 0: levels 2 and 3; at level 1 the fp32
@@ -515,6 +505,10 @@ void build_nested(unetpp_engine* e, Builder& b) {
       b.conv(std::string(nm) + ".conv2", NB[l], da[l], -1, d[l]);
       continue;
     }
+    // Every other level of the exact modes, and level 0 of fast (Cout = 32: narrow tiles, HBM co-bound): the decoder
+    // conv interpolates its `up` channels itself from the low-res tensor (conv3x3_ws.h / conv3x3_mfma.h, UPF) -- no
+    // upsample launch, no `up` tensor.  Levels 1-3 of fast keep the separate upsample kernel.
+    const bool upf = e->P == 2 || l == 0;
     if (!upf) up[l] = b.tensor(std::string(tn) + "u", NB[l + 1], l);
     da[l] = b.tensor(std::string(tn) + "a", NB[l], l);
     d[l] = b.tensor(tn, NB[l], l);
@@ -609,13 +603,6 @@ int unetpp_create(const unetpp_config* cfg, unetpp_engine** out) {
                 cfg->max_batch, cfg->max_h, cfg->max_w, mult);
   if (cfg->precision != UNETPP_PREC_EXACT && cfg->precision != UNETPP_PREC_FAST && cfg->precision != UNETPP_PREC_EXACT8)
     return fail(nullptr, UNETPP_E_INVALID, "precision=%d unknown", cfg->precision);
-  if (cfg->precision == UNETPP_PREC_EXACT8) {
-    // EXACT8 exists in the wave-specialised kernels only: no lock-step / unfused alternatives to switch to
-    // (SimpleUNet: every conv through the wave-specialised kernel -- two full-resolution sources included --, the transposed
-    // convs on fp16 terms decoded from the 8-bit residual plane, convt2x2_mfma.h)
-    for (const char* sw : {"UNETPP_NO_WS", "UNETPP_NO_WS64", "UNETPP_WS_MAX_COUT", "UNETPP_NO_C0F", "UNETPP_NO_UPF", "UNETPP_NO_UPF1"})
-      if (getenv(sw)) return fail(nullptr, UNETPP_E_UNSUPPORTED, "%s has no meaning with precision EXACT8", sw);
-  }
   // the conv loader addresses one image of one tensor with 32-bit byte offsets (buffer loads): the largest
   // full-resolution tensor has 64 channels x (1 or 2) fp16 planes
   if ((double)cfg->max_h * cfg->max_w * 64 * 2 * (cfg->precision == UNETPP_PREC_FAST ? 1 : 2) >= 2147483648.0)
@@ -633,20 +620,13 @@ int unetpp_create(const unetpp_config* cfg, unetpp_engine** out) {
     if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) e->num_cus = prop.multiProcessorCount;
   }
   e->cfg = *cfg;
-  e->use_ws = !getenv("UNETPP_NO_WS");
-  e->ws64 = e->use_ws && !getenv("UNETPP_NO_WS64");
-  if (const char* mc = getenv("UNETPP_WS_MAX_COUT")) e->ws_max_cout = atoi(mc);
   e->P = cfg->precision == UNETPP_PREC_FAST ? 1 : 2;
   e->x8 = cfg->precision == UNETPP_PREC_EXACT8;
-  // convs over two full-resolution sources: the wave-specialised kernel in exact8 (the only kernel with that arithmetic);
-  // exact keeps the lock-step kernel (same speed, and its results do not depend on a split-K plan) unless UNETPP_WS_CAT=1
-  { const char* c = getenv("UNETPP_WS_CAT"); e->ws_cat = e->use_ws && (e->x8 || (c && c[0] == '1')); }
   e->mb = (cfg->micro_batch > 0 && cfg->micro_batch < cfg->max_batch) ? cfg->micro_batch : cfg->max_batch;
   e->nstreams = std::max(1, std::min(4, cfg->streams));
   if (e->mb >= cfg->max_batch) e->nstreams = 1;      // a single pass has nothing to overlap with
   const int P = e->P;
 
-  e->pair9 = !getenv("UNETPP_NO_PAIR9");
   if (const char* k = getenv("UNETPP_KSPLIT")) {
     e->ksplit_max = std::max(1, atoi(k));
     if (const char* c = strchr(k, ',')) {
@@ -656,7 +636,18 @@ int unetpp_create(const unetpp_config* cfg, unetpp_engine** out) {
   }
   Builder b{e};
   if (cfg->arch == UNETPP_ARCH_NESTED) build_nested(e, b); else build_simple(e, b);
-  if (e->P == 2 && e->use_ws && e->ksplit_max > 1) {
+  // The kernel of every conv, fixed here for the engine's lifetime (it also decides the weight layout, see repack): in the
+  // exact modes the wave-specialised one, except SimpleUNet's two-source decoder convs in exact, which stay on the
+  // lock-step kernel (same speed, and results that do not depend on a split-K plan: DESIGN.md 5.6); fast: lock-step.
+  for (ConvLayer& L : e->convs) L.ws = P == 2 && (L.in2 < 0 || L.upf || e->x8);
+  if (e->x8)      // EXACT8 exists in the wave-specialised kernel only: every conv must have a variant there (launch_ws_x)
+    for (const ConvLayer& L : e->convs)
+      if (!L.ws || (L.cout != 32 && L.cout % 64) || (L.in2 >= 0 && (L.do_pool || (!L.upf && L.cout % 64)))) {
+        const std::string name = L.name;
+        delete e;
+        return fail(nullptr, UNETPP_E_UNSUPPORTED, "internal: %s has no EXACT8 kernel", name.c_str());
+      }
+  if (P == 2 && e->ksplit_max > 1) {
     // at most num_cus workgroups take part in a split launch, each with 4 consumer waves x 16 KB of raw accumulators
     e->t_kpart = (int)e->tensors.size();
     { Tensor t; t.name = "ksplit.partials"; t.off = b.act; e->tensors.push_back(t); b.act += align_up((size_t)e->num_cus * 4 * 16384, 256); }
@@ -756,19 +747,13 @@ void unetpp_destroy(unetpp_engine* e) {
 
 size_t unetpp_workspace_bytes(const unetpp_engine* e) { return e ? e->arena_bytes : 0; }
 
-// which conv layers run in the wave-specialised kernel (a property of the engine and the layer, not of a call)
 #ifdef UNETPP_WS_DBG
 static unsigned long long* unetpp_dbg_stamp_buf = nullptr;     // measurement build: in-kernel stamps (scripts/ws_stamps.sh)
 #endif
-static bool layer_uses_ws(const unetpp_engine* e, const ConvLayer& L) {
-  // two full-resolution sources (SimpleUNet's decoder conv1): whole 16-channel records in both, same kernel (exact8, or UNETPP_WS_CAT=1)
-  const bool cat_ok = L.in2 >= 0 && !L.upf && e->ws_cat && e->tensors[L.in].C % 16 == 0 && e->tensors[L.in2].C % 16 == 0 && !L.do_pool && L.cout % 64 == 0;
-  return e->use_ws && e->P == 2 && (L.cout == 32 || (e->ws64 && L.cout >= 64 && L.cout <= e->ws_max_cout)) && (L.in2 < 0 || L.upf || cat_ok);
-}
 
 // EXACT8: layers whose chunk count is even pair the ninth taps of consecutive chunks (conv3x3_ws.h); the split-K plan then
 // only makes shares with an even number of chunks (launch_ws_k)
-static bool x8_pair9(const unetpp_engine* e, const ConvLayer& L) { return e->x8 && e->pair9 && L.nchunks % 2 == 0; }
+static bool x8_pair9(const unetpp_engine* e, const ConvLayer& L) { return e->x8 && L.nchunks % 2 == 0; }
 
 static int repack(unetpp_engine* e, hipStream_t s) {
   const int P = e->P;
@@ -785,7 +770,7 @@ static int repack(unetpp_engine* e, hipStream_t s) {
     }
     long long units = (long long)(L.cout / BN) * L.nchunks * P * 9 * (L.KC / 8) * BN;
     hipLaunchKernelGGL(weight_pack_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, w, L.mult, L.cin_real,
-                       L.cout, P, L.KC, BN, L.nchunks, L.wpk, units, layer_uses_ws(e, L) ? 1 : 0);
+                       L.cout, P, L.KC, BN, L.nchunks, L.wpk, units, L.ws ? 1 : 0);
   }
   for (auto& L : e->convs) {
     if (L.zt < 0) continue;
@@ -1002,19 +987,17 @@ int unetpp_forward_ex(unetpp_engine* e, const void* dev_input, int in_format, in
           bytes += px * ((lg ? 4.0 * C : 0) + (pr ? 4.0 * C : 0) + (mk ? 1 : 0) + (cb ? 1 : 0) + (tpe ? 1 : 0));
           head_done = true;
         }
-        // exact mode, Cout = 32 or a multiple of 64, single source (or skip + fused upsample): the wave-specialised kernel
-        const bool ws = layer_uses_ws(e, L);
         char lbl[160];
         // labels end in the kernel's full template argument list, as rocprofv3 prints it (bench.py matches on it)
         auto tf = [](bool v) { return v ? "true" : "false"; };
-        if (ws) snprintf(lbl, sizeof lbl, "%s%s%s%s|conv3x3_ws_kernel<%d, %s, %s, %s, %s, %d, %d, %s, %s>", L.c0f ? "input+conv0_0.conv1+" : "", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "", P, tf(L.do_pool), tf(head), tf(L.upf), tf(L.c0f), L.cout == 32 ? 1 : 2, L.cout == 32 ? 4 : 2, tf(e->x8), tf(L.in2 >= 0 && !L.upf));
-        else snprintf(lbl, sizeof lbl, "%s%s%s|conv3x3_bias_relu_kernel<%d, %d, %d, %d, %d, %s, %s, %s, %s>", L.name.c_str(), L.upf ? "+up" : (L.zt >= 0 ? ".skip+z" : ""), head ? "+final+argmax" : "", P, L.KC, L.NW, mw, L.WAVES, tf(L.do_pool), tf(head), tf(L.upf), tf(L.zt >= 0));
+        if (L.ws) snprintf(lbl, sizeof lbl, "%s%s%s%s|conv3x3_ws_kernel<%d, %s, %s, %s, %s, %d, %d, %s, %s>", L.c0f ? "input+conv0_0.conv1+" : "", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "", P, tf(L.do_pool), tf(head), tf(L.upf), tf(L.c0f), L.cout == 32 ? 1 : 2, L.cout == 32 ? 4 : 2, tf(e->x8), tf(L.in2 >= 0 && !L.upf));
+        else snprintf(lbl, sizeof lbl, "%s%s%s|conv3x3_bias_relu_kernel<%d, %d, %d, %d, %d, %s, %s, %s>", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "", P, L.KC, L.NW, mw, L.WAVES, tf(L.do_pool), tf(head), tf(L.upf));
         Lx.run(lbl, flops, bytes, [&] {
-          return ws ? launch_ws(LaunchCtx{e->cfg.device, e->num_cus, e->ksplit_max, e->ksplit_min_chunks, e->ksplit_gate}, P, e->x8, a, L.do_pool, head, L.upf, L.c0f, s)
+          return L.ws ? launch_ws(LaunchCtx{e->cfg.device, e->num_cus, e->ksplit_max, e->ksplit_min_chunks, e->ksplit_gate}, P, e->x8, a, L.do_pool, head, L.upf, L.c0f, s)
                     : launch_conv(LaunchCtx{e->cfg.device, e->num_cus}, P, L, mw, a, head, s);
         });
 #ifdef UNETPP_WS_DBG
-        if (stamp_this && ws) {
+        if (stamp_this && L.ws) {
           static int printed = 0;
           std::vector<unsigned long long> hs(1024 * 32 * 5);
           (void)hipStreamSynchronize(s);
@@ -1089,7 +1072,7 @@ int unetpp_forward_ex(unetpp_engine* e, const void* dev_input, int in_format, in
             return hipSuccess;
           });
         }
-      } else if (op.kind == OP_UP) {
+      } else if (op.kind == OP_UP) {      // fast only: the exact modes interpolate in the decoder conv's loader (UPF)
         const Tensor& low = e->tensors[op.idx];
         const Tensor& dst = e->tensors[op.out];
         const int H = h >> dst.lvl, W = w >> dst.lvl;
@@ -1100,10 +1083,10 @@ int unetpp_forward_ex(unetpp_engine* e, const void* dev_input, int in_format, in
         const size_t up_lds = (size_t)3 * (seg_w / 2 + 2) * P * 32;      // staged low-res rows of one segment
         const int up_threads = seg_w * 2 * P >= 1024 ? 512 : (seg_w * 2 * P >= 256 ? 256 : 128);   // one item = both rows of a piece
         char nm[64];
-        snprintf(nm, sizeof nm, "up%d|upsample2x_kernel<%d>", dst.lvl, P);
+        snprintf(nm, sizeof nm, "up%d|upsample2x_kernel<1>", dst.lvl);
         Lx.run(nm, px * low.C * 8, bytes, [&] {
-          if (P == 2) hipLaunchKernelGGL(upsample2x_kernel<2>, dim3((unsigned)((H / 2) * nseg), (unsigned)(nb * (low.C / 16))), dim3(up_threads), up_lds, s, tp(op.idx), H, W, tp(op.out));
-          else hipLaunchKernelGGL(upsample2x_kernel<1>, dim3((unsigned)((H / 2) * nseg), (unsigned)(nb * (low.C / 16))), dim3(up_threads), up_lds, s, tp(op.idx), H, W, tp(op.out));
+          if (P != 1) return hipErrorInvalidValue;
+          hipLaunchKernelGGL(upsample2x_kernel<1>, dim3((unsigned)((H / 2) * nseg), (unsigned)(nb * (low.C / 16))), dim3(up_threads), up_lds, s, tp(op.idx), H, W, tp(op.out));
           return hipSuccess;
         });
       } else if (op.kind == OP_CONVT) {

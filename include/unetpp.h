@@ -165,6 +165,40 @@ typedef struct unetpp_outputs {
 int unetpp_forward_ex(unetpp_engine* e, const void* dev_input, int in_format, int batch, int h, int w,
                       const unetpp_outputs* out, void* stream);
 
+/* ---- deep-supervision outputs and pruned inference (NestedUNet(deep_supervision=True)) ------------------
+ * The list [out, out1, out2, out3] that the reference's forward builds with deep supervision
+ * (src/models/unetpp.py:121-133, BatchNorm with its eval statistics):
+ *   out_k = F.interpolate(dsK(x_k), size=(H, W), mode='bilinear', align_corners=True)
+ *   k = 1: ds1_3 on x1_3 (64 channels)   k = 2: ds2_2 on x2_2 (128)   k = 3: ds3_1 on x3_1 (256)
+ * computed as the 1x1 conv in fp32 at (H >> k, W >> k) and ONE bilinear interpolation to (H, W) with ATen's fp32 index rule,
+ * followed by the same epilogue as the main head (logits, softmax probabilities, first-max argmax, class masks and
+ * rules of unetpp_outputs).  NestedUNet engines only.
+ *
+ * unetpp_ds_blob_bytes: size of the heads' blob, a 32-byte header {magic 'UNDS', version 1, num_classes, 3, 0,0,0,0}
+ * followed by fp32 ds3_1.weight [C][256], ds3_1.bias [C], ds2_2.weight [C][128], ds2_2.bias [C], ds1_3.weight [C][64],
+ * ds1_3.bias [C] (the module's definition order, src/models/unetpp.py:87-91).  0 for num_classes < 1.
+ *
+ * unetpp_load_ds_heads: uploads that blob from host memory.  Synchronous, like unetpp_load_weights.  Allocates the
+ * heads and, per internal stream, a float32 scratch of micro_batch * sum_k C (max_h >> k) (max_w >> k) low-resolution
+ * logits outside the workspace that unetpp_workspace_bytes reports; unetpp_destroy frees them.  A non-finite value in
+ * the blob sets UNETPP_STATUS_NAN.  UNETPP_E_INVALID on a bad magic, size or class count.  The heads belong to the
+ * checkpoint of the main weights: a later unetpp_load_weights or unetpp_load_weights_device drops them, and outs[1..3]
+ * get UNETPP_E_STATE until they are loaded again.
+ *
+ * unetpp_forward_ds: one pass computing outs[k] (k = 0..3, the list [out, out1, out2, out3]); outs[k] == NULL skips
+ * output k.  outs[0] is exactly unetpp_forward_ex's output (bitwise the same results).  The network runs only as deep
+ * as the requested outputs need: with outs[0] == NULL it stops after the node of the smallest requested k, so
+ * decoder levels below it are never launched (pruned UNet++ inference).  The logits and probabilities of outs[1..3]
+ * must be 16-byte aligned and their masks 4-byte aligned (the kernel stores four pixels at once).
+ * Errors: UNETPP_E_UNSUPPORTED for UNETPP_ARCH_SIMPLE; UNETPP_E_INVALID when all four are NULL, a rule is bad or a
+ * buffer of outs[1..3] is misaligned;
+ * UNETPP_E_STATE when outs[1..3] is requested before unetpp_load_ds_heads (e.g. on an engine loaded with
+ * unetpp_load_weights_device only).  Asynchronous on `stream`, like unetpp_forward_ex. */
+size_t unetpp_ds_blob_bytes(int num_classes);
+int unetpp_load_ds_heads(unetpp_engine* e, const void* host_blob, size_t bytes);
+int unetpp_forward_ds(unetpp_engine* e, const void* dev_input, int in_format, int batch, int h, int w,
+                      const unetpp_outputs* const outs[4], void* stream);
+
 /* ---- mask statistics on the device -------------------------------------------
  * From a uint8 class-index mask [B,H,W] (e.g. the dev_mask of a forward): per-frame class pixel counts
  * (np.sum(mask_cable) / coverage, infer_two_stage_burr.py:333-340, src/utils/geometry_enhanced.py:151-152) and,

@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "unetpp_resize_linear_u8", "unetpp_resize_nearest_roi_u8", "unetpp_status",
     "unetpp_profile_enable", "unetpp_profile_count", "unetpp_profile_read", "unetpp_profile_name",
     "unetpp_profile_work", "unetpp_debug_read", "unetpp_debug_keep_intermediates",
+    "unetpp_ds_blob_bytes", "unetpp_load_ds_heads", "unetpp_forward_ds",
 ]
 
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
@@ -165,6 +166,10 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     lib.unetpp_debug_read.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), cs]
     lib.unetpp_debug_read.restype = ctypes.c_longlong
     lib.unetpp_debug_keep_intermediates.argtypes = [vp, ci]; lib.unetpp_debug_keep_intermediates.restype = ci
+    lib.unetpp_ds_blob_bytes.argtypes = [ci]; lib.unetpp_ds_blob_bytes.restype = cs
+    lib.unetpp_load_ds_heads.argtypes = [vp, vp, cs]; lib.unetpp_load_ds_heads.restype = ci
+    lib.unetpp_forward_ds.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.POINTER(ctypes.POINTER(Outputs)), vp]
+    lib.unetpp_forward_ds.restype = ci
     ver = lib.unetpp_version().decode()
     if ver.endswith(" +wsdbg") and os.environ.get("UNETPP_ALLOW_DBG_LIB"):
         ver = ver[:-len(" +wsdbg")]            # measurement build with phase ablations (scripts/ws_ablate.sh)

@@ -343,6 +343,29 @@ __global__ __launch_bounds__(1024) void upsample2x_kernel(const half_t* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
+// Epilogue of a head on one pixel's fp32 logits (lg[c] = -inf for c >= C): argmax (first maximal class, np.argmax),
+// then, when probabilities or a class rule are wanted, the fp32 softmax into pe[] and apply_rule (conv3x3_mfma.h).
+// Shared by head_generic_kernel and ds_upsample_kernel; pe[] is only written when want_probs || rule.
+__device__ __forceinline__ void head_epilogue(const float (&lg)[HEAD_FUSED_MAX_CLASSES], int C, bool want_probs, int rule,
+                                              float t_cable, float t_tape, float bg_margin, float ct_margin,
+                                              float (&pe)[HEAD_FUSED_MAX_CLASSES], int& besti, bool& is_cable, bool& is_tape) {
+  float best = lg[0];
+  besti = 0;
+#pragma unroll
+  for (int c = 1; c < HEAD_FUSED_MAX_CLASSES; ++c)
+    if (lg[c] > best) { best = lg[c]; besti = c; }
+  is_cable = besti == 1; is_tape = besti == 2;
+  if (want_probs || rule) {
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) { pe[c] = (c < C) ? expf(lg[c] - best) : 0.f; sum += pe[c]; }
+#pragma unroll
+    for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) pe[c] = pe[c] / sum;
+    if (rule) apply_rule(rule, pe[0], pe[1], pe[2], t_cable, t_tape, bg_margin, ct_margin, is_cable, is_tape);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Stand-alone 1x1 head: self.final = Conv2d(Cx, C, 1) in fp32 (NestedUNet unetpp.py:85,119 with Cx = 32 —
 // only in debug mode, normally fused into conv0_4.conv2 — and SimpleUNet simple_unet.py:92,124 with
 // Cx = 64), then softmax probabilities, argmax (first maximal class, np.argmax) and the class rules
@@ -398,23 +421,15 @@ __global__ void head_generic_kernel(const half_t* __restrict__ x, int Cx, const 
         lg[c] = s;
       }
   }
-  float best = lg[0];
-  int besti = 0;
-#pragma unroll
-  for (int c = 1; c < HEAD_FUSED_MAX_CLASSES; ++c)
-    if (lg[c] > best) { best = lg[c]; besti = c; }
-  bool is_cable = besti == 1, is_tape = besti == 2;
+  int besti;
+  bool is_cable, is_tape;
+  float pe[HEAD_FUSED_MAX_CLASSES];
+  head_epilogue(lg, C, probs != nullptr, rule, t_cable, t_tape, bg_margin, ct_margin, pe, besti, is_cable, is_tape);
   const size_t o = (size_t)n * hw + p;
-  if (probs || rule) {
-    float pe[HEAD_FUSED_MAX_CLASSES], sum = 0.f;
+  if (probs) {
 #pragma unroll
-    for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) { pe[c] = (c < C) ? expf(lg[c] - best) : 0.f; sum += pe[c]; }
-#pragma unroll
-    for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) {
-      pe[c] = pe[c] / sum;
-      if (probs && c < C) probs[((size_t)n * C + c) * hw + p] = pe[c];
-    }
-    if (rule) apply_rule(rule, pe[0], pe[1], pe[2], t_cable, t_tape, bg_margin, ct_margin, is_cable, is_tape);
+    for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c)
+      if (c < C) probs[((size_t)n * C + c) * hw + p] = pe[c];
   }
   if (logits) {
 #pragma unroll
@@ -424,6 +439,76 @@ __global__ void head_generic_kernel(const half_t* __restrict__ x, int Cx, const 
   if (mask) mask[o] = (uint8_t)besti;
   if (cable) cable[o] = is_cable;
   if (tape) tape[o] = is_tape;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Deep-supervision output k (reference unetpp.py:121-133): F.interpolate(dsK(xK), size=(H, W), mode='bilinear',
+// align_corners=True) of the fp32 low-resolution logits low[N][C][h][w] (head_generic_kernel, logits only) in ONE step
+// of ratio (H-1)/(h-1), then the head epilogue.  ATen's index rule (upsample_bilinear2d, compute_indices_weights_linear)
+// in fp32 without contraction: s = float(in-1)/float(out-1) (from the host), src = s * dst, i0 = min(int(src), in-1),
+// i1 = i0 + (i0 < in-1), l1 = clamp(src - i0, 0, 1), l0 = 1 - l1; value = (v00 l0x + v01 l1x) l0y + (v10 l0x + v11 l1x) l1y.
+// Written as plain operators under the pragma below: __fmul_rn / __fsub_rn / __fadd_rn are plain operators in header
+// functions outside its scope, and the backend fuses them into v_fma after inlining (src - i0 would round once, not twice).
+// One thread = 4 consecutive pixels of one output row (W % 16 == 0): one 16-byte store per class plane of logits and
+// probabilities, one 4-byte store per byte mask.  The low-res logits (<= 2 MB per 512x512 frame) are read from L2.
+__global__ __launch_bounds__(256) void ds_upsample_kernel(const float* __restrict__ low, int C, int h, int w, int N, int H, int W,
+                                                          float sy, float sx, float* __restrict__ logits, float* __restrict__ probs,
+                                                          uint8_t* __restrict__ mask, uint8_t* __restrict__ cable,
+                                                          uint8_t* __restrict__ tape, int rule, float t_cable, float t_tape,
+                                                          float bg_margin, float ct_margin) {
+#pragma clang fp contract(off)
+  const int wq = W >> 2;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * H * wq) return;
+  const int xq = (int)(i % wq);
+  const size_t t = i / wq;
+  const int y = (int)(t % H), n = (int)(t / H);
+  const float fy = sy * (float)y;
+  const int y0 = min((int)fy, h - 1);                      // fy >= 0: truncation is floor
+  const int y1 = y0 + (y0 < h - 1 ? 1 : 0);
+  const float ly1 = fminf(fmaxf(fy - (float)y0, 0.f), 1.f), ly0 = 1.f - ly1;
+  const size_t hw = (size_t)h * w, HW = (size_t)H * W;
+  const float* r0 = low + (size_t)n * C * hw + (size_t)y0 * w;
+  const float* r1 = low + (size_t)n * C * hw + (size_t)y1 * w;
+  float lg[4][HEAD_FUSED_MAX_CLASSES], pe[4][HEAD_FUSED_MAX_CLASSES];
+  int besti[4];
+  bool is_cable[4], is_tape[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float fx = sx * (float)(4 * xq + j);
+    const int x0 = min((int)fx, w - 1);
+    const int x1 = x0 + (x0 < w - 1 ? 1 : 0);
+    const float lx1 = fminf(fmaxf(fx - (float)x0, 0.f), 1.f), lx0 = 1.f - lx1;
+#pragma unroll
+    for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) {
+      if (c < C) {
+        const float top = r0[c * hw + x0] * lx0 + r0[c * hw + x1] * lx1;
+        const float bot = r1[c * hw + x0] * lx0 + r1[c * hw + x1] * lx1;
+        lg[j][c] = top * ly0 + bot * ly1;
+      } else {
+        lg[j][c] = -INFINITY;
+      }
+    }
+    head_epilogue(lg[j], C, probs != nullptr, rule, t_cable, t_tape, bg_margin, ct_margin, pe[j], besti[j], is_cable[j], is_tape[j]);
+  }
+  const size_t o = (size_t)n * HW + (size_t)y * W + 4 * xq;      // first of the 4 pixels in plane n
+#pragma unroll
+  for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) {
+    if (c >= C) break;
+    const size_t oc = ((size_t)n * C + c) * HW + (size_t)y * W + 4 * xq;
+    if (logits) *(float4*)(logits + oc) = make_float4(lg[0][c], lg[1][c], lg[2][c], lg[3][c]);
+    if (probs) *(float4*)(probs + oc) = make_float4(pe[0][c], pe[1][c], pe[2][c], pe[3][c]);
+  }
+  auto pack = [](unsigned a, unsigned b, unsigned c, unsigned d) { return a | (b << 8) | (c << 16) | (d << 24); };
+  if (mask) *(unsigned*)(mask + o) = pack(besti[0], besti[1], besti[2], besti[3]);
+  if (cable) *(unsigned*)(cable + o) = pack(is_cable[0], is_cable[1], is_cable[2], is_cable[3]);
+  if (tape) *(unsigned*)(tape + o) = pack(is_tape[0], is_tape[1], is_tape[2], is_tape[3]);
+}
+
+// A non-finite value among n floats sets ST_NAN in the engine's status (the deep-supervision heads' blob).
+__global__ void nonfinite_flag_kernel(const float* __restrict__ v, int n, unsigned* __restrict__ status) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && !(fabsf(v[i]) <= 3.0e38f)) atomicOr(status, ST_NAN);
 }
 
 // ---- frame glue: cv2.resize either side of the model ----------------------------------

@@ -41,6 +41,7 @@ namespace {
 thread_local std::string g_create_error;
 
 constexpr uint32_t BLOB_MAGIC = 0x50504e55u;  // 'UNPP'
+constexpr uint32_t DS_BLOB_MAGIC = 0x53444e55u;  // 'UNDS': the deep-supervision heads (unetpp_load_ds_heads)
 constexpr int BLOB_VERSION = 1;
 const int NB[5] = {32, 64, 128, 256, 512};    // nb_filter, reference unetpp.py:49
 const int SB[4] = {64, 128, 256, 512};        // SimpleUNet widths, simple_unet.py:32-57
@@ -84,11 +85,11 @@ struct ConvTLayer {
   float* mult = nullptr;
 };
 
-enum OpKind { OP_CONVERT, OP_CONV, OP_UP, OP_CONVT, OP_HEAD, OP_TAPMM, OP_UPSUM };
+enum OpKind { OP_CONVERT, OP_CONV, OP_UP, OP_CONVT, OP_HEAD, OP_TAPMM, OP_UPSUM, OP_DS };
 struct Op {
   OpKind kind;
-  int idx = -1;            // conv / convT index, or (OP_UP) source tensor id
-  int out = -1;            // OP_UP: destination tensor id; OP_HEAD: input tensor id
+  int idx = -1;            // conv / convT index, (OP_UP) source tensor id, or (OP_DS) deep-supervision output k = level
+  int out = -1;            // OP_UP: destination tensor id; OP_HEAD, OP_DS: input tensor id
   bool fuse_head = false;  // OP_CONV: run the 1x1 head in this conv's epilogue when allowed
 };
 
@@ -145,6 +146,12 @@ struct unetpp_engine {
   int ksplit_max = 16, ksplit_min_chunks = 4, ksplit_gate = 4;      // split-K of small launches (UNETPP_KSPLIT=max[,min chunks]; 1 = off)
   int t_kpart = -1, t_kcnt = -1;  // per slot: partial sums and arrival counters of the split tiles
   bool kcnt_dirty = false;        // a forward returned early: its split launches may have left counters behind
+  // deep-supervision heads (unetpp_load_ds_heads): their own allocations, outside the arena
+  float* ds_w = nullptr;          // the UNDS blob payload: ds3_1 weight + bias, ds2_2, ds1_3
+  size_t ds_w_off[4] = {0, 0, 0, 0};      // float offset of output k's weight [C][NB[k]] (its bias follows)
+  float* ds_scratch[4] = {nullptr, nullptr, nullptr, nullptr};   // per slot: fp32 low-res logits of outputs 1..3
+  size_t ds_scr_off[4] = {0, 0, 0, 0};    // float offset of output k's [mb][C][max_h >> k][max_w >> k] in a slot's scratch
+  bool ds_loaded = false;
 };
 
 namespace {
@@ -453,6 +460,8 @@ struct Builder {
     e->ops.push_back(op);
   }
   void up(int src, int dst) { Op op; op.kind = OP_UP; op.idx = src; op.out = dst; e->ops.push_back(op); }
+  // deep-supervision output k right after the op that completes its node: launches only when unetpp_forward_ds asks for it
+  void ds(int k, int node) { Op op; op.kind = OP_DS; op.idx = k; op.out = node; e->ops.push_back(op); }
   void head(int in, int cx) {
     e->t_head_in = in; e->head_cx = cx;
     e->head_w_off = off; off += (size_t)e->cfg.num_classes * cx;
@@ -503,6 +512,7 @@ void build_nested(unetpp_engine* e, Builder& b) {
       L.zt = zt; L.y_t = yt; L.low_t = low;
       L.nchunks = NB[l] / L.KC;                         // K over the skip channels only
       b.conv(std::string(nm) + ".conv2", NB[l], da[l], -1, d[l]);
+      b.ds(l, d[l]);
       continue;
     }
     // Every other level of the exact modes, and level 0 of fast (Cout = 32: narrow tiles, HBM co-bound): the decoder
@@ -518,6 +528,7 @@ void build_nested(unetpp_engine* e, Builder& b) {
     e->convs[ci].upf = upf;
     b.conv(std::string(nm) + ".conv2", NB[l], da[l], -1, d[l]);
     if (l == 0) e->ops.back().fuse_head = true;
+    else b.ds(l, d[l]);
   }
   b.head(d[0], NB[0]);
 }
@@ -742,6 +753,8 @@ void unetpp_destroy(unetpp_engine* e) {
   if (e->ev_start) (void)hipEventDestroy(e->ev_start);
   if (e->arena) (void)hipFree(e->arena);
   for (auto& kv : e->resize_tabs) (void)hipFree(kv.second);
+  if (e->ds_w) (void)hipFree(e->ds_w);
+  for (float* p : e->ds_scratch) if (p) (void)hipFree(p);
   delete e;
 }
 
@@ -812,6 +825,7 @@ int unetpp_load_weights(unetpp_engine* e, const void* host_blob, size_t bytes) {
   if (bytes < 32) return fail(e, UNETPP_E_INVALID, "weight blob too small");
   int rc = check_header(e, (const uint32_t*)host_blob, bytes);
   if (rc) return rc;
+  e->ds_loaded = false;      // the deep-supervision heads belong to the previous checkpoint: load them again
   HIP_TRY(e, hipMemcpy(e->blob, (const char*)host_blob + 32, bytes - 32, hipMemcpyHostToDevice));
   rc = repack(e, nullptr);
   if (rc) return rc;
@@ -829,6 +843,7 @@ int unetpp_load_weights_device(unetpp_engine* e, const void* dev_blob, size_t by
   HIP_TRY(e, hipStreamSynchronize(s));
   int rc = check_header(e, h, bytes);
   if (rc) return rc;
+  e->ds_loaded = false;      // as in unetpp_load_weights
   HIP_TRY(e, hipMemcpyAsync(e->blob, (const char*)dev_blob + 32, bytes - 32, hipMemcpyDeviceToDevice, s));
   return repack(e, s);
 }
@@ -842,15 +857,26 @@ int unetpp_forward(unetpp_engine* e, const void* dev_input, int in_format, int b
   return unetpp_forward_ex(e, dev_input, in_format, batch, h, w, &o, stream);
 }
 
-int unetpp_forward_ex(unetpp_engine* e, const void* dev_input, int in_format, int batch, int h, int w,
-                      const unetpp_outputs* outp, void* stream) {
-  if (!e) return UNETPP_E_INVALID;
-  if (!outp) return fail(e, UNETPP_E_INVALID, "outputs is NULL");
+static int check_rule(unetpp_engine* e, const unetpp_outputs* o) {
+  if (o->rule < UNETPP_RULE_ARGMAX || o->rule > UNETPP_RULE_EXCLUSIVE) return fail(e, UNETPP_E_INVALID, "unknown rule %d", o->rule);
+  if (o->rule != UNETPP_RULE_ARGMAX && e->cfg.num_classes < 3)
+    return fail(e, UNETPP_E_INVALID, "class rules need num_classes >= 3 (bg, cable, tape)");
+  return UNETPP_OK;
+}
+
+// One forward of unetpp_forward_ex (outs = {out, NULL, NULL, NULL}: every op, the same launches) or unetpp_forward_ds.
+// outs[k != 0] launches output k's head and interpolation at its OP_DS; without outs[0] the op list is cut after the
+// last requested OP_DS (the shallowest requested level), so deeper decoder levels never run.
+static int forward_impl(unetpp_engine* e, const void* dev_input, int in_format, int batch, int h, int w,
+                        const unetpp_outputs* const outs[4], void* stream) {
+  static const unetpp_outputs no_outputs{};
+  const unetpp_outputs* outp = outs[0] ? outs[0] : &no_outputs;
   float* dev_logits = outp->dev_logits; float* dev_probs = outp->dev_probs;
   uint8_t* dev_mask = outp->dev_mask; uint8_t* dev_cable = outp->dev_cable; uint8_t* dev_tape = outp->dev_tape;
-  if (outp->rule < UNETPP_RULE_ARGMAX || outp->rule > UNETPP_RULE_EXCLUSIVE) return fail(e, UNETPP_E_INVALID, "unknown rule %d", outp->rule);
-  if (outp->rule != UNETPP_RULE_ARGMAX && e->cfg.num_classes < 3)
-    return fail(e, UNETPP_E_INVALID, "class rules need num_classes >= 3 (bg, cable, tape)");
+  size_t n_ops = e->ops.size();
+  if (!outs[0])
+    for (size_t i = 0; i < e->ops.size(); ++i)
+      if (e->ops[i].kind == OP_DS && outs[e->ops[i].idx]) n_ops = i + 1;
   if (!dev_input) return fail(e, UNETPP_E_INVALID, "input is NULL");
   if (!e->weights_loaded) return fail(e, UNETPP_E_STATE, "forward before load_weights");
   if (in_format != UNETPP_IN_F32_NCHW && in_format != UNETPP_IN_U8_NHWC_BGR) return fail(e, UNETPP_E_INVALID, "unknown input format %d", in_format);
@@ -917,7 +943,8 @@ int unetpp_forward_ex(unetpp_engine* e, const void* dev_input, int in_format, in
     std::vector<std::string> dbg_timeline;                   // UNETPP_WS_STAMPS=all: the wave-specialised launches of this pass, in order
 #endif
 
-    for (const Op& op : e->ops) {
+    for (size_t oi = 0; oi < n_ops; ++oi) {
+      const Op& op = e->ops[oi];
       if (op.kind == OP_CONVERT) {
         const char* src = (const char*)dev_input + (in_format == UNETPP_IN_F32_NCHW ? (size_t)b0 * 3 * hw * 4 : (size_t)b0 * hw * 3);
         size_t total = (size_t)nb * hw;
@@ -1109,6 +1136,42 @@ int unetpp_forward_ex(unetpp_engine* e, const void* dev_input, int in_format, in
           else hipLaunchKernelGGL(convt2x2_kernel<1>, grid, dim3(256), 0, s, a);
           return hipSuccess;
         });
+      } else if (op.kind == OP_DS) {      // unetpp_forward_ds: output k of this node, when requested
+        const int k = op.idx;
+        const unetpp_outputs* dk = outs[k];
+        if (!dk) continue;
+        const int cx = e->tensors[op.out].C, hk = h >> k, wk = w >> k;
+        const double lowpx = (double)nb * hk * wk, px = (double)nb * hw;
+        float* low = e->ds_scratch[slot] + e->ds_scr_off[k];
+        const float* dsw = e->ds_w + e->ds_w_off[k];
+        const float* dsb = dsw + (size_t)C * cx;
+        const char* nm = k == 3 ? "ds3_1" : k == 2 ? "ds2_2" : "ds1_3";
+        char lbl[96];
+        // 1. the 1x1 conv at the node's resolution, fp32 logits only, into the slot's scratch
+        snprintf(lbl, sizeof lbl, "%s|head_generic_kernel<%d>", nm, e->x8 ? 3 : P);
+        const dim3 hgrid((unsigned)((hk * wk + 255) / 256), (unsigned)nb);
+        const size_t lds = (size_t)(C * cx + C) * sizeof(float);
+        Lx.run(lbl, 2.0 * lowpx * cx * C, lowpx * (P * 2.0 * cx + 4.0 * C), [&] {
+          uint8_t* none = nullptr;
+          if (e->x8) hipLaunchKernelGGL(head_generic_kernel<3>, hgrid, dim3(256), lds, s, tp(op.out), cx, dsw, dsb, C, hk, wk, low, (float*)nullptr, none, none, none, 0, 0.f, 0.f, 0.f, 0.f);
+          else if (P == 2) hipLaunchKernelGGL(head_generic_kernel<2>, hgrid, dim3(256), lds, s, tp(op.out), cx, dsw, dsb, C, hk, wk, low, (float*)nullptr, none, none, none, 0, 0.f, 0.f, 0.f, 0.f);
+          else hipLaunchKernelGGL(head_generic_kernel<1>, hgrid, dim3(256), lds, s, tp(op.out), cx, dsw, dsb, C, hk, wk, low, (float*)nullptr, none, none, none, 0, 0.f, 0.f, 0.f, 0.f);
+          return hipSuccess;
+        });
+        // 2. one bilinear step to (h, w) + the head epilogue; ATen's scale, float(in - 1) / float(out - 1)
+        float* dl = dk->dev_logits ? dk->dev_logits + (size_t)b0 * C * hw : nullptr;
+        float* dp = dk->dev_probs ? dk->dev_probs + (size_t)b0 * C * hw : nullptr;
+        uint8_t* dm = dk->dev_mask ? dk->dev_mask + (size_t)b0 * hw : nullptr;
+        uint8_t* dc = dk->dev_cable ? dk->dev_cable + (size_t)b0 * hw : nullptr;
+        uint8_t* dt = dk->dev_tape ? dk->dev_tape + (size_t)b0 * hw : nullptr;
+        const float sy = (float)(hk - 1) / (float)(h - 1), sx = (float)(wk - 1) / (float)(w - 1);
+        const size_t items = (size_t)nb * h * (w / 4);
+        snprintf(lbl, sizeof lbl, "%s+up|ds_upsample_kernel", nm);
+        Lx.run(lbl, px * C * 9.0, lowpx * 4.0 * C + px * ((dl ? 4.0 * C : 0) + (dp ? 4.0 * C : 0) + (dm ? 1 : 0) + (dc ? 1 : 0) + (dt ? 1 : 0)), [&] {
+          hipLaunchKernelGGL(ds_upsample_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const float*)low, C, hk, wk, nb, h, w, sy, sx,
+                             dl, dp, dm, dc, dt, dk->rule, dk->t_cable, dk->t_tape, dk->bg_margin, dk->ct_margin);
+          return hipSuccess;
+        });
       } else if (op.kind == OP_HEAD) {
         if (head_done) continue;     // ran in the last conv's epilogue
         const int cx = e->head_cx;
@@ -1153,6 +1216,66 @@ int unetpp_forward_ex(unetpp_engine* e, const void* dev_input, int in_format, in
   HIP_TRY(e, join.run());
   e->kcnt_dirty = Lx.rc != UNETPP_OK;
   return Lx.rc;
+}
+
+int unetpp_forward_ex(unetpp_engine* e, const void* dev_input, int in_format, int batch, int h, int w,
+                      const unetpp_outputs* outp, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!outp) return fail(e, UNETPP_E_INVALID, "outputs is NULL");
+  const int rc = check_rule(e, outp);
+  if (rc) return rc;
+  const unetpp_outputs* const outs[4] = {outp, nullptr, nullptr, nullptr};
+  return forward_impl(e, dev_input, in_format, batch, h, w, outs, stream);
+}
+
+// ---- deep-supervision outputs -------------------------------------------------------------------------
+static size_t ds_payload_floats(int C) { return (size_t)C * (NB[3] + NB[2] + NB[1]) + 3 * (size_t)C; }
+
+size_t unetpp_ds_blob_bytes(int num_classes) { return num_classes < 1 ? 0 : 32 + 4 * ds_payload_floats(num_classes); }
+
+int unetpp_load_ds_heads(unetpp_engine* e, const void* host_blob, size_t bytes) {
+  if (!e || !host_blob) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (e->cfg.arch != UNETPP_ARCH_NESTED) return fail(e, UNETPP_E_UNSUPPORTED, "deep-supervision heads exist for NestedUNet only");
+  const int C = e->cfg.num_classes;
+  const size_t want = unetpp_ds_blob_bytes(C);
+  if (bytes != want) return fail(e, UNETPP_E_INVALID, "ds blob is %zu bytes, expected %zu for num_classes=%d", bytes, want, C);
+  const uint32_t* hd = (const uint32_t*)host_blob;
+  if (hd[0] != DS_BLOB_MAGIC || (int)hd[1] != BLOB_VERSION) return fail(e, UNETPP_E_INVALID, "bad ds blob magic/version");
+  if ((int)hd[2] != C || (int)hd[3] != e->cfg.in_channels)
+    return fail(e, UNETPP_E_INVALID, "ds blob is for num_classes=%u in_channels=%u", hd[2], hd[3]);
+  ENTER_DEVICE(e);
+  size_t off = 0, per_slot = 0;
+  for (int k = 3; k >= 1; --k) { e->ds_w_off[k] = off; off += (size_t)C * NB[k] + C; }        // definition order: ds3_1, ds2_2, ds1_3
+  for (int k = 1; k <= 3; ++k) { e->ds_scr_off[k] = per_slot; per_slot += (size_t)e->mb * C * (e->cfg.max_h >> k) * (e->cfg.max_w >> k); }
+  for (int i = 0; i < e->nstreams; ++i)
+    if (!e->ds_scratch[i]) HIP_TRY(e, hipMalloc((void**)&e->ds_scratch[i], per_slot * sizeof(float)));
+  const size_t nf = ds_payload_floats(C);
+  if (!e->ds_w) HIP_TRY(e, hipMalloc((void**)&e->ds_w, nf * sizeof(float)));
+  e->ds_loaded = false;
+  HIP_TRY(e, hipMemcpy(e->ds_w, (const char*)host_blob + 32, nf * sizeof(float), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(nonfinite_flag_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, nullptr, (const float*)e->ds_w, (int)nf, e->d_status);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipDeviceSynchronize());
+  e->ds_loaded = true;
+  return UNETPP_OK;
+}
+
+int unetpp_forward_ds(unetpp_engine* e, const void* dev_input, int in_format, int batch, int h, int w,
+                      const unetpp_outputs* const outs[4], void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (e->cfg.arch != UNETPP_ARCH_NESTED) return fail(e, UNETPP_E_UNSUPPORTED, "deep-supervision outputs exist for NestedUNet only");
+  if (!outs || (!outs[0] && !outs[1] && !outs[2] && !outs[3])) return fail(e, UNETPP_E_INVALID, "no output requested");
+  for (int k = 0; k < 4; ++k)
+    if (outs[k]) { const int rc = check_rule(e, outs[k]); if (rc) return rc; }
+  for (int k = 1; k < 4; ++k) {      // ds_upsample_kernel stores 4 pixels at once: 16 bytes of fp32, 4 bytes of a mask
+    if (!outs[k]) continue;
+    const unetpp_outputs& o = *outs[k];
+    if (((uintptr_t)o.dev_logits | (uintptr_t)o.dev_probs) % 16 || ((uintptr_t)o.dev_mask | (uintptr_t)o.dev_cable | (uintptr_t)o.dev_tape) % 4)
+      return fail(e, UNETPP_E_INVALID, "outs[%d]: logits / probs must be 16-byte aligned, masks 4-byte aligned", k);
+  }
+  if (!e->ds_loaded && (outs[1] || outs[2] || outs[3]))
+    return fail(e, UNETPP_E_STATE, "deep-supervision output requested before unetpp_load_ds_heads");
+  return forward_impl(e, dev_input, in_format, batch, h, w, outs, stream);
 }
 
 int unetpp_status(unetpp_engine* e, uint32_t* flags, int clear) {

@@ -9,6 +9,8 @@ and the source of the current HIP stream — no torch op runs on the hot path.
     model.load_state_dict(checkpoint['model'], strict=True); model.eval()                           # :215-217
     outputs = model(img_tensor)                                                                      # :294-297
     pred = model.segment(img_tensor)       # fused replacement of :294-300 (uint8 class-index mask, on device)
+    out, out1, out2, out3 = model.forward_deep_supervision(img_tensor)   # the list of unetpp.py:121-133, one pass
+    pred1 = model.segment(img_tensor, output=1)   # pruned UNet++: stops after x1_3 and uses the ds1_3 head
 """
 from __future__ import annotations
 
@@ -48,6 +50,8 @@ class NestedUNet:
         self._device_index: Optional[int] = None
         self._handle = None
         self._blob: Optional[np.ndarray] = None      # canonical weights (host copy, re-uploaded if the engine is rebuilt)
+        self._ds_blob: Optional[np.ndarray] = None   # deep-supervision heads (host copy, uploaded on the first ds call)
+        self._ds_uploaded = False                    # ... to the current engine
         self._state_dict = None
 
     # ------------------------------------------------------------------ nn.Module surface
@@ -82,6 +86,8 @@ class NestedUNet:
         if missing:
             raise RuntimeError("Missing key(s) in state_dict: " + ", ".join(missing))
         self._blob = packing.build_blob(state_dict, self.num_classes, self.input_channels)
+        self._ds_blob = packing.build_ds_blob(state_dict, self.num_classes) if self.deep_supervision else None
+        self._ds_uploaded = False
         self._state_dict = {k: packing._np(v).copy() for k, v in state_dict.items()}
         if self._handle is not None:
             self._upload()
@@ -105,6 +111,7 @@ class NestedUNet:
         if self._handle is not None:
             _lib.load().unetpp_destroy(self._handle)
             self._handle = None
+        self._ds_uploaded = False
 
     def __del__(self):
         try:
@@ -138,9 +145,32 @@ class NestedUNet:
 
     def _upload(self):
         lib = _lib.load()
+        self._ds_uploaded = False                    # the engine drops its ds heads with new main weights
         rc = lib.unetpp_load_weights(self._handle, self._blob.ctypes.data_as(ctypes.c_void_p), self._blob.nbytes)
         if rc != 0:
             raise RuntimeError(self._err(rc))
+
+    def _upload_ds(self):
+        """The deep-supervision heads, on the first ds call of an engine (also after a rebuild)."""
+        if self._ds_blob is None:      # weights from load_weights_from_device_blob: the broadcast blob has no ds heads
+            raise RuntimeError("no deep-supervision heads loaded: load_state_dict() a checkpoint with ds3_1 / ds2_2 / ds1_3 "
+                               "(sharding.load_replicated broadcasts the main blob only)")
+        if self._ds_uploaded:
+            return
+        rc = _lib.load().unetpp_load_ds_heads(self._handle, self._ds_blob.ctypes.data_as(ctypes.c_void_p), self._ds_blob.nbytes)
+        if rc != 0:
+            raise RuntimeError(self._err(rc))
+        self._ds_uploaded = True
+
+    def _check_output(self, output):
+        """output = k selects the reference's deep-supervision list entry [out, out1, out2, out3][k]."""
+        if self._ARCH != _lib.ARCH_NESTED:
+            raise NotImplementedError(f"output={output!r}: deep-supervision outputs exist for NestedUNet only")
+        if isinstance(output, bool) or not isinstance(output, (int, np.integer)) or not 0 <= int(output) <= 3:
+            raise ValueError(f"output must be 0 (out), 1 (out1, ds1_3), 2 (out2, ds2_2) or 3 (out3, ds3_1), got {output!r}")
+        if output and not self.deep_supervision:
+            raise ValueError(f"output={output}: the model was built with deep_supervision=False and has no ds heads")
+        return int(output)
 
     def _check_and_build_blob(self, state_dict):
         """strict key check + canonical blob of this architecture (rank 0 of sharding.load_replicated)."""
@@ -157,10 +187,12 @@ class NestedUNet:
         if rc != 0:
             raise RuntimeError(self._err(rc))
         self._blob = blob_tensor.cpu().numpy()
+        self._ds_blob = None                         # the broadcast carries no ds heads: output != 0 is refused
+        self._ds_uploaded = False
 
     # ------------------------------------------------------------------ the hot path
-    def _run(self, x, want_logits: bool, want_mask: bool, want_class_masks: bool, want_probs: bool = False,
-             rule: str = "argmax", params=(0.0, 0.0, 0.0, 0.0)):
+    def _prepare(self, x):
+        """Checks the input, builds (or grows) the engine; returns (x contiguous, input format, b, h, w)."""
         import torch
         if self.training:
             raise RuntimeError("engine is inference-only")
@@ -189,6 +221,13 @@ class NestedUNet:
             raise RuntimeError(f"input on {x.device}, engine on cuda:{self._device_index}")
         x = x.contiguous()
         self._ensure_engine(b, h, w)
+        return x, fmt, b, h, w
+
+    def _run(self, x, want_logits: bool, want_mask: bool, want_class_masks: bool, want_probs: bool = False,
+             rule: str = "argmax", params=(0.0, 0.0, 0.0, 0.0), output: int = 0):
+        import torch
+        output = self._check_output(output) if output != 0 else 0
+        x, fmt, b, h, w = self._prepare(x)
         dev = x.device
         logits = torch.empty((b, self.num_classes, h, w), dtype=torch.float32, device=dev) if want_logits else None
         mask = torch.empty((b, h, w), dtype=torch.uint8, device=dev) if want_mask else None
@@ -200,7 +239,13 @@ class NestedUNet:
         if rule not in _lib.RULES:
             raise ValueError(f"rule must be one of {sorted(_lib.RULES)}")
         outs = _lib.Outputs(p(logits), p(probs), p(mask), p(cable), p(tape), _lib.RULES[rule], *[float(v) for v in params])
-        rc = _lib.load().unetpp_forward_ex(self._handle, p(x), fmt, b, h, w, ctypes.byref(outs), stream)
+        if output == 0:
+            rc = _lib.load().unetpp_forward_ex(self._handle, p(x), fmt, b, h, w, ctypes.byref(outs), stream)
+        else:      # pruned: only output k is requested, the engine stops after its node
+            self._upload_ds()
+            lst = (ctypes.POINTER(_lib.Outputs) * 4)()
+            lst[output] = ctypes.pointer(outs)
+            rc = _lib.load().unetpp_forward_ds(self._handle, p(x), fmt, b, h, w, lst, stream)
         if rc != 0:
             raise RuntimeError(self._err(rc))
         if self._check_range:
@@ -232,14 +277,35 @@ class NestedUNet:
             raise RuntimeError("unetpp: value range of the fp16 activation planes exceeded (" + "; ".join(what) +
                                "): results differ from the fp32 reference")
 
-    def forward(self, x):
-        """NestedUNet.forward in eval mode (unetpp.py:93-135): float32 [B,3,H,W] -> float32 logits [B,C,H,W]."""
-        return self._run(x, True, False, False)[0]
+    def forward(self, x, output: int = 0):
+        """NestedUNet.forward in eval mode (unetpp.py:93-135): float32 [B,3,H,W] -> float32 logits [B,C,H,W].
+        output=k (1..3) returns entry k of the deep-supervision list [out, out1, out2, out3] instead (unetpp.py:121-133),
+        from a pass that stops after that entry's node (pruned UNet++)."""
+        return self._run(x, True, False, False, output=output)[0]
 
-    def segment(self, x, return_logits: bool = False, return_class_masks: bool = False):
+    def forward_deep_supervision(self, x):
+        """[out, out1, out2, out3] of the reference's deep-supervision forward (unetpp.py:121-133, BatchNorm in eval
+        mode) as float32 CUDA tensors [B,C,H,W], from one engine pass."""
+        import torch
+        self._check_output(1)
+        x, fmt, b, h, w = self._prepare(x)
+        self._upload_ds()
+        outs = [torch.empty((b, self.num_classes, h, w), dtype=torch.float32, device=x.device) for _ in range(4)]
+        recs = [_lib.Outputs(ctypes.c_void_p(t.data_ptr()), None, None, None, None, 0, 0.0, 0.0, 0.0, 0.0) for t in outs]
+        lst = (ctypes.POINTER(_lib.Outputs) * 4)(*[ctypes.pointer(r) for r in recs])
+        rc = _lib.load().unetpp_forward_ds(self._handle, ctypes.c_void_p(x.data_ptr()), fmt, b, h, w, lst,
+                                           ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+        if rc != 0:
+            raise RuntimeError(self._err(rc))
+        if self._check_range:
+            self.raise_on_range_error()
+        return outs
+
+    def segment(self, x, return_logits: bool = False, return_class_masks: bool = False, output: int = 0):
         """Fused model call + softmax/argmax/uint8 (+ class masks) of infer_two_stage_burr.py:294-304.
-        x: float32 [B,3,H,W] in [0,1] or uint8 [B,H,W,3] BGR frames at model resolution."""
-        logits, mask, cable, tape = self._run(x, return_logits, True, return_class_masks)
+        x: float32 [B,3,H,W] in [0,1] or uint8 [B,H,W,3] BGR frames at model resolution.
+        output=k (1..3): the same on deep-supervision output k, from a pruned pass (see forward)."""
+        logits, mask, cable, tape = self._run(x, return_logits, True, return_class_masks, output=output)
         out = (mask,)
         if return_class_masks:
             out += (cable, tape)
@@ -248,12 +314,13 @@ class NestedUNet:
         return out[0] if len(out) == 1 else out
 
     def segment_thresholded(self, x, rule: str = "thresholded_argmax", t_cable: float = 0.45, t_tape: float = 0.50,
-                            bg_margin: float = 0.15, ct_margin: float = 0.10, return_probs: bool = False):
+                            bg_margin: float = 0.15, ct_margin: float = 0.10, return_probs: bool = False, output: int = 0):
         """The thresholded frame loops' tail on the device: probs = softmax_np(outputs) then
         `thresholded_argmax` (infer_video_3class_best.py:56-83, infer_video_strict.py:36-63),
         `strict_bg_check` (infer_video_fixed.py:35-83: bg_margin is the background-probability ceiling) or
-        `exclusive` (infer_video_robust.py:70-99).  Returns (mask_cable, mask_tape[, probs[B,C,H,W]]) on device."""
-        r = self._run(x, False, False, True, return_probs, rule, (t_cable, t_tape, bg_margin, ct_margin))
+        `exclusive` (infer_video_robust.py:70-99).  Returns (mask_cable, mask_tape[, probs[B,C,H,W]]) on device.
+        output=k (1..3): on deep-supervision output k, from a pruned pass (see forward)."""
+        r = self._run(x, False, False, True, return_probs, rule, (t_cable, t_tape, bg_margin, ct_margin), output=output)
         return (r[2], r[3], r[4]) if return_probs else (r[2], r[3])
 
     def mask_stats(self, mask):
@@ -321,9 +388,10 @@ class NestedUNet:
             raise RuntimeError(self._err(rc))
         return out
 
-    def predict_proba(self, x):
-        """softmax(model(x), dim=1) as float32 [B,C,H,W] on the device (one fused pass)."""
-        return self._run(x, False, False, False, True)[4]
+    def predict_proba(self, x, output: int = 0):
+        """softmax(model(x), dim=1) as float32 [B,C,H,W] on the device (one fused pass); output=k (1..3): of
+        deep-supervision output k, from a pruned pass (see forward)."""
+        return self._run(x, False, False, False, True, output=output)[4]
 
     # ------------------------------------------------------------------ measurement / debug hooks
     def workspace_bytes(self) -> int:

@@ -81,13 +81,34 @@ def folded_layers(state_dict, in_channels: int = 3):
 
 def build_blob(state_dict, num_classes: int, in_channels: int = 3) -> np.ndarray:
     """Canonical blob (uint8 array): 32-byte header + fp32 payload; ds* heads and num_batches_tracked are dropped
-    (deep-supervision heads run only in train mode, unetpp.py:121-133)."""
+    (the reference evaluates the deep-supervision heads only in train mode, unetpp.py:121-133; build_ds_blob packs
+    them for forward_deep_supervision / output=k)."""
     layers = folded_layers(state_dict, in_channels)
     header = np.array([BLOB_MAGIC, BLOB_VERSION, num_classes, in_channels, len(layers), 0, 0, 0], dtype=np.uint32)   # arch 0
     parts = [header.view(np.uint8)]
     for _, w, b in layers:
         parts.append(np.ascontiguousarray(w, dtype=np.float32).ravel().view(np.uint8))
         parts.append(np.ascontiguousarray(b, dtype=np.float32).ravel().view(np.uint8))
+    return np.concatenate(parts)
+
+
+# ---------------------------------------------------------------------------- deep-supervision heads
+DS_BLOB_MAGIC = 0x53444E55  # 'UNDS'
+DS_HEADS = (("ds3_1", 256), ("ds2_2", 128), ("ds1_3", 64))   # definition order (unetpp.py:87-91), input channels
+
+
+def build_ds_blob(state_dict, num_classes: int) -> np.ndarray:
+    """Blob of the deep-supervision heads that unetpp_load_ds_heads() consumes (layout: include/unetpp.h): 32-byte header
+    {'UNDS', 1, num_classes, 3, 0, 0, 0, 0}, then fp32 weight [C][Cx] and bias [C] of ds3_1, ds2_2 and ds1_3."""
+    header = np.array([DS_BLOB_MAGIC, BLOB_VERSION, num_classes, 3, 0, 0, 0, 0], dtype=np.uint32)
+    parts = [header.view(np.uint8)]
+    for name, cx in DS_HEADS:
+        w = _np(state_dict[f"{name}.weight"]).astype(np.float32)
+        b = _np(state_dict[f"{name}.bias"]).astype(np.float32)
+        if w.shape != (num_classes, cx, 1, 1) or b.shape != (num_classes,):
+            raise ValueError(f"{name}: weight {w.shape} / bias {b.shape}, expected ({num_classes}, {cx}, 1, 1) / ({num_classes},)")
+        parts.append(np.ascontiguousarray(w).ravel().view(np.uint8))
+        parts.append(np.ascontiguousarray(b).ravel().view(np.uint8))
     return np.concatenate(parts)
 
 

@@ -19,6 +19,15 @@
  * float32 input value) beyond +-65504 is clamped and a NaN does not propagate the way it does in the fp32
  * reference (src/models/unetpp.py:23-26, src/models/simple_unet.py:94-128).  Neither happens silently: the
  * kernel that narrows such a value sets a sticky flag, see unetpp_status().
+ *
+ * The BOTTOM of the fp16 window is not flagged.  EXACT's lo plane is an fp16 subnormal (quantum 2^-24) for every
+ * |x| < 0.25, so a stored tensor whose LARGEST value is far below 1 is kept with fewer bits.  Measured on the device
+ * (tests/test_gpu_value_range.py, one tensor of the network moved at a time, logits of +-1): largest value
+ * >= 0.04: logit error <= 6e-6 as at the usual scale; 0.01: <= 2e-5; 2e-3 ... 5e-3 (2^-10 of the usual scale):
+ * 2e-5 ... 8e-5; 1.5e-4 ... 3e-4 (2^-14): 3e-4 ... 1.3e-3, i.e. beyond the 1e-3 parity bar.  A checkpoint can be
+ * checked with unetpp_debug_read (largest value of every tensor).  EXACT8 keeps its usual error down to 0.01 at
+ * least; its error is RELATIVE to the logits (about 1e-4 of the largest |logit|), so it meets 1e-3 absolute only
+ * for logits within about +-6, where EXACT stays below 5e-4 up to +-400.  DESIGN.md section 3, "Range".
  */
 #ifndef UNETPP_H
 #define UNETPP_H

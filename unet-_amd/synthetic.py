@@ -124,3 +124,108 @@ def make_trained_like_state_dict(num_classes: int = 3, in_channels: int = 3, dee
         sd[bn + "weight"][zero] = 0
         sd[bn + "weight"][big] *= big_gain
     return sd
+
+
+# ----------------------------------------------------------------------------- moving a tensor through the value range
+# ConvBlock is conv -> BatchNorm -> ReLU (reference unetpp.py:23-26): a block's output scale (gamma, beta) and its consumers'
+# weight scale trade any power of two without changing the function -- and, in fp32, without changing a bit of it.  The
+# engine stores activations as fp16 planes, so where a tensor sits in that window is NOT arbitrary for it
+# (tests/test_value_range_host.py, tests/test_gpu_value_range.py).
+NESTED_NODES = ("x0_0", "x1_0", "x2_0", "x3_0", "x4_0", "x3_1", "x2_2", "x1_3", "x0_4")
+NESTED_SITES = NESTED_NODES + tuple(n + "a" for n in NESTED_NODES)
+SIMPLE_SITES = ("enc1a", "enc1", "enc2a", "enc2", "enc3a", "enc3", "enc4a", "enc4",
+                "up3t", "dec3a", "dec3", "up2t", "dec2a", "dec2", "up1t", "dec1a", "dec1")
+
+
+def _pow2(k: int) -> np.float32:
+    k = int(k)
+    if not -60 <= k <= 60:
+        raise ValueError(f"k={k}: powers of two between 2^-60 and 2^60 only")
+    return np.float32(2.0) ** np.float32(k)
+
+
+def _mul(sd, key, f, cols=slice(None)):
+    """sd[key][:, cols] *= f (f a power of two: exact in float32 short of under/overflow), on a fresh copy of that entry"""
+    a = np.array(sd[key], dtype=np.float32, copy=True)
+    if a.ndim == 1:
+        a *= f
+    else:
+        a[:, cols] *= f
+    sd[key] = a
+
+
+def rescale_state_dict(sd: dict, site: str, k: int) -> dict:
+    """A copy of a NestedUNet state dict in which tensor `site` is produced 2^k larger and consumed 2^-k smaller.
+
+    site: a node 'x0_0' ... 'x4_0', 'x3_1', 'x2_2', 'x1_3', 'x0_4' (the block's bn2 weight and bias are multiplied; the
+    consumers divided: the next encoder block's conv1 over all input channels -- the pool commutes with a positive scale --,
+    the skip or up slice of the decoder conv1 that reads it (skip channels first, unetpp.py:112-116), its ds head if the
+    checkpoint has one, `final` for x0_4), or a block's inner tensor 'x0_0a' ... (bn1 against conv2.weight).
+    Every reference output is unchanged, bit for bit in float32.  site='logits' multiplies final.weight and final.bias
+    instead: that one changes the function (logits x 2^k)."""
+    out = dict(sd)
+    up, down = _pow2(k), _pow2(-k)
+    if site == "logits":
+        _mul(out, "final.weight", up); _mul(out, "final.bias", up)
+        return out
+    if site not in NESTED_SITES:
+        raise ValueError(f"unknown site {site!r}: one of {NESTED_SITES} or 'logits'")
+    l, j = int(site[1]), int(site[3])
+    blk = f"conv{l}_{j}"
+    if site.endswith("a"):
+        _mul(out, f"{blk}.bn1.weight", up); _mul(out, f"{blk}.bn1.bias", up)
+        _mul(out, f"{blk}.conv2.weight", down)
+        return out
+    _mul(out, f"{blk}.bn2.weight", up); _mul(out, f"{blk}.bn2.bias", up)
+    f = NB_FILTER
+    if j == 0:
+        if l < 4:
+            _mul(out, f"conv{l + 1}_0.conv1.weight", down)                            # through the pool
+            _mul(out, f"conv{l}_{4 - l}.conv1.weight", down, slice(0, f[l]))          # as the skip of its own level
+        else:
+            _mul(out, "conv3_1.conv1.weight", down, slice(f[3], None))                # as the up source of level 3
+    elif l > 0:
+        _mul(out, f"conv{l - 1}_{j + 1}.conv1.weight", down, slice(f[l - 1], None))   # up source of the level above
+        if f"ds{l}_{j}.weight" in out:
+            _mul(out, f"ds{l}_{j}.weight", down)
+    else:
+        _mul(out, "final.weight", down)
+    return out
+
+
+def rescale_simple_state_dict(sd: dict, site: str, k: int) -> dict:
+    """The same for SimpleUNet (simple_unet.py:94-128), which has no BatchNorm: the producing conv's or transposed conv's
+    weight and bias are multiplied, its consumers' weights divided (cat([up, skip]): up channels first).  Sites are the
+    engine's tensor names: 'enc1a' (after enc1.0), 'enc1' (after enc1.2), 'up3t', 'dec3a', 'dec3', ...; 'logits'."""
+    out = dict(sd)
+    up, down = _pow2(k), _pow2(-k)
+    if site == "logits":
+        _mul(out, "final.weight", up); _mul(out, "final.bias", up)
+        return out
+    if site not in SIMPLE_SITES:
+        raise ValueError(f"unknown site {site!r}: one of {SIMPLE_SITES} or 'logits'")
+    w = SIMPLE_WIDTHS
+    kind = site.rstrip("at0123456789")                         # 'enc', 'dec' or 'up'
+    l = int(site[len(kind)])
+    if site.startswith("up"):
+        prod, cons = f"up{l}", [(f"dec{l}.0.weight", slice(0, w[l - 1]))]
+    elif site.endswith("a"):
+        prod, cons = f"{kind}{l}.0", [(f"{kind}{l}.2.weight", slice(None))]
+    elif kind == "enc":
+        prod = f"enc{l}.2"
+        cons = [(f"enc{l + 1}.0.weight", slice(None)), (f"dec{l}.0.weight", slice(w[l - 1], None))] if l < 4 \
+            else [("up3.weight", None)]
+    else:
+        prod = f"dec{l}.2"
+        cons = [(f"up{l - 1}.weight", None)] if l > 1 else [("final.weight", slice(None))]
+    if prod.startswith("up"):
+        _mul(out, prod + ".weight", up, slice(None))           # ConvTranspose2d weight is [Cin, Cout, 2, 2]: all of it
+    else:
+        _mul(out, prod + ".weight", up)
+    _mul(out, prod + ".bias", up)
+    for key, cols in cons:
+        if cols is None:                                       # a transposed conv consumes over dim 0: all of it
+            out[key] = np.array(out[key], dtype=np.float32, copy=True) * down
+        else:
+            _mul(out, key, down, cols)
+    return out

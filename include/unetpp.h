@@ -212,14 +212,75 @@ int unetpp_forward_ds(unetpp_engine* e, const void* dev_input, int in_format, in
  * From a uint8 class-index mask [B,H,W] (e.g. the dev_mask of a forward): per-frame class pixel counts
  * (np.sum(mask_cable) / coverage, infer_two_stage_burr.py:333-340, src/utils/geometry_enhanced.py:151-152) and,
  * per class and row, the first and last column of that class — the operands of _compute_width_per_row
- * (geometry_enhanced.py:45-74: width = xs.max() - xs.min() + 1).  The reference's smoothing and
- * connected-component filtering (cv2) stay on the host.
+ * (geometry_enhanced.py:45-74: width = xs.max() - xs.min() + 1).  The reference's Gaussian smoothing (cv2) stays on
+ * the host; its connected-component filtering runs on the device, see unetpp_components_filter below.
  *   dev_counts   uint32 [B,num_classes]      (zeroed by this call)
  *   dev_row_min  int32  [B,num_classes,H]    W  when the row has no pixel of the class
  *   dev_row_max  int32  [B,num_classes,H]    -1 when the row has no pixel of the class
  * Asynchronous on `stream`. */
 int unetpp_mask_stats(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, uint32_t* dev_counts,
                       int32_t* dev_row_min, int32_t* dev_row_max, void* stream);
+
+/* ---- connected components and the reference's component filters on the device ---------------------------------
+ * What every frame loop of the reference does next with a class mask is cv2.connectedComponentsWithStats(mask,
+ * connectivity=8) followed by a choice among the components (src/utils/geometry_enhanced.py:81-110 and :275-311,
+ * src/refactor/postprocess.py:12-76 and :106-116, infer_video_spatial.py:24-53).
+ *
+ * unetpp_components labels B frames.  dev_mask is uint8 [B,h,w] (any h, w >= 1, h * w <= 2^30, h, w <= 65535);
+ * foreground = (mask == match_class), or (mask != 0) for match_class < 0; connectivity is 4 or 8.
+ *   dev_labels  int32 [B,h,w]         0 = background, components 1..n NUMBERED IN RASTER ORDER OF THEIR FIRST PIXEL
+ *                                     (row-major, per frame): scipy.ndimage.label's order.  cv2's own numbering is an
+ *                                     artefact of its block-based algorithm and is not reproduced; the reference depends
+ *                                     on it only to break ties between components of equal area / score, which here go
+ *                                     to the lower label.
+ *   dev_num     int32 [B]             n + 1 like cv2's num_labels (the background counts); exact whatever `capacity`
+ *   dev_stats   int32 [B,capacity,5]  cv2's columns LEFT, TOP, WIDTH, HEIGHT, AREA; row = label, row 0 = background;
+ *                                     rows >= num (and a background without pixels) are zero
+ *   dev_sums    uint64 [B,capacity,2] sum of x, sum of y over the label's pixels: cv2's double centroids are
+ *                                     sums / area in one correctly rounded division
+ * dev_stats and dev_sums may both be NULL (labels and num only).  `capacity` (>= 2) is the number of rows: labels and
+ * num are exact for any number of components, stats and sums hold labels 0 .. capacity - 1.  The worst case is
+ * h * w / 2 components (a checkerboard at connectivity 4), real masks stay in the low thousands.
+ * All results are integers and every component is rooted at its smallest pixel index, so they are bitwise the same
+ * from run to run.  dev_workspace: unetpp_components_workspace_bytes(batch, h, w, capacity) bytes (0 for bad
+ * arguments), 16-byte aligned, owned by the caller; nothing is allocated per call and the engine's activation
+ * workspace is not touched.  Asynchronous on `stream`.
+ *
+ * unetpp_components_filter writes dev_out uint8 [B,h,w] = out_value where the pixel's component is kept, else 0,
+ * from the outputs of unetpp_components (same batch, h, w, capacity and workspace).  All arithmetic in fp64 without
+ * contraction, as the reference's NumPy / Python expressions evaluate:
+ *   UNETPP_CC_LARGEST      _largest_connected_component(mask, min_area), geometry_enhanced.py:81-110: the first
+ *                          (lowest label) of the largest components with area >= min_area, nothing if there is none;
+ *                          min_area = 0 is the tail of constrain_tape_to_ring, postprocess.py:106-116
+ *   UNETPP_CC_SPATIAL      spatial_filter, infer_video_spatial.py:24-53: every component with area > min_area and
+ *                          min_width <= width <= max_width and height >= h * min_height_ratio
+ *   UNETPP_CC_CABLE_SHAPE  filter_cable_by_shape, postprocess.py:12-76: area >= min_area,
+ *                          aspect = max(w,h) / (min(w,h) + 1e-6) >= min_aspect,
+ *                          offset = |cx - roi_width / 2| / roi_width <= max_center_offset; the first of the highest
+ *                          score = area * aspect * (1 - offset) is kept (out_value 255 in the reference)
+ * A frame with num > capacity cannot be decided from truncated stats: its output is all zero; callers compare
+ * dev_num with capacity.  Errors: UNETPP_E_INVALID for connectivity other than 4 / 8, capacity < 2, a bad shape or
+ * rule, NULL where not allowed, exactly one of dev_stats / dev_sums NULL. */
+enum { UNETPP_CC_LARGEST = 0, UNETPP_CC_SPATIAL = 1, UNETPP_CC_CABLE_SHAPE = 2 };
+
+typedef struct unetpp_cc_rule {
+  double min_area;           /* all rules (reference defaults: 100 / 1000 / 1000) */
+  double min_width;          /* SPATIAL (50) */
+  double max_width;          /* SPATIAL (300) */
+  double min_height_ratio;   /* SPATIAL (0.3) */
+  double min_aspect;         /* CABLE_SHAPE (1.6) */
+  double max_center_offset;  /* CABLE_SHAPE (0.3) */
+  double roi_width;          /* CABLE_SHAPE: the ROI's width in pixels, > 0 */
+} unetpp_cc_rule;
+
+size_t unetpp_components_workspace_bytes(int batch, int h, int w, int capacity);
+int unetpp_components(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, int match_class,
+                      int connectivity, int capacity, int32_t* dev_labels, int32_t* dev_num, int32_t* dev_stats,
+                      uint64_t* dev_sums, void* dev_workspace, void* stream);
+int unetpp_components_filter(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num,
+                             const int32_t* dev_stats, const uint64_t* dev_sums, int batch, int h, int w,
+                             int capacity, int rule, const unetpp_cc_rule* params, uint8_t out_value,
+                             uint8_t* dev_out, void* dev_workspace, void* stream);
 
 /* ---- frame glue either side of the model --------------------------------
  * unetpp_resize_linear_u8 replaces `cv2.resize(frame_rgb, target_size, interpolation=cv2.INTER_LINEAR)`

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunetpp_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["unetpp_abi.hip"]
-HEADERS = ["conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", os.path.join("..", "..", "include", "unetpp.h")]
+HEADERS = ["conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "components.h", os.path.join("..", "..", "include", "unetpp.h")]
 
 # every symbol include/unetpp.h declares
 ABI_SYMBOLS = [
@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "unetpp_profile_enable", "unetpp_profile_count", "unetpp_profile_read", "unetpp_profile_name",
     "unetpp_profile_work", "unetpp_debug_read", "unetpp_debug_keep_intermediates",
     "unetpp_ds_blob_bytes", "unetpp_load_ds_heads", "unetpp_forward_ds",
+    "unetpp_components_workspace_bytes", "unetpp_components", "unetpp_components_filter",
 ]
 
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
@@ -40,6 +41,13 @@ class Config(ctypes.Structure):
                 ("device", ctypes.c_int), ("micro_batch", ctypes.c_int), ("streams", ctypes.c_int), ("arch", ctypes.c_int)]
 
 
+class CcRule(ctypes.Structure):
+    """unetpp_cc_rule: the parameters of the component filters (all doubles)."""
+    _fields_ = [(n, ctypes.c_double) for n in ("min_area", "min_width", "max_width", "min_height_ratio", "min_aspect",
+                                               "max_center_offset", "roi_width")]
+
+
+CC_RULES = {"largest": 0, "spatial": 1, "cable_shape": 2}
 RULES = {"argmax": 0, "thresholded_argmax": 1, "strict_bg_check": 2, "exclusive": 3}
 
 
@@ -170,6 +178,10 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     lib.unetpp_load_ds_heads.argtypes = [vp, vp, cs]; lib.unetpp_load_ds_heads.restype = ci
     lib.unetpp_forward_ds.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.POINTER(ctypes.POINTER(Outputs)), vp]
     lib.unetpp_forward_ds.restype = ci
+    lib.unetpp_components_workspace_bytes.argtypes = [ci, ci, ci, ci]; lib.unetpp_components_workspace_bytes.restype = cs
+    lib.unetpp_components.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]; lib.unetpp_components.restype = ci
+    lib.unetpp_components_filter.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(CcRule), ctypes.c_uint8, vp, vp, vp]
+    lib.unetpp_components_filter.restype = ci
     ver = lib.unetpp_version().decode()
     if ver.endswith(" +wsdbg") and os.environ.get("UNETPP_ALLOW_DBG_LIB"):
         ver = ver[:-len(" +wsdbg")]            # measurement build with phase ablations (scripts/ws_ablate.sh)

@@ -29,6 +29,7 @@
 
 #include "../../include/unetpp.h"
 #include "aux_kernels.h"
+#include "components.h"
 #include "conv3x3_mfma.h"
 #include "conv3x3_ws.h"
 #include "convt2x2_mfma.h"
@@ -1301,6 +1302,101 @@ int unetpp_mask_stats(unetpp_engine* e, const uint8_t* dev_mask, int batch, int 
   HIP_TRY(e, hipMemsetAsync(dev_counts, 0, (size_t)batch * C * sizeof(uint32_t), s));
   hipLaunchKernelGGL(mask_stats_kernel, dim3((unsigned)h, (unsigned)batch), dim3(256), 0, s, dev_mask, C, h, w,
                      (unsigned*)dev_counts, (int*)dev_row_min, (int*)dev_row_max);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+// ---- connected components + the reference's component filters (components.h) -----------------------------------
+}  // extern "C"
+namespace {
+struct CcWorkspace {
+  size_t parent = 0, chunks = 0, keep = 0, total = 0;   // byte offsets
+  int nchunk = 0;
+};
+bool cc_layout(int batch, int h, int w, int capacity, CcWorkspace* ws) {
+  if (batch < 1 || batch > 65535 || h < 1 || w < 1 || h > 65535 || w > 65535 || (size_t)h * w > (1u << 30) || capacity < 2) return false;
+  const size_t hw = (size_t)h * w;
+  ws->nchunk = (int)((hw + CC_CHUNK - 1) / CC_CHUNK);
+  ws->parent = 0;
+  ws->chunks = align_up(hw * batch * sizeof(int), 256);
+  ws->keep = ws->chunks + align_up((size_t)ws->nchunk * batch * sizeof(int), 256);
+  ws->total = ws->keep + align_up((size_t)capacity * batch, 256);
+  return true;
+}
+}  // namespace
+extern "C" {
+
+size_t unetpp_components_workspace_bytes(int batch, int h, int w, int capacity) {
+  CcWorkspace ws;
+  return cc_layout(batch, h, w, capacity, &ws) ? ws.total : 0;
+}
+
+int unetpp_components(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, int match_class, int connectivity,
+                      int capacity, int32_t* dev_labels, int32_t* dev_num, int32_t* dev_stats, uint64_t* dev_sums,
+                      void* dev_workspace, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_mask || !dev_labels || !dev_num || !dev_workspace) return fail(e, UNETPP_E_INVALID, "null argument");
+  if ((dev_stats == nullptr) != (dev_sums == nullptr)) return fail(e, UNETPP_E_INVALID, "dev_stats and dev_sums go together (both or neither)");
+  if (connectivity != 4 && connectivity != 8) return fail(e, UNETPP_E_INVALID, "connectivity must be 4 or 8, got %d", connectivity);
+  if (capacity < 2) return fail(e, UNETPP_E_INVALID, "capacity %d: at least 2 rows (background + one component)", capacity);
+  if (match_class > 255) return fail(e, UNETPP_E_INVALID, "match_class %d out of range", match_class);
+  CcWorkspace ws;
+  if (!cc_layout(batch, h, w, capacity, &ws)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if ((uintptr_t)dev_workspace % 16) return fail(e, UNETPP_E_INVALID, "dev_workspace must be 16-byte aligned");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w, conn8 = connectivity == 8;
+  int* parent = (int*)((char*)dev_workspace + ws.parent);
+  int* chunks = (int*)((char*)dev_workspace + ws.chunks);
+  const int ntx = (w + CC_TW - 1) / CC_TW, nty = (h + CC_TH - 1) / CC_TH;
+  if (nty > 65535) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  const dim3 blk(CC_THREADS), per_px((unsigned)ws.nchunk, (unsigned)batch);
+  if (dev_stats) {
+    HIP_TRY(e, hipMemsetAsync(dev_stats, 0, (size_t)batch * capacity * 5 * sizeof(int32_t), s));
+    HIP_TRY(e, hipMemsetAsync(dev_sums, 0, (size_t)batch * capacity * 2 * sizeof(uint64_t), s));
+  }
+  const int mask_vec = w % 16 == 0 && (uintptr_t)dev_mask % 16 == 0;
+  hipLaunchKernelGGL(cc_tile_kernel, dim3((unsigned)ntx, (unsigned)nty, (unsigned)batch), blk, 0, s, dev_mask, h, w, match_class, conn8,
+                     mask_vec, parent);
+  const long long items = (long long)(nty - 1) * w + 2LL * (ntx - 1) * h;
+  if (items > 0)
+    hipLaunchKernelGGL(cc_merge_kernel, dim3((unsigned)((items + CC_THREADS - 1) / CC_THREADS), (unsigned)batch), blk, 0, s, parent, h, w,
+                       conn8, nty - 1, ntx - 1);
+  const int par_vec = hw % 4 == 0;             // the workspace is 16-byte aligned and `parent` starts it
+  hipLaunchKernelGGL(cc_compress_kernel, per_px, blk, 0, s, parent, hw, par_vec, chunks);
+  hipLaunchKernelGGL(cc_scan_kernel, dim3((unsigned)batch), blk, 0, s, chunks, ws.nchunk, (int*)dev_num);
+  hipLaunchKernelGGL(cc_number_kernel, per_px, blk, 0, s, parent, hw, par_vec, (const int*)chunks);
+  const int lab_vec = par_vec && (uintptr_t)dev_labels % 16 == 0;
+  hipLaunchKernelGGL(cc_relabel_kernel, per_px, blk, 0, s, (const int*)parent, h, w, capacity, lab_vec, (int*)dev_labels, (int*)dev_stats,
+                     (unsigned long long*)dev_sums);
+  if (dev_stats)
+    hipLaunchKernelGGL(cc_finish_stats_kernel, dim3((unsigned)((capacity + CC_THREADS - 1) / CC_THREADS), (unsigned)batch), blk, 0, s,
+                       (int*)dev_stats, h, w, capacity);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_components_filter(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num, const int32_t* dev_stats,
+                             const uint64_t* dev_sums, int batch, int h, int w, int capacity, int rule, const unetpp_cc_rule* params,
+                             uint8_t out_value, uint8_t* dev_out, void* dev_workspace, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_labels || !dev_num || !dev_stats || !dev_sums || !params || !dev_out || !dev_workspace) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (rule != UNETPP_CC_LARGEST && rule != UNETPP_CC_SPATIAL && rule != UNETPP_CC_CABLE_SHAPE) return fail(e, UNETPP_E_INVALID, "unknown rule %d", rule);
+  if (capacity < 2) return fail(e, UNETPP_E_INVALID, "capacity %d: at least 2 rows (background + one component)", capacity);
+  if (rule == UNETPP_CC_CABLE_SHAPE && !(params->roi_width > 0)) return fail(e, UNETPP_E_INVALID, "roi_width must be positive");
+  CcWorkspace ws;
+  if (!cc_layout(batch, h, w, capacity, &ws)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  uint8_t* keep = (uint8_t*)dev_workspace + ws.keep;
+  CcRule r{params->min_area, params->min_width, params->max_width, params->min_height_ratio, params->min_aspect,
+           params->max_center_offset, params->roi_width};
+  hipLaunchKernelGGL(cc_select_kernel, dim3((unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_num, (const int*)dev_stats,
+                     (const unsigned long long*)dev_sums, h, capacity, rule, r, keep);
+  const int vec = hw % 16 == 0 && (uintptr_t)dev_labels % 16 == 0 && (uintptr_t)dev_out % 16 == 0;
+  hipLaunchKernelGGL(cc_apply_kernel, dim3((unsigned)ws.nchunk, (unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_labels,
+                     (const uint8_t*)keep, hw, capacity, vec, (unsigned)out_value, dev_out);
   HIP_TRY(e, hipGetLastError());
   return UNETPP_OK;
 }

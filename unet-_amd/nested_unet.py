@@ -11,6 +11,7 @@ and the source of the current HIP stream — no torch op runs on the hot path.
     pred = model.segment(img_tensor)       # fused replacement of :294-300 (uint8 class-index mask, on device)
     out, out1, out2, out3 = model.forward_deep_supervision(img_tensor)   # the list of unetpp.py:121-133, one pass
     pred1 = model.segment(img_tensor, output=1)   # pruned UNet++: stops after x1_3 and uses the ds1_3 head
+    cable = model.filter_components(pred, 1, rule="largest", min_area=50)   # src/utils/geometry_enhanced.py:140, on device
 """
 from __future__ import annotations
 
@@ -53,6 +54,7 @@ class NestedUNet:
         self._ds_blob: Optional[np.ndarray] = None   # deep-supervision heads (host copy, uploaded on the first ds call)
         self._ds_uploaded = False                    # ... to the current engine
         self._state_dict = None
+        self._cc_workspaces = {}                     # components(): scratch per (B, H, W, max_components)
 
     # ------------------------------------------------------------------ nn.Module surface
     def to(self, device):
@@ -347,6 +349,101 @@ class NestedUNet:
             raise RuntimeError(self._err(rc))
         widths = torch.where(rmax >= 0, (rmax - rmin + 1), torch.zeros_like(rmax)).to(torch.float32)
         return counts.to(torch.int64), widths
+
+    # ------------------------------------------------------------------ connected components
+    def _components(self, mask, match_class, connectivity, max_components, want_stats: bool):
+        import torch
+        if not (isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype == torch.uint8 and mask.dim() == 3):
+            raise RuntimeError("mask must be a uint8 CUDA tensor [B,H,W]")
+        if connectivity not in (4, 8):
+            raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+        k = int(max_components)
+        if k < 2:
+            raise ValueError(f"max_components must be at least 2 (background + one component), got {max_components!r}")
+        if self._device_index is None:
+            self.to(mask.device)
+        if mask.device.index != self._device_index:
+            raise RuntimeError(f"mask on {mask.device}, engine on cuda:{self._device_index}")
+        self._ensure_engine(1, self._SIZE_MULTIPLE, self._SIZE_MULTIPLE)
+        mask = mask.contiguous()
+        b, h, w = mask.shape
+        lib = _lib.load()
+        key = (b, h, w, k)
+        cache = self._cc_workspaces
+        ws = cache.get(key)
+        if ws is None or ws.device != mask.device:
+            nbytes = int(lib.unetpp_components_workspace_bytes(b, h, w, k))
+            if nbytes == 0:
+                raise RuntimeError(f"components: unsupported shape {tuple(mask.shape)}")
+            ws = cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=mask.device)
+        dev = mask.device
+        labels = torch.empty((b, h, w), dtype=torch.int32, device=dev)
+        num = torch.empty((b,), dtype=torch.int32, device=dev)
+        stats = torch.empty((b, k, 5), dtype=torch.int32, device=dev) if want_stats else None
+        sums = torch.empty((b, k, 2), dtype=torch.int64, device=dev) if want_stats else None   # uint64 bits; values < 2^63
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = lib.unetpp_components(self._handle, p(mask), b, h, w, int(match_class), int(connectivity), k, p(labels), p(num),
+                                   p(stats), p(sums), p(ws), stream)
+        if rc != 0:
+            raise RuntimeError(self._err(rc))
+        return labels, num, stats, sums, ws, stream
+
+    def components(self, mask, match_class: int = -1, connectivity: int = 8, max_components: int = 8192):
+        """cv2.connectedComponentsWithStats(mask == match_class, connectivity) on the device for a uint8 CUDA mask
+        [B,H,W] (any H, W; match_class < 0: mask != 0).  Returns (labels int32 [B,H,W], num int32 [B],
+        stats int32 [B,K,5], centroids float64 [B,K,2]) with K = max_components rows: stats in cv2's column order
+        LEFT, TOP, WIDTH, HEIGHT, AREA, row 0 = background, rows >= num zero (centroids NaN there); num counts the
+        background like cv2's num_labels and is exact even beyond K.  Labels are numbered in raster order of each
+        component's first pixel (scipy.ndimage.label's order, not cv2's, which only matters for ties)."""
+        import torch
+        labels, num, stats, sums, _, _ = self._components(mask, match_class, connectivity, max_components, True)
+        centroids = sums.to(torch.float64) / stats[:, :, 4:5].to(torch.float64)
+        return labels, num, stats, centroids
+
+    def filter_components(self, mask, match_class: int = -1, rule: str = "largest", *, connectivity: int = 8,
+                          max_components: int = 8192, out_value: int = 1, check: bool = True, min_area=None,
+                          min_width=50, max_width=300, min_height_ratio=0.3, min_aspect=1.6, max_center_offset=0.3,
+                          roi_width=None):
+        """The reference's component filters on the device: uint8 [B,H,W], out_value where the pixel's component is kept.
+        rule='largest'      _largest_connected_component(mask, min_area=100), src/utils/geometry_enhanced.py:81-110;
+                            min_area=0 is the tail of constrain_tape_to_ring (src/refactor/postprocess.py:106-116)
+        rule='spatial'      spatial_filter(mask, min_width, max_width, min_height_ratio), infer_video_spatial.py:24-53
+                            (min_area=1000, fixed in the reference)
+        rule='cable_shape'  filter_cable_by_shape with PostprocessConfig's min_area=1000, min_aspect, max_center_offset
+                            and roi_width (default W), src/refactor/postprocess.py:12-76; the reference's out_value is 255
+        Ties between equal areas / scores go to the lower label (raster order of first pixels).  A frame with more than
+        max_components - 1 components cannot be filtered: with check=True (one B-int read-back, synchronises) that
+        raises RuntimeError, with check=False its output is all zero."""
+        if rule not in _lib.CC_RULES:
+            raise ValueError(f"rule must be one of {sorted(_lib.CC_RULES)}")
+        if isinstance(out_value, bool) or not isinstance(out_value, (int, np.integer)) or not 1 <= int(out_value) <= 255:
+            raise ValueError(f"out_value must be an integer in 1..255, got {out_value!r}")
+        import torch
+        labels, num, stats, sums, ws, stream = self._components(mask, match_class, connectivity, max_components, True)
+        b, h, w = labels.shape
+        k = int(max_components)
+        if min_area is None:
+            min_area = 100 if rule == "largest" else 1000
+        if roi_width is None:
+            roi_width = w
+        if rule == "cable_shape" and not float(roi_width) > 0:
+            raise ValueError(f"roi_width must be positive, got {roi_width!r}")
+        params = _lib.CcRule(float(min_area), float(min_width), float(max_width), float(min_height_ratio), float(min_aspect),
+                             float(max_center_offset), float(roi_width))
+        out = torch.empty((b, h, w), dtype=torch.uint8, device=labels.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        rc = _lib.load().unetpp_components_filter(self._handle, p(labels), p(num), p(stats), p(sums), b, h, w, k,
+                                                  _lib.CC_RULES[rule], ctypes.byref(params), int(out_value), p(out), p(ws), stream)
+        if rc != 0:
+            raise RuntimeError(self._err(rc))
+        if check:
+            n = num.cpu().tolist()
+            for i, v in enumerate(n):
+                if v > k:
+                    raise RuntimeError(f"filter_components: frame {i} has num = {v} labels (background included), more than "
+                                       f"max_components = {k}: raise max_components")
+        return out
 
     def resize_frames(self, frames, size_hw):
         """cv2.resize(frame, (W, H), interpolation=cv2.INTER_LINEAR) for uint8 CUDA frames [B,h,w,C] -> [B,H,W,C]

@@ -282,6 +282,66 @@ int unetpp_components_filter(unetpp_engine* e, const int32_t* dev_labels, const 
                              int capacity, int rule, const unetpp_cc_rule* params, uint8_t out_value,
                              uint8_t* dev_out, void* dev_workspace, void* stream);
 
+/* ---- binary morphology programs on the device ------------------------------------------------------------------
+ * cv2.dilate / cv2.erode / cv2.morphologyEx (OPEN, CLOSE) with a structuring element on class masks, and the short
+ * programs the reference builds from them (src/refactor/postprocess.py:79-118 and :144-166,
+ * src/utils/geometry_enhanced.py:281-289, src/refactor/burr_detector.py:37-41, infer_two_stage_burr.py:78-79), each
+ * program in ONE kernel launch.  Everything is boolean: results are exact.
+ *
+ * Masks are uint8 [B,h,w] on the device, any h, w >= 1 (h, w <= 65535, h * w <= 2^30).  Foreground of dev_mask0 is
+ * (mask == match0), or (mask != 0) for match0 < 0; likewise dev_mask1 / match1.  dev_mask1 may be NULL.
+ *
+ * Semantics (OpenCV's published definition; cv2 itself is not available to the tests, so its own output stays
+ * unpinned).  An element is uint8 [kh,kw], row-major in HOST memory (read during the call), with anchor (ax, ay);
+ * ax = -1 / ay = -1 mean kw / 2 and kh / 2.
+ *   dilate: dst(x,y) = OR  over (i,j) with elem[i][j] != 0 of src(x + j - ax, y + i - ay)
+ *   erode:  dst(x,y) = AND over (i,j) with elem[i][j] != 0 of src(x + j - ax, y + i - ay)
+ * The element is NOT reflected (this differs from scipy.ndimage.binary_dilation for an asymmetric element such as
+ * cv2's ELLIPSE (8,8)).  Pixels outside the image do not contribute: they count as 0 for a dilate and as 1 for an
+ * erode, at every step and every iteration (BORDER_CONSTANT with morphologyDefaultBorderValue).  iterations = n
+ * repeats the step n times.  cv2 replaces n iterations of a RECT element by one pass with an enlarged element and a
+ * scaled anchor, which differs for an anchor off the centre: that shortcut is not imitated and stays unpinned.
+ *
+ * Planes: P0 = fg(dev_mask0), P1 = fg(dev_mask1) (all zero for NULL), P2 and P3 scratch.  A program is at most 8
+ * steps {op, dst, a, b, element, iterations}:
+ *   UNETPP_MORPH_DILATE / _ERODE   P[dst] = op^iterations(P[a]) with elements[element]   (b unused)
+ *   UNETPP_MORPH_AND / _ANDNOT / _OR   P[dst] = P[a] & P[b] / P[a] & ~P[b] / P[a] | P[b]  (element, iterations unused)
+ *   UNETPP_MORPH_COPY                  P[dst] = P[a]
+ * dst may be any plane, a or b included.  dev_out uint8 [B,h,w] = out_value where P[result_plane] is set, else 0.
+ * open = ERODE then DILATE, close = DILATE then ERODE (cv2.morphologyEx, each with the same iterations).
+ *
+ * Limits: at most 4 elements, each at most 63 x 63 and ROW-CONVEX (the non-zeros of every row form one run: rect,
+ * cross and every ellipse are); the sum of iterations * (kh - 1) over the program's dilates and erodes at most 126,
+ * and the same for kw (a close with one 63 x 63 element, or close(E5, iterations=2) then dilate(E3), fit).
+ * Beyond these: UNETPP_E_UNSUPPORTED, never a wrong result.  UNETPP_E_INVALID for NULL dev_mask0 / dev_out, a bad
+ * shape, op, plane or element index, a step or result_plane reading a scratch plane no earlier step wrote,
+ * iterations < 1, an empty element, an anchor outside the element, and dev_out overlapping an input mask
+ * (workgroups read halo rows their neighbours write).  After an error dev_out is untouched.
+ * No allocation, no device workspace; program and elements travel as kernel arguments.  Asynchronous on `stream`.
+ *
+ * unetpp_morphology_layout reports how the kernel tiles a program (no engine, no device needed): band_rows = rows
+ * of a frame one workgroup owns, tile_cols = its columns (a multiple of 64, >= w when rows are not split).  Tests
+ * aim at these boundaries; callers need not care. */
+enum { UNETPP_MORPH_DILATE = 0, UNETPP_MORPH_ERODE = 1, UNETPP_MORPH_AND = 2, UNETPP_MORPH_ANDNOT = 3,
+       UNETPP_MORPH_OR = 4, UNETPP_MORPH_COPY = 5 };
+
+typedef struct unetpp_morph_element {
+  int kw, kh;                /* 1..63 each */
+  int ax, ay;                /* anchor, 0 <= ax < kw, 0 <= ay < kh; -1 = centre (k / 2) */
+  const uint8_t* host_data;  /* [kh,kw], row-major, non-zero = member */
+} unetpp_morph_element;
+
+typedef struct unetpp_morph_step {
+  int op, dst, a, b, element, iterations;
+} unetpp_morph_step;
+
+int unetpp_morphology(unetpp_engine* e, const uint8_t* dev_mask0, int match0, const uint8_t* dev_mask1, int match1,
+                      int batch, int h, int w, const unetpp_morph_element* elements, int n_elements,
+                      const unetpp_morph_step* steps, int n_steps, int result_plane, uint8_t out_value,
+                      uint8_t* dev_out, void* stream);
+int unetpp_morphology_layout(int batch, int h, int w, const unetpp_morph_element* elements, int n_elements,
+                             const unetpp_morph_step* steps, int n_steps, int* band_rows, int* tile_cols);
+
 /* ---- frame glue either side of the model --------------------------------
  * unetpp_resize_linear_u8 replaces `cv2.resize(frame_rgb, target_size, interpolation=cv2.INTER_LINEAR)`
  * of preprocess_image (infer_two_stage_burr.py:124; also the --normalize-resolution resize, :281):

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunetpp_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["unetpp_abi.hip"]
-HEADERS = ["conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "components.h", os.path.join("..", "..", "include", "unetpp.h")]
+HEADERS = ["conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "components.h", "morphology.h", os.path.join("..", "..", "include", "unetpp.h")]
 
 # every symbol include/unetpp.h declares
 ABI_SYMBOLS = [
@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "unetpp_profile_work", "unetpp_debug_read", "unetpp_debug_keep_intermediates",
     "unetpp_ds_blob_bytes", "unetpp_load_ds_heads", "unetpp_forward_ds",
     "unetpp_components_workspace_bytes", "unetpp_components", "unetpp_components_filter",
+    "unetpp_morphology", "unetpp_morphology_layout",
 ]
 
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
@@ -48,6 +49,20 @@ class CcRule(ctypes.Structure):
 
 
 CC_RULES = {"largest": 0, "spatial": 1, "cable_shape": 2}
+
+
+class MorphElement(ctypes.Structure):
+    """unetpp_morph_element: a structuring element in host memory, uint8 [kh,kw], anchor (ax, ay)."""
+    _fields_ = [("kw", ctypes.c_int), ("kh", ctypes.c_int), ("ax", ctypes.c_int), ("ay", ctypes.c_int),
+                ("host_data", ctypes.c_void_p)]
+
+
+class MorphStep(ctypes.Structure):
+    """unetpp_morph_step: P[dst] = op(P[a], P[b]) with elements[element], repeated `iterations` times."""
+    _fields_ = [(n, ctypes.c_int) for n in ("op", "dst", "a", "b", "element", "iterations")]
+
+
+MORPH_OPS = {"dilate": 0, "erode": 1, "and": 2, "andnot": 3, "or": 4, "copy": 5}
 RULES = {"argmax": 0, "thresholded_argmax": 1, "strict_bg_check": 2, "exclusive": 3}
 
 
@@ -182,6 +197,12 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     lib.unetpp_components.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]; lib.unetpp_components.restype = ci
     lib.unetpp_components_filter.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(CcRule), ctypes.c_uint8, vp, vp, vp]
     lib.unetpp_components_filter.restype = ci
+    lib.unetpp_morphology.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ctypes.POINTER(MorphElement), ci, ctypes.POINTER(MorphStep), ci, ci,
+                                      ctypes.c_uint8, vp, vp]
+    lib.unetpp_morphology.restype = ci
+    lib.unetpp_morphology_layout.argtypes = [ci, ci, ci, ctypes.POINTER(MorphElement), ci, ctypes.POINTER(MorphStep), ci,
+                                             ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    lib.unetpp_morphology_layout.restype = ci
     ver = lib.unetpp_version().decode()
     if ver.endswith(" +wsdbg") and os.environ.get("UNETPP_ALLOW_DBG_LIB"):
         ver = ver[:-len(" +wsdbg")]            # measurement build with phase ablations (scripts/ws_ablate.sh)

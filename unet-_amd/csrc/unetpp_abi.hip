@@ -33,6 +33,7 @@
 #include "conv3x3_mfma.h"
 #include "conv3x3_ws.h"
 #include "convt2x2_mfma.h"
+#include "morphology.h"
 #include "tapmm_ws.h"
 
 using namespace unetpp;
@@ -1397,6 +1398,154 @@ int unetpp_components_filter(unetpp_engine* e, const int32_t* dev_labels, const 
   const int vec = hw % 16 == 0 && (uintptr_t)dev_labels % 16 == 0 && (uintptr_t)dev_out % 16 == 0;
   hipLaunchKernelGGL(cc_apply_kernel, dim3((unsigned)ws.nchunk, (unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_labels,
                      (const uint8_t*)keep, hw, capacity, vec, (unsigned)out_value, dev_out);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+// ---- binary morphology programs (morphology.h) ------------------------------------------------------------------
+}  // extern "C"
+namespace {
+struct MorphPlan {
+  MorphArgs args;
+  dim3 grid;
+  size_t lds_bytes = 0;
+};
+
+// Checks a program and lays its tiles out.  Everything the kernel indexes with is validated here.
+int morph_plan(unetpp_engine* e, int batch, int h, int w, const unetpp_morph_element* elements, int n_elements,
+               const unetpp_morph_step* steps, int n_steps, int result_plane, MorphPlan* plan) {
+  if (batch < 1 || batch > 65535 || h < 1 || w < 1 || h > 65535 || w > 65535 || (size_t)h * w > (1u << 30))
+    return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if (n_elements < 0 || n_elements > MORPH_MAX_ELEMENTS || (n_elements > 0 && !elements))
+    return fail(e, UNETPP_E_INVALID, "n_elements %d not in [0,%d]", n_elements, MORPH_MAX_ELEMENTS);
+  if (n_steps < 0 || n_steps > MORPH_MAX_STEPS || (n_steps > 0 && !steps))
+    return fail(e, UNETPP_E_INVALID, "n_steps %d not in [0,%d]", n_steps, MORPH_MAX_STEPS);
+  MorphArgs& A = plan->args;
+  std::memset(&A, 0, sizeof A);
+  int ax[MORPH_MAX_ELEMENTS], ay[MORPH_MAX_ELEMENTS];
+  for (int k = 0; k < n_elements; ++k) {
+    const unetpp_morph_element& el = elements[k];
+    if (el.kw < 1 || el.kh < 1 || !el.host_data) return fail(e, UNETPP_E_INVALID, "element %d: bad size %dx%d or NULL data", k, el.kw, el.kh);
+    if (el.kw > MORPH_MAX_K || el.kh > MORPH_MAX_K)
+      return fail(e, UNETPP_E_UNSUPPORTED, "element %d is %dx%d: too large, at most %dx%d", k, el.kw, el.kh, MORPH_MAX_K, MORPH_MAX_K);
+    ax[k] = el.ax < 0 ? el.kw / 2 : el.ax;
+    ay[k] = el.ay < 0 ? el.kh / 2 : el.ay;
+    if (ax[k] >= el.kw || ay[k] >= el.kh) return fail(e, UNETPP_E_INVALID, "element %d: anchor (%d,%d) outside %dx%d", k, el.ax, el.ay, el.kw, el.kh);
+    MorphElem& E = A.elem[k];
+    for (int i = 0; i < el.kh; ++i) {
+      const uint8_t* r = el.host_data + (size_t)i * el.kw;
+      int first = -1, last = -1, count = 0;
+      for (int j = 0; j < el.kw; ++j)
+        if (r[j]) { if (first < 0) first = j; last = j; ++count; }
+      if (!count) continue;
+      if (count != last - first + 1)
+        return fail(e, UNETPP_E_UNSUPPORTED, "element %d is not row-convex: the non-zeros of row %d are not one run", k, i);
+      E.row[E.nrows++] = MorphRow{(signed char)(i - ay[k]), (signed char)(first - ax[k]), (signed char)(last - ax[k]), 0};
+    }
+    if (!E.nrows) return fail(e, UNETPP_E_INVALID, "element %d is empty (all zero)", k);
+    std::sort(E.row, E.row + E.nrows, [](const MorphRow& p, const MorphRow& q) {
+      return std::make_tuple(p.lo, p.hi, p.dy) < std::make_tuple(q.lo, q.hi, q.dy);
+    });
+  }
+  bool written[MORPH_USER_PLANES] = {true, true, false, false};     // plane 1 is all zero without a second mask
+  auto plane_ok = [](int p) { return p >= 0 && p < MORPH_USER_PLANES; };
+  int up = 0, down = 0, left = 0, right = 0;
+  for (int s = 0; s < n_steps; ++s) {
+    const unetpp_morph_step& st = steps[s];
+    if (st.op < UNETPP_MORPH_DILATE || st.op > UNETPP_MORPH_COPY) return fail(e, UNETPP_E_INVALID, "step %d: unknown op %d", s, st.op);
+    const bool morph = st.op == UNETPP_MORPH_DILATE || st.op == UNETPP_MORPH_ERODE;
+    const bool binary = st.op == UNETPP_MORPH_AND || st.op == UNETPP_MORPH_ANDNOT || st.op == UNETPP_MORPH_OR;
+    if (!plane_ok(st.dst) || !plane_ok(st.a) || (binary && !plane_ok(st.b)))
+      return fail(e, UNETPP_E_INVALID, "step %d: plane index out of range [0,%d)", s, MORPH_USER_PLANES);
+    if (!written[st.a] || (binary && !written[st.b]))
+      return fail(e, UNETPP_E_INVALID, "step %d reads scratch plane %d before any step has written it", s, !written[st.a] ? st.a : st.b);
+    MorphStep& D = A.step[s];
+    D.op = st.op; D.dst = st.dst; D.a = st.a; D.b = binary ? st.b : st.a; D.elem = 0; D.iters = 1;
+    if (morph) {
+      if (st.element < 0 || st.element >= n_elements) return fail(e, UNETPP_E_INVALID, "step %d: element index %d not in [0,%d)", s, st.element, n_elements);
+      if (st.iterations < 1) return fail(e, UNETPP_E_INVALID, "step %d: iterations must be at least 1, got %d", s, st.iterations);
+      if (st.iterations > MORPH_MAX_REACH) return fail(e, UNETPP_E_UNSUPPORTED, "step %d: iterations %d beyond %d", s, st.iterations, MORPH_MAX_REACH);
+      D.elem = st.element; D.iters = st.iterations;
+      const unetpp_morph_element& el = elements[st.element];
+      up += st.iterations * ay[st.element]; down += st.iterations * (el.kh - 1 - ay[st.element]);
+      left += st.iterations * ax[st.element]; right += st.iterations * (el.kw - 1 - ax[st.element]);
+      if (up + down > MORPH_MAX_REACH || left + right > MORPH_MAX_REACH)
+        return fail(e, UNETPP_E_UNSUPPORTED, "the program's reach (sum of iterations * (k - 1) over its dilates and erodes) exceeds %d pixels "
+                    "(vertical %d, horizontal %d)", MORPH_MAX_REACH, up + down, left + right);
+    }
+    written[st.dst] = true;
+  }
+  if (!plane_ok(result_plane) || !written[result_plane])
+    return fail(e, UNETPP_E_INVALID, "result_plane %d is out of range or never written", result_plane);
+  A.n_steps = n_steps; A.result = result_plane;
+  A.H = h; A.W = w; A.wpr = (w + 63) / 64;
+  const int halo = up + down;
+  int band_max;
+  if (A.wpr * (halo + 1) <= MORPH_PLANE_WORDS) {            // bands of full-width rows: no horizontal halo
+    A.cw = A.wpr; A.hl = 0; A.tw = A.wpr;
+    band_max = MORPH_PLANE_WORDS / A.wpr - halo;
+    // enough workgroups to fill the device before the bands grow: at most as much halo as core, never below 16 rows
+    int band = std::min(std::max(halo, 16), band_max);
+    while ((long long)batch * ((h + band - 1) / band) > 2048 && band * 2 <= band_max) band *= 2;
+    band = std::min(band, h);
+    // one thread per word and pass: grow the band until the window's words fill whole passes of the workgroup
+    int unit = MORPH_THREADS;
+    for (int a = MORPH_THREADS, b = A.wpr; b;) { const int r = a % b; a = b; b = r; unit = MORPH_THREADS / a; }
+    const int rows_up = (band + halo + unit - 1) / unit * unit;
+    if (rows_up - halo <= std::min(band_max, h)) band = rows_up - halo;
+    A.band = band;
+  } else {                                                  // tiles with a halo on all four sides: the best core share
+    const int hl = (left + 63) / 64, hr = (right + 63) / 64;
+    double best = -1.0;
+    for (int cw = 1; cw <= std::min(A.wpr, 64); ++cw) {
+      const int bm = std::min(MORPH_PLANE_WORDS / (cw + hl + hr) - halo, h);
+      if (bm < 1) break;
+      const double share = (double)cw * bm / ((double)(cw + hl + hr) * (bm + halo));
+      if (share > best) { best = share; A.cw = cw; A.band = bm; }
+    }
+    A.hl = hl; A.tw = A.cw + hl + hr;
+  }
+  A.up = up; A.rows = A.band + halo;
+  plan->grid = dim3((unsigned)((A.wpr + A.cw - 1) / A.cw), (unsigned)((h + A.band - 1) / A.band), (unsigned)batch);
+  plan->lds_bytes = (size_t)MORPH_PLANES * A.rows * A.tw * sizeof(unsigned long long);
+  if (A.band < 1 || A.rows * A.tw > MORPH_PLANE_WORDS) return fail(e, UNETPP_E_STATE, "internal: morphology tile layout");
+  return UNETPP_OK;
+}
+}  // namespace
+extern "C" {
+
+int unetpp_morphology_layout(int batch, int h, int w, const unetpp_morph_element* elements, int n_elements,
+                             const unetpp_morph_step* steps, int n_steps, int* band_rows, int* tile_cols) {
+  if (!band_rows || !tile_cols) return fail(nullptr, UNETPP_E_INVALID, "null argument");
+  MorphPlan plan;
+  const int rc = morph_plan(nullptr, batch, h, w, elements, n_elements, steps, n_steps, n_steps > 0 ? steps[n_steps - 1].dst : 0, &plan);
+  if (rc != UNETPP_OK) return rc;
+  *band_rows = plan.args.band;
+  *tile_cols = plan.args.cw * 64;
+  return UNETPP_OK;
+}
+
+int unetpp_morphology(unetpp_engine* e, const uint8_t* dev_mask0, int match0, const uint8_t* dev_mask1, int match1, int batch,
+                      int h, int w, const unetpp_morph_element* elements, int n_elements, const unetpp_morph_step* steps,
+                      int n_steps, int result_plane, uint8_t out_value, uint8_t* dev_out, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_mask0 || !dev_out) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (match0 > 255 || match1 > 255) return fail(e, UNETPP_E_INVALID, "match_class %d out of range", match0 > 255 ? match0 : match1);
+  MorphPlan plan;
+  const int rc = morph_plan(e, batch, h, w, elements, n_elements, steps, n_steps, result_plane, &plan);
+  if (rc != UNETPP_OK) return rc;
+  const size_t n = (size_t)batch * h * w;
+  auto overlaps = [&](const uint8_t* p) { return p && p < dev_out + n && dev_out < p + n; };
+  if (overlaps(dev_mask0) || overlaps(dev_mask1))
+    return fail(e, UNETPP_E_INVALID, "dev_out aliases an input mask: every workgroup reads the halo rows its neighbours write");
+  ENTER_DEVICE(e);
+  MorphArgs& A = plan.args;
+  A.match0 = match0; A.match1 = match1; A.out_value = out_value;
+  A.vec0 = w % 16 == 0 && (uintptr_t)dev_mask0 % 16 == 0;
+  A.vec1 = w % 16 == 0 && (uintptr_t)dev_mask1 % 16 == 0;
+  A.vec_out = w % 16 == 0 && (uintptr_t)dev_out % 16 == 0;
+  hipLaunchKernelGGL(morph_program_kernel, plan.grid, dim3(MORPH_THREADS), plan.lds_bytes, (hipStream_t)stream, dev_mask0, dev_mask1,
+                     dev_out, A);
   HIP_TRY(e, hipGetLastError());
   return UNETPP_OK;
 }

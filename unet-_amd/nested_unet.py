@@ -55,6 +55,7 @@ class NestedUNet:
         self._ds_uploaded = False                    # ... to the current engine
         self._state_dict = None
         self._cc_workspaces = {}                     # components(): scratch per (B, H, W, max_components)
+        self._morph_programs = {}                    # morphology programs in their ctypes form, per parameter set
 
     # ------------------------------------------------------------------ nn.Module surface
     def to(self, device):
@@ -444,6 +445,144 @@ class NestedUNet:
                     raise RuntimeError(f"filter_components: frame {i} has num = {v} labels (background included), more than "
                                        f"max_components = {k}: raise max_components")
         return out
+
+    # ------------------------------------------------------------------ binary morphology
+    @staticmethod
+    def _check_out_value(out_value):
+        if isinstance(out_value, bool) or not isinstance(out_value, (int, np.integer)) or not 1 <= int(out_value) <= 255:
+            raise ValueError(f"out_value must be an integer in 1..255, got {out_value!r}")
+        return int(out_value)
+
+    def _morph_compile(self, key, elements, steps, result_plane):
+        """The ctypes form of a checked program; cached under `key` (None: not cached).  The element arrays stay
+        referenced from the entry: the C structures point into them."""
+        if key is not None and key in self._morph_programs:
+            return self._morph_programs[key]
+        from . import morphology as mo
+        elements, steps = mo.check_program(elements, steps, result_plane)
+        c_el = (_lib.MorphElement * max(len(elements), 1))()
+        for i, (arr, (ax, ay)) in enumerate(elements):
+            c_el[i] = _lib.MorphElement(arr.shape[1], arr.shape[0], ax, ay, arr.ctypes.data)
+        c_st = (_lib.MorphStep * max(len(steps), 1))()
+        for i, st in enumerate(steps):
+            c_st[i] = _lib.MorphStep(*st)
+        entry = (elements, c_el, len(elements), c_st, len(steps), int(result_plane))
+        if key is not None:
+            self._morph_programs[key] = entry
+        return entry
+
+    def _morph_launch(self, compiled, mask0, match0, mask1, match1, out_value):
+        import torch
+        for m in (mask0,) + (() if mask1 is None else (mask1,)):
+            if not (isinstance(m, torch.Tensor) and m.is_cuda and m.dtype == torch.uint8 and m.dim() == 3):
+                raise RuntimeError("mask must be a uint8 CUDA tensor [B,H,W]")
+        if mask1 is not None and (mask1.shape != mask0.shape or mask1.device != mask0.device):
+            raise RuntimeError(f"mask1 {tuple(mask1.shape)} on {mask1.device} does not match mask0 {tuple(mask0.shape)} on {mask0.device}")
+        if self._device_index is None:
+            self.to(mask0.device)
+        if mask0.device.index != self._device_index:
+            raise RuntimeError(f"mask on {mask0.device}, engine on cuda:{self._device_index}")
+        self._ensure_engine(1, self._SIZE_MULTIPLE, self._SIZE_MULTIPLE)
+        mask0 = mask0.contiguous()
+        mask1 = None if mask1 is None else mask1.contiguous()
+        b, h, w = mask0.shape
+        _, c_el, n_el, c_st, n_st, result = compiled
+        out = torch.empty((b, h, w), dtype=torch.uint8, device=mask0.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = _lib.load().unetpp_morphology(self._handle, p(mask0), int(match0), p(mask1), int(match1), b, h, w, c_el, n_el, c_st, n_st,
+                                           result, out_value, p(out), ctypes.c_void_p(torch.cuda.current_stream(mask0.device).cuda_stream))
+        if rc != 0:
+            raise (ValueError if rc == -2 else RuntimeError)(self._err(rc))
+        return out
+
+    def morphology_program(self, mask0, match0, steps, elements, mask1=None, match1: int = -1, result_plane: int = 2,
+                           out_value: int = 1):
+        """One launch of a morphology program (include/unetpp.h, unetpp_morphology) on uint8 CUDA masks [B,H,W]: planes
+        P0 = (mask0 == match0), P1 = (mask1 == match1) (match < 0: != 0; all zero without mask1), P2 / P3 scratch; steps
+        are (op, dst, a, b, element, iterations) with op in dilate | erode | and | andnot | or | copy; elements are uint8
+        arrays [kh,kw] or (array, (ax, ay)).  Returns uint8 [B,H,W] = out_value where P[result_plane] is set.  The
+        semantics are cv2's (element not reflected, outside pixels never contribute); see unet_amd/morphology.py.
+        ValueError for what the kernel does not support (element above 63, not row-convex, reach above 126)."""
+        out_value = self._check_out_value(out_value)
+        return self._morph_launch(self._morph_compile(None, elements, steps, result_plane), mask0, match0, mask1, match1, out_value)
+
+    def morphology(self, mask, match_class: int = -1, op: str = "close", ksize=5, shape: str = "ellipse", iterations: int = 1,
+                   element=None, anchor=None, out_value: int = 1):
+        """cv2.dilate / cv2.erode / cv2.morphologyEx(MORPH_OPEN | MORPH_CLOSE) of (mask == match_class) with
+        getStructuringElement(shape, ksize) (restated, unet_amd/morphology.py) or a caller-supplied `element` (e.g.
+        cv2's own kernel) and `anchor` (ax, ay); open / close are one launch.  uint8 [B,H,W], out_value where set."""
+        from . import morphology as mo
+        out_value = self._check_out_value(out_value)
+        if element is None:
+            key = ("single", op, shape, ksize if isinstance(ksize, (int, np.integer)) else tuple(ksize), anchor if anchor is None else tuple(anchor),
+                   int(iterations))
+            if key not in self._morph_programs:
+                self._morph_compile(key, *mo.program_single(op, mo.structuring_element(shape, ksize), anchor, int(iterations)))
+            compiled = self._morph_programs[key]
+        else:
+            compiled = self._morph_compile(None, *mo.program_single(op, element, anchor, int(iterations)))
+        return self._morph_launch(compiled, mask, match_class, None, -1, out_value)
+
+    def _morph_named(self, name, params, builder):
+        key = (name,) + tuple(params)
+        if key not in self._morph_programs:
+            self._morph_compile(key, *builder(*params))
+        return self._morph_programs[key]
+
+    def morphology_cleanup(self, mask, match_class: int = -1, kernel_size: int = 3, out_value: int = 1):
+        """apply_morphology_cleanup (src/refactor/postprocess.py:144-166): open then close with ELLIPSE (k, k), one launch."""
+        from . import morphology as mo
+        out_value = self._check_out_value(out_value)
+        return self._morph_launch(self._morph_named("cleanup", (int(kernel_size),), mo.program_cleanup), mask, match_class, None, -1, out_value)
+
+    def boundary_band(self, mask_cable, match_class: int = -1, band_out: int = 10, out_value: int = 255):
+        """The outer band of src/refactor/burr_detector.py:37-41: dilate(cable, ELLIPSE (2 band_out + 1)) - cable, one launch."""
+        from . import morphology as mo
+        out_value = self._check_out_value(out_value)
+        return self._morph_launch(self._morph_named("band", (int(band_out),), mo.program_band), mask_cable, match_class, None, -1, out_value)
+
+    def constrain_tape_to_ring(self, mask_tape, mask_cable, tape_class: int = -1, cable_class: int = -1, ring_dilate: int = 15,
+                               ring_erode: int = 5, out_value: int = 255, max_components: int = 8192, check: bool = True):
+        """constrain_tape_to_ring (src/refactor/postprocess.py:79-118): tape & (dilate(cable, E15) - erode(cable, E5)) in one
+        morphology launch, then its largest component (filter_components, rule='largest', min_area=0)."""
+        from . import morphology as mo
+        out_value = self._check_out_value(out_value)
+        ring = self._morph_launch(self._morph_named("ring", (int(ring_dilate), int(ring_erode)), mo.program_ring), mask_tape, tape_class,
+                                  mask_cable, cable_class, 1)
+        return self.filter_components(ring, 1, rule="largest", min_area=0, out_value=out_value, max_components=max_components, check=check)
+
+    def postprocess_masks(self, pred, cable_class: int = 1, tape_class: int = 2, roi_width=None, *, min_area=1000, min_aspect=1.6,
+                          max_center_offset=0.3, ring_dilate: int = 15, ring_erode: int = 5, out_value: int = 255,
+                          max_components: int = 8192, check: bool = True):
+        """postprocess_masks (src/refactor/postprocess.py:121-141, PostprocessConfig defaults) on a class mask [B,H,W]:
+        (filter_cable_by_shape(pred == cable_class), constrain_tape_to_ring(pred == tape_class, filtered cable)), both
+        uint8 [B,H,W] with out_value (255 in the reference), nothing leaving the device."""
+        cable = self.filter_components(pred, cable_class, rule="cable_shape", min_area=min_area, min_aspect=min_aspect,
+                                       max_center_offset=max_center_offset, roi_width=roi_width, out_value=out_value,
+                                       max_components=max_components, check=check)
+        tape = self.constrain_tape_to_ring(pred, cable, tape_class, -1, ring_dilate, ring_erode, out_value, max_components, check)
+        return cable, tape
+
+    def tape_holes(self, pred, tape_class: int = 2, hole_min_size: int = 10, max_components: int = 8192, check: bool = True):
+        """The hole statistics of analyze_defects (src/utils/geometry_enhanced.py:281-295): holes = close(tape, ELLIPSE (5,5))
+        - tape (one morphology launch), then the components with area >= hole_min_size.  Returns (tape_num_holes,
+        hole area) as int64 [B] on the device, reduced there from the components' stats.  A frame with more than
+        max_components - 1 hole components cannot be counted: with check=True (one B-int read-back, synchronises) that
+        raises RuntimeError as filter_components does, with check=False its counts cover the first max_components - 1."""
+        import torch
+        from . import morphology as mo
+        holes = self._morph_launch(self._morph_named("holes", (), mo.program_holes), pred, tape_class, None, -1, 1)
+        k = int(max_components)
+        _, num, stats, _, _, _ = self._components(holes, -1, 8, k, True)
+        area = stats[:, 1:, 4].to(torch.int64)
+        valid = area >= int(hole_min_size)
+        num_holes, hole_area = valid.sum(1), (area * valid).sum(1)
+        if check:
+            for i, v in enumerate(num.cpu().tolist()):
+                if v > k:
+                    raise RuntimeError(f"filter_components: frame {i} has num = {v} labels (background included), more than "
+                                       f"max_components = {k}: raise max_components")
+        return num_holes, hole_area
 
     def resize_frames(self, frames, size_hw):
         """cv2.resize(frame, (W, H), interpolation=cv2.INTER_LINEAR) for uint8 CUDA frames [B,h,w,C] -> [B,H,W,C]

@@ -282,6 +282,70 @@ int unetpp_components_filter(unetpp_engine* e, const int32_t* dev_labels, const 
                              int capacity, int rule, const unetpp_cc_rule* params, uint8_t out_value,
                              uint8_t* dev_out, void* dev_workspace, void* stream);
 
+/* ---- stage-2 burr detection on the device: grey, blur, Canny, Laplacian band, box rule -----------------------------
+ * What the reference's frame loop does after every segmentation: detect_burrs_on_cable(frame_gray, mask_cable, cfg)
+ * (infer_two_stage_burr.py:50-119 and :317-318, infer_high_res_custom_roi.py:50-93) and its Laplacian variant
+ * get_burr_mask_rulebased (src/refactor/burr_detector.py:11-66).  Their band, close / open and component steps are
+ * unetpp_morphology and unetpp_components above; the entries here are the grey-level steps and the final choice.
+ * All arithmetic is integer and restated from OpenCV's published algorithms (unet_amd/edges.py is the NumPy form);
+ * cv2 itself is not available to the tests, so its own output stays unpinned.  Everything is asynchronous on `stream`.
+ *
+ * Shapes: uint8 [B,h,w] images on the device.  unetpp_gaussian_blur_u8 and unetpp_canny_u8 need 8 <= h, w <= 65535 and
+ * h * w <= 2^30 (UNETPP_E_UNSUPPORTED beyond, UNETPP_E_INVALID for a shape below 1), any size in between.
+ *
+ * unetpp_gray_u8: cv2.cvtColor(frame, COLOR_BGR2GRAY) (burr_detector.py:27-28) for uint8 [B,h,w,3]:
+ *   (3735 B + 19235 G + 9798 R + 16384) >> 15, OpenCV 4's 15-bit constants (3.x used a 14-bit set).
+ *
+ * unetpp_gaussian_blur_u8: cv2.GaussianBlur(gray, (k, k), sigma) (infer_two_stage_burr.py:85) with the kernel given as
+ * `taps`: n_taps (odd, <= 7: UNETPP_E_UNSUPPORTED above) integers with 8 fractional bits that sum to 256
+ * (UNETPP_E_INVALID otherwise), read from HOST memory during the call.  Horizontal pass into a 16-bit 8.8 value,
+ * vertical pass into 32 bits, (acc + 32768) >> 16; BORDER_REFLECT_101 on both axes.  A caller holding cv2's own
+ * fixed-point kernel passes it here.  dev_out must not overlap dev_gray.
+ *
+ * unetpp_canny_u8: cv2.Canny(blurred, low, high) (infer_two_stage_burr.py:86; L2gradient off, aperture 3), with the
+ * blur fused when taps != NULL (taps == NULL: dev_gray is used as it is).  3x3 Sobel with BORDER_REPLICATE of the
+ * blurred image, mag = |dx| + |dy|, 0 outside the image; candidate if mag > floor(low) and it passes the non-maximum
+ * test along its direction (TG22 = 13573 in 15 bits: with x = |dx|, y = |dy| << 15: y < x TG22 horizontal,
+ * m > left && m >= right; y > x TG22 + (x << 16) vertical, m > up && m >= down; otherwise the diagonal chosen by the
+ * sign of dx ^ dy, strict on both sides); strong if mag > floor(high).  dev_out uint8 [B,h,w] = 255 on every candidate
+ * that is 8-connected to a strong pixel through candidates, else 0.  low > high swaps them, as cv2 does.  The
+ * hysteresis is not iterated: the candidates are labelled with the launches of unetpp_components and a flag per root
+ * pixel decides, so the result is the same bits from run to run and no component count limits it.
+ * dev_workspace: unetpp_canny_workspace_bytes(batch, h, w) bytes (0 for bad arguments), 16-byte aligned, the
+ * caller's; nothing is allocated per call.  unetpp_canny_layout reports the core rows x columns of one workgroup's
+ * tile (no engine, no device needed); tests aim at these seams, callers need not care.
+ *
+ * unetpp_laplacian_band_u8: burr_detector.py:44-51 in one launch: dev_out = 255 where dev_band != 0 and
+ * (|L| & 255) > threshold, else 0, with L = cv2.Laplacian(gray, CV_64F) = 4 neighbours - 4 centre under
+ * BORDER_REFLECT_101.  `& 255` is what the reference's np.abs(L).astype(np.uint8) does to the values above 255
+ * (300 -> 44); it is the reference's behaviour and is reproduced.  h, w >= 2.  dev_out must not overlap dev_gray.
+ *
+ * unetpp_components_filter_box: the loop of infer_two_stage_burr.py:100-117 (and burr_detector.py:53-64 with
+ * max_aspect = infinity, min_side = 0) from the outputs of unetpp_components (same batch, h, w, capacity,
+ * workspace): keeps EVERY component with min_area <= area <= max_area and
+ * max(w,h) / (min(w,h) + 1e-6) < max_aspect (fp64, no contraction) and w > min_side and h > min_side.
+ * As for unetpp_components_filter, a frame with num > capacity gives all zero. */
+typedef struct unetpp_cc_box_rule {
+  double min_area;           /* 30 */
+  double max_area;           /* 800 */
+  double max_aspect;         /* 5.0 */
+  double min_side;           /* 3 */
+} unetpp_cc_box_rule;
+
+int unetpp_gray_u8(unetpp_engine* e, const uint8_t* dev_bgr, int batch, int h, int w, uint8_t* dev_gray, void* stream);
+int unetpp_gaussian_blur_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h, int w, const int32_t* taps,
+                            int n_taps, uint8_t* dev_out, void* stream);
+size_t unetpp_canny_workspace_bytes(int batch, int h, int w);
+int unetpp_canny_layout(int h, int w, int* tile_rows, int* tile_cols);
+int unetpp_canny_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h, int w, const int32_t* taps, int n_taps,
+                    double low, double high, uint8_t* dev_out, void* dev_workspace, void* stream);
+int unetpp_laplacian_band_u8(unetpp_engine* e, const uint8_t* dev_gray, const uint8_t* dev_band, int batch, int h, int w,
+                             int threshold, uint8_t* dev_out, void* stream);
+int unetpp_components_filter_box(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num,
+                                 const int32_t* dev_stats, int batch, int h, int w, int capacity,
+                                 const unetpp_cc_box_rule* params, uint8_t out_value, uint8_t* dev_out,
+                                 void* dev_workspace, void* stream);
+
 /* ---- binary morphology programs on the device ------------------------------------------------------------------
  * cv2.dilate / cv2.erode / cv2.morphologyEx (OPEN, CLOSE) with a structuring element on class masks, and the short
  * programs the reference builds from them (src/refactor/postprocess.py:79-118 and :144-166,

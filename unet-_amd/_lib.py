@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunetpp_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["unetpp_abi.hip"]
-HEADERS = ["conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "components.h", "morphology.h", os.path.join("..", "..", "include", "unetpp.h")]
+HEADERS = ["conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "components.h", "morphology.h", "edges.h", os.path.join("..", "..", "include", "unetpp.h")]
 
 # every symbol include/unetpp.h declares
 ABI_SYMBOLS = [
@@ -27,6 +27,8 @@ ABI_SYMBOLS = [
     "unetpp_ds_blob_bytes", "unetpp_load_ds_heads", "unetpp_forward_ds",
     "unetpp_components_workspace_bytes", "unetpp_components", "unetpp_components_filter",
     "unetpp_morphology", "unetpp_morphology_layout",
+    "unetpp_gray_u8", "unetpp_gaussian_blur_u8", "unetpp_canny_workspace_bytes", "unetpp_canny_layout", "unetpp_canny_u8",
+    "unetpp_laplacian_band_u8", "unetpp_components_filter_box",
 ]
 
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
@@ -49,6 +51,11 @@ class CcRule(ctypes.Structure):
 
 
 CC_RULES = {"largest": 0, "spatial": 1, "cable_shape": 2}
+
+
+class CcBoxRule(ctypes.Structure):
+    """unetpp_cc_box_rule: the parameters of unetpp_components_filter_box (all doubles)."""
+    _fields_ = [(n, ctypes.c_double) for n in ("min_area", "max_area", "max_aspect", "min_side")]
 
 
 class MorphElement(ctypes.Structure):
@@ -203,6 +210,15 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     lib.unetpp_morphology_layout.argtypes = [ci, ci, ci, ctypes.POINTER(MorphElement), ci, ctypes.POINTER(MorphStep), ci,
                                              ctypes.POINTER(ci), ctypes.POINTER(ci)]
     lib.unetpp_morphology_layout.restype = ci
+    i32p, cd = ctypes.POINTER(ctypes.c_int32), ctypes.c_double
+    lib.unetpp_gray_u8.argtypes = [vp, vp, ci, ci, ci, vp, vp]; lib.unetpp_gray_u8.restype = ci
+    lib.unetpp_gaussian_blur_u8.argtypes = [vp, vp, ci, ci, ci, i32p, ci, vp, vp]; lib.unetpp_gaussian_blur_u8.restype = ci
+    lib.unetpp_canny_workspace_bytes.argtypes = [ci, ci, ci]; lib.unetpp_canny_workspace_bytes.restype = cs
+    lib.unetpp_canny_layout.argtypes = [ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]; lib.unetpp_canny_layout.restype = ci
+    lib.unetpp_canny_u8.argtypes = [vp, vp, ci, ci, ci, i32p, ci, cd, cd, vp, vp, vp]; lib.unetpp_canny_u8.restype = ci
+    lib.unetpp_laplacian_band_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, vp]; lib.unetpp_laplacian_band_u8.restype = ci
+    lib.unetpp_components_filter_box.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ctypes.POINTER(CcBoxRule), ctypes.c_uint8, vp, vp, vp]
+    lib.unetpp_components_filter_box.restype = ci
     ver = lib.unetpp_version().decode()
     if ver.endswith(" +wsdbg") and os.environ.get("UNETPP_ALLOW_DBG_LIB"):
         ver = ver[:-len(" +wsdbg")]            # measurement build with phase ablations (scripts/ws_ablate.sh)

@@ -27,11 +27,13 @@ constexpr int CC_CHUNK = CC_THREADS * CC_PX; // raster chunk of the per-pixel ke
 constexpr int CC_TAB = 512;                  // slots of the per-chunk stats table
 constexpr int CC_PROBES = 8;
 
-enum { CC_RULE_LARGEST = 0, CC_RULE_SPATIAL = 1, CC_RULE_CABLE_SHAPE = 2 };
+enum { CC_RULE_LARGEST = 0, CC_RULE_SPATIAL = 1, CC_RULE_CABLE_SHAPE = 2, CC_RULE_BOX = 3 };
 
-struct CcRule {                              // unetpp_cc_rule, as the kernels take it
+struct CcRule {                              // unetpp_cc_rule / unetpp_cc_box_rule, as the kernels take them
   double min_area, min_width, max_width, min_height_ratio, min_aspect, max_center_offset, roi_width;
+  double max_area, max_aspect, min_side;     // CC_RULE_BOX
 };
+__host__ __device__ __forceinline__ bool cc_keeps_all(int rule) { return rule == CC_RULE_SPATIAL || rule == CC_RULE_BOX; }
 
 __device__ __forceinline__ bool cc_is_fg(unsigned v, int match_class) { return match_class < 0 ? v != 0 : (int)v == match_class; }
 
@@ -395,7 +397,8 @@ __global__ void __launch_bounds__(CC_THREADS) cc_finish_stats_kernel(int* __rest
 }
 
 // ---- filters --------------------------------------------------------------------------------------------------------
-// cc_select_kernel, grid (B): the rule's predicate per component in fp64 and, for the rules that keep one component,
+// cc_select_kernel, grid (B): the rule's predicate per component in fp64 (SPATIAL and BOX keep every component that
+// passes) and, for the rules that keep one component,
 // the first of the best (lowest label among equal scores) -> keep[B][K].  A frame with more components than the
 // stats hold (num > K) keeps nothing.  The arithmetic restates the reference line by line; no contraction, so that a
 // product and a sum stay two roundings as in NumPy.
@@ -407,6 +410,11 @@ __device__ __forceinline__ bool cc_candidate(const int* st, const unsigned long 
   if (rule == CC_RULE_SPATIAL) {
     *score = 0.0;
     return area > r.min_area && r.min_width <= w && w <= r.max_width && h >= (double)H * r.min_height_ratio;
+  }
+  if (rule == CC_RULE_BOX) {                                 // the loop of detect_burrs_on_cable, infer_two_stage_burr.py:103-117
+    *score = 0.0;
+    const double aspect = fmax(w, h) / (fmin(w, h) + 1e-6);
+    return r.min_area <= area && area <= r.max_area && aspect < r.max_aspect && w > r.min_side && h > r.min_side;
   }
   if (area < r.min_area) return false;
   const double aspect = fmax(w, h) / (fmin(w, h) + 1e-6);
@@ -431,7 +439,7 @@ __global__ void __launch_bounds__(CC_THREADS) cc_select_kernel(const int* __rest
   uint8_t* kp = keep + (size_t)b * K;
   const int n = num[b] <= K ? num[b] : 0;
   int best = -1;
-  if (rule != CC_RULE_SPATIAL) {
+  if (!cc_keeps_all(rule)) {
     double bs = 0.0;
     for (int l = 1 + t; l < n; l += CC_THREADS) {            // ascending labels: '>' keeps the first of equal scores
       double s;
@@ -452,7 +460,7 @@ __global__ void __launch_bounds__(CC_THREADS) cc_select_kernel(const int* __rest
   for (int l = t; l < K; l += CC_THREADS) {
     bool k = false;
     double s;
-    if (l >= 1 && l < n) k = rule == CC_RULE_SPATIAL ? cc_candidate(st, sm, l, rule, r, H, &s) : l == best;
+    if (l >= 1 && l < n) k = cc_keeps_all(rule) ? cc_candidate(st, sm, l, rule, r, H, &s) : l == best;
     kp[l] = k ? 1 : 0;
   }
 }

@@ -33,6 +33,7 @@
 #include "conv3x3_mfma.h"
 #include "conv3x3_ws.h"
 #include "convt2x2_mfma.h"
+#include "edges.h"
 #include "morphology.h"
 #include "tapmm_ws.h"
 
@@ -1398,6 +1399,172 @@ int unetpp_components_filter(unetpp_engine* e, const int32_t* dev_labels, const 
   const int vec = hw % 16 == 0 && (uintptr_t)dev_labels % 16 == 0 && (uintptr_t)dev_out % 16 == 0;
   hipLaunchKernelGGL(cc_apply_kernel, dim3((unsigned)ws.nchunk, (unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_labels,
                      (const uint8_t*)keep, hw, capacity, vec, (unsigned)out_value, dev_out);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_components_filter_box(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num, const int32_t* dev_stats,
+                                 int batch, int h, int w, int capacity, const unetpp_cc_box_rule* params, uint8_t out_value,
+                                 uint8_t* dev_out, void* dev_workspace, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_labels || !dev_num || !dev_stats || !params || !dev_out || !dev_workspace) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (capacity < 2) return fail(e, UNETPP_E_INVALID, "capacity %d: at least 2 rows (background + one component)", capacity);
+  if (std::isnan(params->min_area) || std::isnan(params->max_area) || std::isnan(params->max_aspect) || std::isnan(params->min_side))
+    return fail(e, UNETPP_E_INVALID, "box rule: NaN parameter");
+  CcWorkspace ws;
+  if (!cc_layout(batch, h, w, capacity, &ws)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  uint8_t* keep = (uint8_t*)dev_workspace + ws.keep;
+  CcRule r{};
+  r.min_area = params->min_area; r.max_area = params->max_area; r.max_aspect = params->max_aspect; r.min_side = params->min_side;
+  hipLaunchKernelGGL(cc_select_kernel, dim3((unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_num, (const int*)dev_stats,
+                     (const unsigned long long*)nullptr, h, capacity, (int)CC_RULE_BOX, r, keep);      // the box rule reads no sums
+  const int vec = hw % 16 == 0 && (uintptr_t)dev_labels % 16 == 0 && (uintptr_t)dev_out % 16 == 0;
+  hipLaunchKernelGGL(cc_apply_kernel, dim3((unsigned)ws.nchunk, (unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_labels,
+                     (const uint8_t*)keep, hw, capacity, vec, (unsigned)out_value, dev_out);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+// ---- grey-level front end of the burr detection (edges.h) -----------------------------------------------------------
+}  // extern "C"
+namespace {
+struct CannyWorkspace {
+  size_t parent = 0, chunks = 0, map = 0, flags = 0, total = 0;   // byte offsets
+  int nchunk = 0;
+};
+bool edge_shape_ok(int batch, int h, int w) {
+  return batch >= 1 && batch <= 65535 && h >= 8 && w >= 8 && h <= 65535 && w <= 65535 && (size_t)h * w <= (1u << 30);
+}
+bool canny_layout(int batch, int h, int w, CannyWorkspace* ws) {
+  if (!edge_shape_ok(batch, h, w)) return false;
+  const size_t hw = (size_t)h * w;
+  ws->nchunk = (int)((hw + CC_CHUNK - 1) / CC_CHUNK);
+  ws->parent = 0;
+  ws->chunks = align_up(hw * batch * sizeof(int), 256);
+  ws->map = ws->chunks + align_up((size_t)ws->nchunk * batch * sizeof(int), 256);
+  ws->flags = ws->map + align_up(hw * batch, 256);
+  ws->total = ws->flags + align_up(hw * batch, 256);
+  return true;
+}
+// taps == NULL: no blur (the identity tap).  Otherwise n_taps odd, <= 7, every tap in [0,256], sum 256, symmetric or not.
+int edge_taps(unetpp_engine* e, const int32_t* taps, int n_taps, EdgeTaps* out) {
+  std::memset(out, 0, sizeof *out);
+  if (!taps) { out->n = 1; out->t[0] = 256; return UNETPP_OK; }
+  if (n_taps < 1 || n_taps % 2 == 0) return fail(e, UNETPP_E_INVALID, "n_taps %d: must be odd and positive", n_taps);
+  if (n_taps > ED_MAX_TAPS) return fail(e, UNETPP_E_UNSUPPORTED, "n_taps %d: at most %d", n_taps, ED_MAX_TAPS);
+  int sum = 0;
+  for (int k = 0; k < n_taps; ++k) {
+    if (taps[k] < 0 || taps[k] > 256) return fail(e, UNETPP_E_INVALID, "tap %d = %d not in [0,256]", k, (int)taps[k]);
+    out->t[k] = taps[k];
+    sum += taps[k];
+  }
+  if (sum != 256) return fail(e, UNETPP_E_INVALID, "taps sum to %d, not 256", sum);
+  out->n = n_taps;
+  return UNETPP_OK;
+}
+}  // namespace
+extern "C" {
+
+int unetpp_gray_u8(unetpp_engine* e, const uint8_t* dev_bgr, int batch, int h, int w, uint8_t* dev_gray, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_bgr || !dev_gray) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (batch < 1 || batch > 65535 || h < 1 || w < 1 || (size_t)h * w > (1u << 30)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  ENTER_DEVICE(e);
+  const int hw = h * w;
+  hipLaunchKernelGGL(gray_kernel, dim3((unsigned)((hw + ED_THREADS - 1) / ED_THREADS), (unsigned)batch), dim3(ED_THREADS), 0, (hipStream_t)stream,
+                     dev_bgr, hw, dev_gray);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_canny_layout(int h, int w, int* tile_rows, int* tile_cols) {
+  if (!tile_rows || !tile_cols) return fail(nullptr, UNETPP_E_INVALID, "null argument");
+  if (!edge_shape_ok(1, h, w)) return fail(nullptr, UNETPP_E_UNSUPPORTED, "bad shape %dx%d", h, w);
+  *tile_rows = ED_TH;
+  *tile_cols = ED_TW;
+  return UNETPP_OK;
+}
+
+size_t unetpp_canny_workspace_bytes(int batch, int h, int w) {
+  CannyWorkspace ws;
+  return canny_layout(batch, h, w, &ws) ? ws.total : 0;
+}
+
+int unetpp_gaussian_blur_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h, int w, const int32_t* taps, int n_taps,
+                            uint8_t* dev_out, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_gray || !dev_out || !taps) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (batch < 1 || h < 1 || w < 1) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if (!edge_shape_ok(batch, h, w)) return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside 8 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  EdgeTaps T;
+  const int rc = edge_taps(e, taps, n_taps, &T);
+  if (rc != UNETPP_OK) return rc;
+  const size_t n = (size_t)batch * h * w;
+  if (dev_gray < dev_out + n && dev_out < dev_gray + n) return fail(e, UNETPP_E_INVALID, "dev_out aliases dev_gray: workgroups read halo pixels their neighbours write");
+  ENTER_DEVICE(e);
+  const dim3 grid((unsigned)((w + ED_TW - 1) / ED_TW), (unsigned)((h + ED_TH - 1) / ED_TH), (unsigned)batch);
+  const int vec = w % 16 == 0 && (uintptr_t)dev_out % 16 == 0;
+  hipLaunchKernelGGL(edge_map_kernel<true>, grid, dim3(ED_THREADS), 0, (hipStream_t)stream, dev_gray, h, w, T, 0, 0, vec, dev_out);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_canny_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h, int w, const int32_t* taps, int n_taps, double low,
+                    double high, uint8_t* dev_out, void* dev_workspace, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_gray || !dev_out || !dev_workspace) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (batch < 1 || h < 1 || w < 1) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  CannyWorkspace ws;
+  if (!canny_layout(batch, h, w, &ws)) return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside 8 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  if (!(low >= 0) || !(high >= 0)) return fail(e, UNETPP_E_INVALID, "thresholds must be non-negative numbers");
+  if ((uintptr_t)dev_workspace % 16) return fail(e, UNETPP_E_INVALID, "dev_workspace must be 16-byte aligned");
+  EdgeTaps T;
+  const int rc = edge_taps(e, taps, n_taps, &T);
+  if (rc != UNETPP_OK) return rc;
+  if (low > high) std::swap(low, high);                      // cv2.Canny does the same
+  const int ilow = (int)std::floor(std::min(low, 1e6)), ihigh = (int)std::floor(std::min(high, 1e6));
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  int* parent = (int*)((char*)dev_workspace + ws.parent);
+  int* chunks = (int*)((char*)dev_workspace + ws.chunks);
+  uint8_t* map = (uint8_t*)dev_workspace + ws.map;
+  uint8_t* flags = (uint8_t*)dev_workspace + ws.flags;
+  const int ntx = (w + ED_TW - 1) / ED_TW, nty = (h + ED_TH - 1) / ED_TH;
+  const dim3 blk(ED_THREADS), tiles((unsigned)ntx, (unsigned)nty, (unsigned)batch), per_px((unsigned)ws.nchunk, (unsigned)batch);
+  HIP_TRY(e, hipMemsetAsync(flags, 0, (size_t)batch * hw, s));
+  const int row_vec = w % 16 == 0;                           // map starts on a 256-byte boundary of the workspace
+  hipLaunchKernelGGL(edge_map_kernel<false>, tiles, blk, 0, s, dev_gray, h, w, T, ilow, ihigh, row_vec, map);
+  hipLaunchKernelGGL(cc_tile_kernel, tiles, blk, 0, s, (const uint8_t*)map, h, w, -1, 1, row_vec, parent);
+  const long long items = (long long)(nty - 1) * w + 2LL * (ntx - 1) * h;
+  if (items > 0)
+    hipLaunchKernelGGL(cc_merge_kernel, dim3((unsigned)((items + CC_THREADS - 1) / CC_THREADS), (unsigned)batch), blk, 0, s, parent, h, w, 1,
+                       nty - 1, ntx - 1);
+  const int par_vec = hw % 4 == 0;
+  hipLaunchKernelGGL(cc_compress_kernel, per_px, blk, 0, s, parent, hw, par_vec, chunks);
+  hipLaunchKernelGGL(edge_seed_kernel, per_px, blk, 0, s, (const uint8_t*)map, (const int*)parent, hw, (int)(hw % 16 == 0), flags);
+  hipLaunchKernelGGL(edge_apply_kernel, per_px, blk, 0, s, (const int*)parent, (const uint8_t*)flags, hw, par_vec,
+                     (int)(hw % 16 == 0 && (uintptr_t)dev_out % 16 == 0), dev_out);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_laplacian_band_u8(unetpp_engine* e, const uint8_t* dev_gray, const uint8_t* dev_band, int batch, int h, int w, int threshold,
+                             uint8_t* dev_out, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_gray || !dev_band || !dev_out) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (batch < 1 || batch > 65535 || h < 2 || w < 2 || h > 65535 || w > 65535 || (size_t)h * w > (1u << 30))
+    return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  const size_t n = (size_t)batch * h * w;
+  if (dev_gray < dev_out + n && dev_out < dev_gray + n) return fail(e, UNETPP_E_INVALID, "dev_out aliases dev_gray: threads read neighbours that others write");
+  ENTER_DEVICE(e);
+  const long long items = (long long)h * ((w + CC_PX - 1) / CC_PX);
+  const int vec = w % 16 == 0 && (uintptr_t)dev_band % 16 == 0 && (uintptr_t)dev_out % 16 == 0;
+  hipLaunchKernelGGL(laplacian_band_kernel, dim3((unsigned)((items + ED_THREADS - 1) / ED_THREADS), (unsigned)batch), dim3(ED_THREADS), 0,
+                     (hipStream_t)stream, dev_gray, dev_band, h, w, threshold, vec, dev_out);
   HIP_TRY(e, hipGetLastError());
   return UNETPP_OK;
 }

@@ -584,6 +584,206 @@ class NestedUNet:
                                        f"max_components = {k}: raise max_components")
         return num_holes, hole_area
 
+    # ------------------------------------------------------------------ stage-2 burr detection
+    def _edge_input(self, img, what="gray", channels=None):
+        """A contiguous uint8 CUDA image batch on the engine's device, with the engine made ready."""
+        import torch
+        dims = 3 if channels is None else 4
+        if not (isinstance(img, torch.Tensor) and img.is_cuda and img.dtype == torch.uint8 and img.dim() == dims and
+                (channels is None or img.shape[-1] == channels)):
+            shape = "[B,H,W]" if channels is None else f"[B,H,W,{channels}]"
+            raise RuntimeError(f"{what} must be a uint8 CUDA tensor {shape}")
+        if self._device_index is None:
+            self.to(img.device)
+        if img.device.index != self._device_index:
+            raise RuntimeError(f"{what} on {img.device}, engine on cuda:{self._device_index}")
+        self._ensure_engine(1, self._SIZE_MULTIPLE, self._SIZE_MULTIPLE)
+        return img.contiguous()
+
+    def _raise(self, rc):
+        raise (ValueError if rc == -2 else RuntimeError)(self._err(rc))
+
+    @staticmethod
+    def _check_edge_shape(shape):
+        from . import edges as ed
+        h, w = int(shape[-2]), int(shape[-1])
+        if h < ed.MIN_SIDE or w < ed.MIN_SIDE or h > 65535 or w > 65535 or h * w > 1 << 30:
+            raise ValueError(f"image is {h}x{w}: the blur and Canny need {ed.MIN_SIDE} <= H, W <= 65535 and H * W <= 2^30")
+
+    @staticmethod
+    def _c_taps(taps):
+        return None if taps is None else taps.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+    def bgr_to_gray(self, frames):
+        """cv2.cvtColor(frame, cv2.COLOR_BGR2GRAY) for uint8 CUDA frames [B,H,W,3] -> [B,H,W] with OpenCV 4's 15-bit
+        constants (unet_amd/edges.py bgr_to_gray_np)."""
+        import torch
+        frames = self._edge_input(frames, "frames", 3)
+        b, h, w, _ = frames.shape
+        out = torch.empty((b, h, w), dtype=torch.uint8, device=frames.device)
+        rc = _lib.load().unetpp_gray_u8(self._handle, ctypes.c_void_p(frames.data_ptr()), b, h, w, ctypes.c_void_p(out.data_ptr()),
+                                        ctypes.c_void_p(torch.cuda.current_stream(frames.device).cuda_stream))
+        if rc != 0:
+            self._raise(rc)
+        return out
+
+    def gaussian_blur(self, gray, ksize: int = 5, sigma: float = 1.0, taps=None):
+        """cv2.GaussianBlur(gray, (ksize, ksize), sigma) for uint8 CUDA images [B,H,W] in 8.8 fixed point with
+        BORDER_REFLECT_101 (unet_amd/edges.py gaussian_blur_np); `taps` (odd, at most 7 integers summing to 256)
+        replaces the kernel gaussian_taps(ksize, sigma) restates, e.g. by cv2's own.  8 <= H, W."""
+        import torch
+        from . import edges as ed
+        t = ed.resolve_taps(ksize, sigma, taps)
+        if t is None:
+            raise ValueError("gaussian_blur needs a kernel: ksize >= 1 or taps")
+        if hasattr(gray, "shape") and len(gray.shape) == 3:
+            self._check_edge_shape(gray.shape)
+        gray = self._edge_input(gray)
+        b, h, w = gray.shape
+        out = torch.empty_like(gray)
+        rc = _lib.load().unetpp_gaussian_blur_u8(self._handle, ctypes.c_void_p(gray.data_ptr()), b, h, w, self._c_taps(t), len(t),
+                                                 ctypes.c_void_p(out.data_ptr()),
+                                                 ctypes.c_void_p(torch.cuda.current_stream(gray.device).cuda_stream))
+        if rc != 0:
+            self._raise(rc)
+        return out
+
+    def canny(self, gray, low, high, blur=None):
+        """cv2.Canny(gray, low, high) (aperture 3, L2gradient off) for uint8 CUDA images [B,H,W]: uint8, 0 or 255
+        (unet_amd/edges.py canny_np).  blur: None, or the Gaussian blur to run first inside the same kernel, as
+        (ksize, sigma) or as an integer tap array (see gaussian_blur).  The hysteresis runs on the component launches
+        with a flag per root pixel: exact, the same bits from run to run, no limit on the number of fragments."""
+        import torch
+        from . import edges as ed
+        low, high = float(low), float(high)
+        if not (low >= 0 and high >= 0):
+            raise ValueError(f"thresholds must be non-negative, got {low!r}, {high!r}")
+        if blur is None:
+            t = None
+        elif isinstance(blur, tuple) and len(blur) == 2 and not isinstance(blur[0], np.ndarray):
+            t = ed.resolve_taps(blur[0], blur[1], None)
+        else:
+            t = ed.check_taps(blur)
+        if hasattr(gray, "shape") and len(gray.shape) == 3:
+            self._check_edge_shape(gray.shape)
+        gray = self._edge_input(gray)
+        b, h, w = gray.shape
+        lib = _lib.load()
+        key = ("canny", b, h, w)
+        ws = self._cc_workspaces.get(key)
+        if ws is None or ws.device != gray.device:
+            nbytes = int(lib.unetpp_canny_workspace_bytes(b, h, w))
+            if nbytes == 0:
+                raise RuntimeError(f"canny: unsupported shape {tuple(gray.shape)}")
+            ws = self._cc_workspaces[key] = torch.empty(nbytes, dtype=torch.uint8, device=gray.device)
+        out = torch.empty_like(gray)
+        rc = lib.unetpp_canny_u8(self._handle, ctypes.c_void_p(gray.data_ptr()), b, h, w, self._c_taps(t), 0 if t is None else len(t),
+                                 low, high, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                 ctypes.c_void_p(torch.cuda.current_stream(gray.device).cuda_stream))
+        if rc != 0:
+            self._raise(rc)
+        return out
+
+    @staticmethod
+    def _check_box(min_area, max_area, max_aspect, min_side):
+        vals = [float(min_area), float(max_area), float(max_aspect), float(min_side)]
+        if any(v != v for v in vals):
+            raise ValueError("min_area, max_area, max_aspect and min_side must be numbers, got a NaN")
+        return vals
+
+    def filter_components_box(self, mask, match_class: int = -1, min_area=30, max_area=800, max_aspect=float("inf"), min_side=0, *,
+                              connectivity: int = 8, max_components: int = 8192, out_value: int = 1, check: bool = True):
+        """The component loop of detect_burrs_on_cable (infer_two_stage_burr.py:100-117) on a uint8 CUDA mask [B,H,W]:
+        uint8 [B,H,W], out_value on EVERY component of (mask == match_class) with min_area <= area <= max_area,
+        max(w,h) / (min(w,h) + 1e-6) < max_aspect (fp64) and w > min_side and h > min_side (unet_amd/edges.py keep_box).
+        The defaults max_aspect=inf, min_side=0 leave the area clause of get_burr_mask_rulebased
+        (src/refactor/burr_detector.py:53-64).  max_components and check as for filter_components."""
+        box = self._check_box(min_area, max_area, max_aspect, min_side)
+        out_value = self._check_out_value(out_value)
+        import torch
+        labels, num, stats, _, ws, stream = self._components(mask, match_class, connectivity, max_components, True)
+        b, h, w = labels.shape
+        k = int(max_components)
+        params = _lib.CcBoxRule(*box)
+        out = torch.empty((b, h, w), dtype=torch.uint8, device=labels.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        rc = _lib.load().unetpp_components_filter_box(self._handle, p(labels), p(num), p(stats), b, h, w, k, ctypes.byref(params),
+                                                      out_value, p(out), p(ws), stream)
+        if rc != 0:
+            self._raise(rc)
+        if check:
+            for i, v in enumerate(num.cpu().tolist()):
+                if v > k:
+                    raise RuntimeError(f"filter_components: frame {i} has num = {v} labels (background included), more than "
+                                       f"max_components = {k}: raise max_components")
+        return out
+
+    def detect_burrs(self, gray, mask_cable, match_class: int = -1, *, min_area=30, max_area=800, band_ksize: int = 8,
+                     blur_ksize: int = 5, blur_sigma: float = 1.0, taps=None, canny_low=50, canny_high=150, close_ksize: int = 3,
+                     open_ksize: int = 2, max_aspect=5.0, min_side=3, out_value: int = 1, max_components: int = 8192,
+                     check: bool = True):
+        """detect_burrs_on_cable(frame_gray, mask_cable, config) (infer_two_stage_burr.py:50-119; the defaults are the
+        function's constants and its default config) for uint8 CUDA grey frames and cable masks [B,H,W], nothing leaving
+        the device: canny with the blur fused -> ONE morphology launch ((dilate(cable, E8) & ~cable) & edges, close E3,
+        open E2: unet_amd/edges.py program_burr) -> components -> the box rule.  Foreground of mask_cable is
+        (mask == match_class), != 0 for match_class < 0.  An empty cable gives an empty band and so an empty result:
+        the reference's two early returns need no read-back.  A sensitivity preset of the reference is
+        detect_burrs(gray, cable, min_area=p["min_area"], max_area=p["max_area"]) with p = edges.PRESETS[name].
+        uint8 [B,H,W], out_value (1 in the reference) on the kept components."""
+        from . import edges as ed
+        self._check_box(min_area, max_area, max_aspect, min_side)
+        self._check_out_value(out_value)
+        t = ed.resolve_taps(blur_ksize, blur_sigma, taps)
+        ed.program_burr(band_ksize, close_ksize, open_ksize)
+        if hasattr(gray, "shape") and hasattr(mask_cable, "shape") and tuple(gray.shape) != tuple(mask_cable.shape):
+            raise RuntimeError(f"gray {tuple(gray.shape)} and mask_cable {tuple(mask_cable.shape)} differ in shape")
+        edges = self.canny(gray, canny_low, canny_high, blur=t)
+        return self.burrs_from_edges(edges, mask_cable, match_class, min_area=min_area, max_area=max_area, band_ksize=band_ksize,
+                                     close_ksize=close_ksize, open_ksize=open_ksize, max_aspect=max_aspect, min_side=min_side,
+                                     out_value=out_value, max_components=max_components, check=check)
+
+    def burrs_from_edges(self, edges, mask_cable, match_class: int = -1, *, min_area=30, max_area=800, band_ksize: int = 8,
+                         close_ksize: int = 3, open_ksize: int = 2, max_aspect=5.0, min_side=3, out_value: int = 1,
+                         max_components: int = 8192, check: bool = True):
+        """detect_burrs_on_cable after its cv2.Canny call (infer_two_stage_burr.py:78-117 without :85-86) for an edge
+        image `edges` (uint8 CUDA [B,H,W], non-zero = edge) from any source: one morphology launch (program_burr), the
+        components, the box rule.  detect_burrs is canny() followed by this."""
+        from . import edges as ed
+        box = self._check_box(min_area, max_area, max_aspect, min_side)
+        out_value = self._check_out_value(out_value)
+        program = self._morph_named("burr", (int(band_ksize), int(close_ksize), int(open_ksize)), ed.program_burr)
+        cand = self._morph_launch(program, edges, -1, mask_cable, match_class, 1)
+        return self.filter_components_box(cand, 1, *box, max_components=max_components, out_value=out_value, check=check)
+
+    def burr_mask_rulebased(self, gray, mask_cable, match_class: int = -1, *, band_out: int = 10, laplacian_threshold=30, min_area=20,
+                            max_area=500, out_value: int = 255, max_components: int = 8192, check: bool = True):
+        """get_burr_mask_rulebased(frame_gray, mask_cable, BurrConfig(...)) (src/refactor/burr_detector.py:11-66, defaults
+        of BurrConfig) on the device: boundary_band -> |Laplacian| & 255 above the threshold inside the band (the
+        reference's uint8 cast wraps above 255 and so does this) -> components -> min_area <= area <= max_area.
+        uint8 [B,H,W], out_value (255 in the reference) on the kept components."""
+        import math
+        import torch
+        from . import morphology as mo
+        box = self._check_box(min_area, max_area, float("inf"), 0)
+        out_value = self._check_out_value(out_value)
+        thr = float(laplacian_threshold)
+        if thr != thr:
+            raise ValueError("laplacian_threshold must be a number")
+        thr = int(math.floor(min(max(thr, -1.0), 256.0)))
+        program = self._morph_named("band", (int(band_out),), mo.program_band)
+        if hasattr(gray, "shape") and hasattr(mask_cable, "shape") and tuple(gray.shape) != tuple(mask_cable.shape):
+            raise RuntimeError(f"gray {tuple(gray.shape)} and mask_cable {tuple(mask_cable.shape)} differ in shape")
+        gray = self._edge_input(gray)
+        band = self._morph_launch(program, mask_cable, match_class, None, -1, 1)
+        b, h, w = gray.shape
+        hot = torch.empty_like(gray)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        rc = _lib.load().unetpp_laplacian_band_u8(self._handle, p(gray), p(band), b, h, w, thr, p(hot),
+                                                  ctypes.c_void_p(torch.cuda.current_stream(gray.device).cuda_stream))
+        if rc != 0:
+            self._raise(rc)
+        return self.filter_components_box(hot, -1, *box, max_components=max_components, out_value=out_value, check=check)
+
     def resize_frames(self, frames, size_hw):
         """cv2.resize(frame, (W, H), interpolation=cv2.INTER_LINEAR) for uint8 CUDA frames [B,h,w,C] -> [B,H,W,C]
         (preprocess_image, infer_two_stage_burr.py:124).  Chain with segment(): the BGR->RGB swap and /255 run

@@ -454,6 +454,37 @@ long long unetpp_debug_read(unetpp_engine* e, const char* name, float* host_out,
  * unetpp_debug_read("x0_4") works. */
 int unetpp_debug_keep_intermediates(unetpp_engine* e, int on);
 
+/* ---- the multi-scale and the DoG burr detectors, has_burr ---------------------------------------------------------
+ * The grey-level steps of detect_burrs_enhanced (infer_enhanced_burr.py:87-106), get_burr_mask_dog
+ * (src/refactor/burr_detector.py:93-103) and has_burr (:121-133); their mask-side steps are unetpp_morphology,
+ * unetpp_components and unetpp_components_filter_box.  All integer, exact; images uint8 [B,h,w] on the device with the
+ * shape limits and status codes of unetpp_canny_u8 (8 <= h, w <= 65535, h * w <= 2^30: UNETPP_E_UNSUPPORTED beyond).
+ * Asynchronous on `stream`; nothing is allocated.
+ *
+ * unetpp_edges_union_u8: dev_out = dev_canny | sobel | laplacian, bytewise, where
+ *   sobel     = 255 where uint8(sqrt(s) / sqrt(max s over the frame) * 255) > sobel_threshold (float64, truncating),
+ *               s = dx^2 + dy^2 of cv2.Sobel(ksize = 3) on the raw grey image with BORDER_REFLECT_101.  A constant frame
+ *               (max s = 0; 0 / 0 in the reference) has no Sobel edges.
+ *   laplacian = 255 where (|cv2.Laplacian(ksize = 1)| & 255) > laplacian_threshold (the reference's uint8 cast wraps).
+ *   dev_workspace: unetpp_edges_union_workspace_bytes(batch) bytes (0 for a bad batch), 16-byte aligned; it holds the
+ *   per-frame maximum between the two launches.  dev_out may be dev_canny itself (in place), not dev_gray.
+ *   Thresholds are those of cv2.threshold on uint8: below 0 everything passes, from 255 on nothing.
+ *
+ * unetpp_dog_band_u8: dev_out = 255 where dev_band != 0 and cv2.subtract(blur1, blur2) > threshold, else 0; blur1 and
+ *   blur2 are unetpp_gaussian_blur_u8 with taps1[n1] and taps2[n2] (host memory; odd, at most 7, in [0,256], sum 256).
+ *   The subtraction saturates at 0.  dev_out may alias neither input.
+ *
+ * unetpp_count_nonzero_u8: dev_counts uint32 [B] = number of non-zero bytes of each frame (any h, w >= 1). */
+size_t unetpp_edges_union_workspace_bytes(int batch);
+int unetpp_edges_union_u8(unetpp_engine* e, const uint8_t* dev_gray, const uint8_t* dev_canny, int batch, int h, int w,
+                          int sobel_threshold, int laplacian_threshold, void* dev_workspace, uint8_t* dev_out,
+                          void* stream);
+int unetpp_dog_band_u8(unetpp_engine* e, const uint8_t* dev_gray, const uint8_t* dev_band, int batch, int h, int w,
+                       const int32_t* taps1, int n1, const int32_t* taps2, int n2, int threshold, uint8_t* dev_out,
+                       void* stream);
+int unetpp_count_nonzero_u8(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, uint32_t* dev_counts,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

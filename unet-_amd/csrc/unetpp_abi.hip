@@ -34,6 +34,7 @@
 #include "conv3x3_ws.h"
 #include "convt2x2_mfma.h"
 #include "edges.h"
+#include "edges_multi.h"
 #include "morphology.h"
 #include "tapmm_ws.h"
 
@@ -1565,6 +1566,77 @@ int unetpp_laplacian_band_u8(unetpp_engine* e, const uint8_t* dev_gray, const ui
   const int vec = w % 16 == 0 && (uintptr_t)dev_band % 16 == 0 && (uintptr_t)dev_out % 16 == 0;
   hipLaunchKernelGGL(laplacian_band_kernel, dim3((unsigned)((items + ED_THREADS - 1) / ED_THREADS), (unsigned)batch), dim3(ED_THREADS), 0,
                      (hipStream_t)stream, dev_gray, dev_band, h, w, threshold, vec, dev_out);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+// ---- the multi-scale and the DoG burr detectors, has_burr (edges_multi.h) ---------------------------------------
+size_t unetpp_edges_union_workspace_bytes(int batch) {
+  return batch >= 1 && batch <= 65535 ? align_up((size_t)batch * sizeof(uint32_t), 256) : 0;
+}
+
+int unetpp_edges_union_u8(unetpp_engine* e, const uint8_t* dev_gray, const uint8_t* dev_canny, int batch, int h, int w,
+                          int sobel_threshold, int laplacian_threshold, void* dev_workspace, uint8_t* dev_out, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_gray || !dev_canny || !dev_workspace || !dev_out) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (batch < 1 || h < 1 || w < 1) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if (!edge_shape_ok(batch, h, w)) return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside 8 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  if ((uintptr_t)dev_workspace % 16) return fail(e, UNETPP_E_INVALID, "dev_workspace must be 16-byte aligned");
+  const size_t n = (size_t)batch * h * w;
+  if (dev_gray < dev_out + n && dev_out < dev_gray + n) return fail(e, UNETPP_E_INVALID, "dev_out aliases dev_gray: workgroups read halo pixels their neighbours write");
+  if (dev_out != dev_canny && dev_canny < dev_out + n && dev_out < dev_canny + n)
+    return fail(e, UNETPP_E_INVALID, "dev_out overlaps dev_canny: in place means the same pointer");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  unsigned* smax = (unsigned*)dev_workspace;
+  const dim3 blk(ED_THREADS), tiles((unsigned)((w + ED_TW - 1) / ED_TW), (unsigned)((h + ED_TH - 1) / ED_TH), (unsigned)batch);
+  const int sthr = std::min(std::max(sobel_threshold, -1), 255), lthr = std::min(std::max(laplacian_threshold, -1), 255);
+  HIP_TRY(e, hipMemsetAsync(smax, 0, (size_t)batch * sizeof(unsigned), s));
+  hipLaunchKernelGGL(sobel_max_kernel, tiles, blk, 0, s, dev_gray, h, w, smax);
+  const int vec = w % 16 == 0 && (uintptr_t)dev_canny % 16 == 0 && (uintptr_t)dev_out % 16 == 0;
+  hipLaunchKernelGGL(edge_union_kernel, tiles, blk, 0, s, dev_gray, dev_canny, h, w, (const unsigned*)smax, sthr, lthr, vec, dev_out);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_dog_band_u8(unetpp_engine* e, const uint8_t* dev_gray, const uint8_t* dev_band, int batch, int h, int w, const int32_t* taps1,
+                       int n1, const int32_t* taps2, int n2, int threshold, uint8_t* dev_out, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_gray || !dev_band || !dev_out || !taps1 || !taps2) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (batch < 1 || h < 1 || w < 1) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if (!edge_shape_ok(batch, h, w)) return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside 8 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  EdgeTaps T1, T2;
+  int rc = edge_taps(e, taps1, n1, &T1);
+  if (rc != UNETPP_OK) return rc;
+  rc = edge_taps(e, taps2, n2, &T2);
+  if (rc != UNETPP_OK) return rc;
+  const size_t n = (size_t)batch * h * w;
+  if ((dev_gray < dev_out + n && dev_out < dev_gray + n) || (dev_band < dev_out + n && dev_out < dev_band + n))
+    return fail(e, UNETPP_E_INVALID, "dev_out aliases an input: workgroups read halo pixels their neighbours write");
+  DogTaps D;
+  std::memset(&D, 0, sizeof D);
+  for (int k = 0; k < T1.n; ++k) D.t1[ED_MAX_R - T1.n / 2 + k] = T1.t[k];
+  for (int k = 0; k < T2.n; ++k) D.t2[ED_MAX_R - T2.n / 2 + k] = T2.t[k];
+  ENTER_DEVICE(e);
+  const dim3 tiles((unsigned)((w + ED_TW - 1) / ED_TW), (unsigned)((h + ED_TH - 1) / ED_TH), (unsigned)batch);
+  const int vec = w % 16 == 0 && (uintptr_t)dev_band % 16 == 0 && (uintptr_t)dev_out % 16 == 0;
+  hipLaunchKernelGGL(dog_band_kernel, tiles, dim3(ED_THREADS), 0, (hipStream_t)stream, dev_gray, dev_band, h, w, D,
+                     std::min(std::max(threshold, -1), 255), vec, dev_out);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_count_nonzero_u8(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, uint32_t* dev_counts, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_mask || !dev_counts) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (batch < 1 || batch > 65535 || h < 1 || w < 1 || h > 65535 || w > 65535 || (size_t)h * w > (1u << 30))
+    return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  HIP_TRY(e, hipMemsetAsync(dev_counts, 0, (size_t)batch * sizeof(uint32_t), s));
+  hipLaunchKernelGGL(count_nonzero_kernel, dim3((unsigned)((hw + CC_CHUNK - 1) / CC_CHUNK), (unsigned)batch), dim3(ED_THREADS), 0, s, dev_mask, hw,
+                     (int)(hw % 16 == 0 && (uintptr_t)dev_mask % 16 == 0), (unsigned*)dev_counts);
   HIP_TRY(e, hipGetLastError());
   return UNETPP_OK;
 }

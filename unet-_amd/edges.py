@@ -249,12 +249,13 @@ def burr_mask_rulebased_np(gray, mask_cable, match_class=-1, *, band_out=10, lap
     return filter_box_np(hot, -1, min_area, max_area, math.inf, 0, out_value)
 
 
-def make_burr_scene(H, W, seed):
+def make_burr_scene(H, W, seed, noise_sigma=3.0):
     """(grey uint8 [H,W], cable uint8 0/1 [H,W]) for the burr tests: the cable class of components.make_scene_mask
     (distractor and speckle included, as a network's mask has them); a grey step one pixel inside the edge of the cable
     proper; max(60, H W / 1000) textured blobs of radius 2 .. 9 px centred on edge pixels of the mask (the burrs:
     stripes of period 4 in x or y with 15 % salt and pepper, so that the blur leaves dense edges and the Laplacian
-    passes 255); sigma = 3 noise."""
+    passes 255); sigma = 3 noise.  noise_sigma: another sigma for the same noise field (the multi-scale detector thresholds
+    |Laplacian| at 15, which sigma = 3 noise alone passes on a quarter of all pixels, so its fixtures use 1)."""
     m = cc.make_scene_mask(H, W, seed)
     cable = (m == 1).astype(np.uint8)
     r = np.random.default_rng(5003 + seed)
@@ -272,7 +273,7 @@ def make_burr_scene(H, W, seed):
         blob = ((yy - ys[k]) ** 2 + (xx - xs[k]) ** 2) <= rad * rad
         stripes = (((xx if vertical else yy) // 2) % 2) * 255.0 * np.ones(blob.shape)
         grey[y0:y1, x0:x1] = np.where(blob, np.where(pepper[y0:y1, x0:x1] >= 0, pepper[y0:y1, x0:x1], stripes), grey[y0:y1, x0:x1])
-    grey = grey + r.normal(0.0, 3.0, (H, W))
+    grey = grey + r.normal(0.0, 3.0, (H, W)) * (noise_sigma / 3.0)
     return np.clip(np.rint(grey), 0, 255).astype(np.uint8), cable
 
 
@@ -348,3 +349,172 @@ def make_direction_cases(size=40):
             d = (sa * a * (x - size / 2) + sb * b * (y - size / 2)) / n          # signed distance from a line through the centre
             frames.append(np.clip(np.rint(128 + 100 * np.tanh(d / 2.5)), 0, 255).astype(np.uint8))
     return np.stack(frames)
+
+
+# ---- the multi-scale and the DoG detector ----------------------------------------------------------------------------
+#   detect_burrs_enhanced      infer_enhanced_burr.py:69-138
+#   get_burr_mask_dog, has_burr   src/refactor/burr_detector.py:69-133
+# Device entries: unetpp_edges_union_u8, unetpp_dog_band_u8, unetpp_count_nonzero_u8 (include/unetpp.h).  The fixtures
+# (scripts/make_golden_burr_enhanced.py) pin the composition on the reference's code as above; cv2's own Sobel and blur
+# stay unpinned.
+
+SOBEL_S_MAX = 2 * 1020 * 1020   # the largest dx^2 + dy^2 of a uint8 image
+
+
+def sobel_xy_np(gray):
+    """(dx, dy) int32 of cv2.Sobel(gray, CV_64F, 1, 0, ksize=3) and cv2.Sobel(gray, CV_64F, 0, 1, ksize=3) on the RAW
+    grey image with BORDER_REFLECT_101, OpenCV's default (infer_enhanced_burr.py:93-94).  Not sobel_np: that one is the
+    Sobel inside cv2.Canny, which runs on the blurred image with BORDER_REPLICATE.  The two differ on the border
+    rows and columns only, where reflect-101 makes the derivative across the border exactly 0."""
+    p = np.pad(_check_gray(gray).astype(np.int32), 1, mode="reflect")
+    a, b, c = p[:-2, :-2], p[:-2, 1:-1], p[:-2, 2:]
+    d, f = p[1:-1, :-2], p[1:-1, 2:]
+    g, h, k = p[2:, :-2], p[2:, 1:-1], p[2:, 2:]
+    return (c + 2 * f + k) - (a + 2 * d + g), (g + 2 * h + k) - (a + 2 * b + c)
+
+
+def _u8_threshold(threshold):
+    """cv2.threshold on a uint8 image compares against floor(thresh); below 0 everything passes, from 255 on nothing."""
+    t = float(threshold)
+    if t != t:
+        raise ValueError("the threshold must be a number")
+    return int(math.floor(min(max(t, -1.0), 255.0)))
+
+
+def _sobel_level(s, root_max):
+    """np.uint8(np.sqrt(s) / np.sqrt(s.max()) * 255) for one s, in float64, truncating (infer_enhanced_burr.py:95-96)."""
+    return int(np.sqrt(np.float64(s)) / root_max * np.float64(255.0))
+
+
+def sobel_s_threshold(smax, threshold=50):
+    """The smallest integer s in [0, smax] with uint8(sqrt(s) / sqrt(smax) * 255) > threshold, smax + 1 where no s
+    passes.  sqrt, the division and the product are monotone in float64, so `s >= sobel_s_threshold(smax, t)` is the
+    per-pixel test of sobel_edges_np exactly.  Found as the device finds it: from the estimate ((t + 1) / 255)^2 smax,
+    walking down while the value below still passes and up while the value itself fails, each probe evaluating the
+    reference's own float64 expression.  smax == 0 (0 / 0 in the reference): 1, no s passes."""
+    smax, thr = int(smax), _u8_threshold(threshold)
+    if smax <= 0:
+        return 1
+    if thr < 0:
+        return 0
+    root_max = np.sqrt(np.float64(smax))
+    passes = lambda s: _sobel_level(s, root_max) > thr
+    k = np.float64(thr + 1) / np.float64(255.0)
+    c = int(min(max(np.floor(k * k * np.float64(smax)), 0.0), float(smax)))
+    if passes(c):
+        while c > 0 and passes(c - 1):
+            c -= 1
+    else:
+        while c <= smax and not passes(c):
+            c += 1
+    return c
+
+
+def sobel_edges_np(gray, threshold=50):
+    """edges_sobel of infer_enhanced_burr.py:93-97: s = dx^2 + dy^2 (an exact integer, <= 2 * 1020^2),
+    v = np.uint8(np.sqrt(s) / np.sqrt(s.max()) * 255) in float64, truncating; 255 where v > threshold.
+    The one stated departure: a frame with s.max() == 0 (a constant image) is 0 / 0 in the reference, whose uint8 cast
+    of NaN is undefined; here it has no Sobel edges."""
+    dx, dy = sobel_xy_np(gray)
+    s = (dx.astype(np.int64) ** 2 + dy.astype(np.int64) ** 2).astype(np.float64)
+    if s.max() == 0:
+        return np.zeros(s.shape, np.uint8)
+    v = (np.sqrt(s) / np.sqrt(s.max()) * 255).astype(np.uint8)
+    return np.where(v > _u8_threshold(threshold), np.uint8(255), np.uint8(0)).astype(np.uint8)
+
+
+def laplacian_edges_np(gray, threshold=15):
+    """edges_laplacian of infer_enhanced_burr.py:100-102: laplacian_abs_u8_np (the `& 255` wrap of the reference's
+    uint8 cast, reproduced and not corrected) above the threshold, 0 / 255."""
+    return np.where(laplacian_abs_u8_np(gray) > _u8_threshold(threshold), np.uint8(255), np.uint8(0)).astype(np.uint8)
+
+
+def edges_combined_np(gray, canny_edges, sobel_threshold=50, laplacian_threshold=15):
+    """edges_combined of infer_enhanced_burr.py:105-106: canny_edges | Sobel edges | Laplacian edges, bytewise.  What
+    NestedUNet.edges_combined computes for one frame given its Canny image."""
+    c = _check_gray(canny_edges)
+    if c.shape != np.asarray(gray).shape:
+        raise ValueError(f"gray {np.asarray(gray).shape} and canny_edges {c.shape} differ in shape")
+    return c | sobel_edges_np(gray, sobel_threshold) | laplacian_edges_np(gray, laplacian_threshold)
+
+
+def detect_burrs_enhanced_np(gray, mask_cable, match_class=-1, *, min_area=50, max_area=500, band_ksize=25, blur_ksize=5,
+                             blur_sigma=1.0, taps=None, canny_low=30, canny_high=100, sobel_threshold=50, laplacian_threshold=15,
+                             close_ksize=5, open_ksize=3, max_aspect=6.0, min_side=4, out_value=1):
+    """What NestedUNet.detect_burrs_enhanced computes for one frame: detect_burrs_enhanced(gray, mask_cable,
+    {"min_area": .., "max_area": ..}) (infer_enhanced_burr.py:69-138) with the function's constants as defaults.  The
+    reference's `width >= 5 and height >= 5` is keep_box's strict `> min_side` with min_side = 4: the same test on
+    integers.  An empty cable gives an empty band: the two early returns."""
+    t = resolve_taps(blur_ksize, blur_sigma, taps)
+    blurred = _check_gray(gray) if t is None else gaussian_blur_np(gray, t)
+    edges = edges_combined_np(gray, canny_np(blurred, canny_low, canny_high), sobel_threshold, laplacian_threshold)
+    return burrs_from_edges_np(edges, mask_cable, match_class, min_area=min_area, max_area=max_area, band_ksize=band_ksize,
+                               close_ksize=close_ksize, open_ksize=open_ksize, max_aspect=max_aspect, min_side=min_side,
+                               out_value=out_value)
+
+
+def resolve_dog_taps(taps1=None, taps2=None):
+    """The two kernels of get_burr_mask_dog: gaussian_taps(3, 1.0) and gaussian_taps(7, 2.0) unless given."""
+    return (check_taps(gaussian_taps(3, 1.0) if taps1 is None else taps1),
+            check_taps(gaussian_taps(7, 2.0) if taps2 is None else taps2))
+
+
+def dog_u8_np(gray, taps1=None, taps2=None):
+    """cv2.subtract(blur1, blur2) of src/refactor/burr_detector.py:94-97 on uint8: the subtraction saturates at 0 and
+    never wraps, so the reference's np.abs after it changes nothing and only the positive lobe of the difference of
+    Gaussians survives.  Reproduced, not corrected."""
+    t1, t2 = resolve_dog_taps(taps1, taps2)
+    d = gaussian_blur_np(gray, t1).astype(np.int32) - gaussian_blur_np(gray, t2).astype(np.int32)
+    return np.clip(d, 0, 255).astype(np.uint8)
+
+
+def burr_mask_dog_np(gray, mask_cable, match_class=-1, *, band_out=10, threshold=30, min_area=20, max_area=500, taps1=None,
+                     taps2=None, out_value=255):
+    """What NestedUNet.burr_mask_dog computes for one frame: get_burr_mask_dog(gray, mask_cable, BurrConfig(band_out,
+    laplacian_threshold=threshold, min_area, max_area)) (src/refactor/burr_detector.py:69-118)."""
+    el, steps, res = mo.program_band(band_out)
+    band = mo.run_program_np(mask_cable, None, el, steps, match_class, -1, res, 1)
+    hot = ((band != 0) & (dog_u8_np(gray, taps1, taps2) > _u8_threshold(threshold))).astype(np.uint8)
+    return filter_box_np(hot, -1, min_area, max_area, math.inf, 0, out_value)
+
+
+def has_burr_np(mask, min_total_area=50):
+    """has_burr of src/refactor/burr_detector.py:121-133: np.sum(mask > 0) >= min_total_area."""
+    return bool(int(np.count_nonzero(np.asarray(mask))) >= min_total_area)
+
+
+# (height, width) of the rectangles of make_crafted_enhanced_case: pairs that straddle each clause of
+# infer_enhanced_burr.py:131-135 with the config 50 / 500 after close E5 (which leaves a rectangle alone) and open E3
+# (a cross: it keeps the box and costs the four corner pixels, so the area is h w - 4).
+CRAFTED_ENHANCED_RECTS = [(14, 4), (14, 5), (4, 14), (5, 14),                       # w < 5, h < 5
+                          (6, 9), (6, 8), (7, 8), (7, 7), (9, 6),                   # area, low end: 50 kept, 44 and 45 not
+                          (24, 21), (25, 21), (22, 22), (23, 22),                   # area, high end: 500 and 480 kept, 521 and 502 not
+                          (30, 5), (31, 5), (36, 7), (43, 7)]                       # aspect: 5.999.. kept, 6.2 not; 5.14, 6.14
+
+
+def make_crafted_enhanced_case(H=200, W=336, return_boxes=False):
+    """(grey uint8 [H,W], edges uint8 0/255 [H,W], cable uint8 0/1 [H,W]) for the tail of detect_burrs_enhanced: solid
+    rectangles (CRAFTED_ENHANCED_RECTS, one in every other 24-px cell, each starting one column right of a stripe) in
+    place of the Canny output, and a cable of 1-px vertical stripes every 24 px over the columns below W - 48, whose band
+    (dilate with ELLIPSE (25,25), minus the cable) covers everything between and 12 px beyond them.  The grey image is
+    flat but for one bright square at least 14 px from every cable pixel: it is not constant (that is the 0 / 0 frame),
+    and neither its Sobel nor its Laplacian response reaches the band."""
+    boxes = []
+    edges = np.zeros((H, W), np.uint8)
+    cable = np.zeros((H, W), np.uint8)
+    last = (W - 48) // 24 * 24
+    cable[:, 0:last + 1:24] = 1
+    x = 25; y = 6; row_h = 0                                # not the cell on the image border: a close grows into the border
+    for h, w in CRAFTED_ENHANCED_RECTS:
+        if x + w + 1 > last:
+            x = 25; y += row_h + 6; row_h = 0
+        assert y + h + 6 <= H and w <= 22, "make_crafted_enhanced_case: the rectangles do not fit"
+        edges[y:y + h, x:x + w] = 255
+        boxes.append((y, x, h, w))
+        row_h = max(row_h, h)
+        x += 48
+    grey = np.full((H, W), 100, np.uint8)
+    x0 = last + 12 + 14 + 2
+    assert x0 + 6 <= W - 2
+    grey[H // 2 - 3:H // 2 + 3, x0:x0 + 6] = 180
+    return (grey, edges, cable, boxes) if return_boxes else (grey, edges, cable)

@@ -784,6 +784,127 @@ class NestedUNet:
             self._raise(rc)
         return self.filter_components_box(hot, -1, *box, max_components=max_components, out_value=out_value, check=check)
 
+    @staticmethod
+    def _same_shape(gray, other, what):
+        if hasattr(gray, "shape") and hasattr(other, "shape") and tuple(gray.shape) != tuple(other.shape):
+            raise RuntimeError(f"gray {tuple(gray.shape)} and {what} {tuple(other.shape)} differ in shape")
+
+    def edges_combined(self, gray, canny_edges=None, *, blur=(5, 1.0), canny_low=30, canny_high=100, sobel_threshold=50,
+                       laplacian_threshold=15):
+        """edges_combined of detect_burrs_enhanced (infer_enhanced_burr.py:87-106) for uint8 CUDA grey frames [B,H,W]:
+        Canny | Sobel | Laplacian, uint8 (unet_amd/edges.py edges_combined_np).  Sobel: 255 where
+        uint8(sqrt(dx^2 + dy^2) / its maximum over the frame * 255) > sobel_threshold, cv2.Sobel(ksize=3) on the raw
+        frame with BORDER_REFLECT_101; the per-frame maximum is reduced on the device and never read back.  A constant
+        frame (0 / 0 in the reference) has no Sobel edges.  Laplacian: (|cv2.Laplacian| & 255) > laplacian_threshold.
+        canny_edges: the Canny image to OR into (left unchanged), or None to run canny(gray, canny_low, canny_high,
+        blur=blur) here, blur as for canny()."""
+        import torch
+        from . import edges as ed
+        sthr, lthr = ed._u8_threshold(sobel_threshold), ed._u8_threshold(laplacian_threshold)
+        if hasattr(gray, "shape") and len(gray.shape) == 3:
+            self._check_edge_shape(gray.shape)
+        gray = self._edge_input(gray)
+        if canny_edges is None:
+            canny_edges = out = self.canny(gray, canny_low, canny_high, blur=blur)       # ORed in place: the image is ours
+        else:
+            self._same_shape(gray, canny_edges, "canny_edges")
+            canny_edges = self._edge_input(canny_edges, "canny_edges")
+            out = torch.empty_like(gray)
+        b, h, w = gray.shape
+        lib = _lib.load()
+        key = ("edges_union", b)
+        ws = self._cc_workspaces.get(key)
+        if ws is None or ws.device != gray.device:
+            ws = self._cc_workspaces[key] = torch.empty(int(lib.unetpp_edges_union_workspace_bytes(b)), dtype=torch.uint8, device=gray.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        rc = lib.unetpp_edges_union_u8(self._handle, p(gray), p(canny_edges), b, h, w, sthr, lthr, p(ws), p(out),
+                                       ctypes.c_void_p(torch.cuda.current_stream(gray.device).cuda_stream))
+        if rc != 0:
+            self._raise(rc)
+        return out
+
+    def detect_burrs_enhanced(self, gray, mask_cable, match_class: int = -1, *, min_area=50, max_area=500, band_ksize: int = 25,
+                              blur_ksize: int = 5, blur_sigma: float = 1.0, taps=None, canny_low=30, canny_high=100, sobel_threshold=50,
+                              laplacian_threshold=15, close_ksize: int = 5, open_ksize: int = 3, max_aspect=6.0, min_side=4,
+                              out_value: int = 1, max_components: int = 8192, check: bool = True):
+        """detect_burrs_enhanced(frame_gray, mask_cable, config) (infer_enhanced_burr.py:69-138; the defaults are the
+        function's constants and the config 50 / 500 it is run with) for uint8 CUDA grey frames and cable masks [B,H,W],
+        nothing leaving the device: edges_combined -> burrs_from_edges ((dilate(cable, E25) & ~cable) & edges, close E5,
+        open E3 in one morphology launch, components, the box rule).  The reference's `width >= 5 and height >= 5` is
+        the box rule's strict `> min_side` with min_side = 4.  An empty cable gives an empty band and so an empty
+        result: the two early returns need no read-back.  uint8 [B,H,W], out_value (1 in the reference)."""
+        from . import edges as ed
+        self._check_box(min_area, max_area, max_aspect, min_side)
+        self._check_out_value(out_value)
+        t = ed.resolve_taps(blur_ksize, blur_sigma, taps)
+        ed.program_burr(band_ksize, close_ksize, open_ksize)
+        self._same_shape(gray, mask_cable, "mask_cable")
+        edges = self.edges_combined(gray, blur=t, canny_low=canny_low, canny_high=canny_high, sobel_threshold=sobel_threshold,
+                                    laplacian_threshold=laplacian_threshold)
+        return self.burrs_from_edges(edges, mask_cable, match_class, min_area=min_area, max_area=max_area, band_ksize=band_ksize,
+                                     close_ksize=close_ksize, open_ksize=open_ksize, max_aspect=max_aspect, min_side=min_side,
+                                     out_value=out_value, max_components=max_components, check=check)
+
+    def dog_band(self, gray, band, *, threshold=30, taps1=None, taps2=None):
+        """255 where band != 0 and cv2.subtract(GaussianBlur(gray, 3, 1.0), GaussianBlur(gray, 7, 2.0)) > threshold, else
+        0, for uint8 CUDA images [B,H,W] (src/refactor/burr_detector.py:93-103; unet_amd/edges.py dog_u8_np): both
+        blurs, the saturating subtraction, the band and the threshold in one kernel.  taps1 / taps2 replace the two
+        kernels (odd, at most 7 integers summing to 256, e.g. cv2's own)."""
+        import torch
+        from . import edges as ed
+        thr = ed._u8_threshold(threshold)
+        t1, t2 = ed.resolve_dog_taps(taps1, taps2)
+        self._same_shape(gray, band, "band")
+        if hasattr(gray, "shape") and len(gray.shape) == 3:
+            self._check_edge_shape(gray.shape)
+        gray, band = self._edge_input(gray), self._edge_input(band, "band")
+        b, h, w = gray.shape
+        hot = torch.empty_like(gray)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        rc = _lib.load().unetpp_dog_band_u8(self._handle, p(gray), p(band), b, h, w, self._c_taps(t1), len(t1), self._c_taps(t2), len(t2),
+                                            thr, p(hot), ctypes.c_void_p(torch.cuda.current_stream(gray.device).cuda_stream))
+        if rc != 0:
+            self._raise(rc)
+        return hot
+
+    def burr_mask_dog(self, gray, mask_cable, match_class: int = -1, *, band_out: int = 10, threshold=30, min_area=20, max_area=500,
+                      taps1=None, taps2=None, out_value: int = 255, max_components: int = 8192, check: bool = True):
+        """get_burr_mask_dog(frame_gray, mask_cable, BurrConfig(...)) (src/refactor/burr_detector.py:69-118; `threshold`
+        is the config's laplacian_threshold, which this detector reads too) on the device: boundary_band -> dog_band
+        -> components -> min_area <= area <= max_area.  The subtraction of the two blurs saturates at 0, so only the
+        positive lobe counts, as in the reference.  uint8 [B,H,W], out_value (255 in the reference) on the kept
+        components."""
+        from . import edges as ed
+        from . import morphology as mo
+        box = self._check_box(min_area, max_area, float("inf"), 0)
+        out_value = self._check_out_value(out_value)
+        ed._u8_threshold(threshold)
+        ed.resolve_dog_taps(taps1, taps2)
+        program = self._morph_named("band", (int(band_out),), mo.program_band)
+        self._same_shape(gray, mask_cable, "mask_cable")
+        if hasattr(gray, "shape") and len(gray.shape) == 3:
+            self._check_edge_shape(gray.shape)
+        band = self._morph_launch(program, mask_cable, match_class, None, -1, 1)
+        hot = self.dog_band(gray, band, threshold=threshold, taps1=taps1, taps2=taps2)
+        return self.filter_components_box(hot, -1, *box, max_components=max_components, out_value=out_value, check=check)
+
+    def count_nonzero(self, mask):
+        """np.count_nonzero per frame of a uint8 CUDA mask [B,H,W] (any H, W): int32 [B] on the device."""
+        import torch
+        mask = self._edge_input(mask, "mask")
+        b, h, w = mask.shape
+        counts = torch.empty((b,), dtype=torch.int32, device=mask.device)      # uint32 bits; H * W <= 2^30
+        rc = _lib.load().unetpp_count_nonzero_u8(self._handle, ctypes.c_void_p(mask.data_ptr()), b, h, w, ctypes.c_void_p(counts.data_ptr()),
+                                                 ctypes.c_void_p(torch.cuda.current_stream(mask.device).cuda_stream))
+        if rc != 0:
+            self._raise(rc)
+        return counts
+
+    def has_burr(self, mask, min_total_area=50):
+        """has_burr(burr_mask, min_total_area) (src/refactor/burr_detector.py:121-133) for a uint8 CUDA burr mask
+        [B,H,W]: bool [B] on the device, np.sum(mask > 0) >= min_total_area per frame.  Nothing is read back."""
+        return self.count_nonzero(mask) >= min_total_area
+
     def resize_frames(self, frames, size_hw):
         """cv2.resize(frame, (W, H), interpolation=cv2.INTER_LINEAR) for uint8 CUDA frames [B,h,w,C] -> [B,H,W,C]
         (preprocess_image, infer_two_stage_burr.py:124).  Chain with segment(): the BGR->RGB swap and /255 run

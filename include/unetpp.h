@@ -212,8 +212,8 @@ int unetpp_forward_ds(unetpp_engine* e, const void* dev_input, int in_format, in
  * From a uint8 class-index mask [B,H,W] (e.g. the dev_mask of a forward): per-frame class pixel counts
  * (np.sum(mask_cable) / coverage, infer_two_stage_burr.py:333-340, src/utils/geometry_enhanced.py:151-152) and,
  * per class and row, the first and last column of that class — the operands of _compute_width_per_row
- * (geometry_enhanced.py:45-74: width = xs.max() - xs.min() + 1).  The reference's Gaussian smoothing (cv2) stays on
- * the host; its connected-component filtering runs on the device, see unetpp_components_filter below.
+ * (geometry_enhanced.py:45-74: width = xs.max() - xs.min() + 1).  The reference's Gaussian smoothing of these widths
+ * is unetpp_width_profile, its connected-component filtering unetpp_components_filter, both below.
  *   dev_counts   uint32 [B,num_classes]      (zeroed by this call)
  *   dev_row_min  int32  [B,num_classes,H]    W  when the row has no pixel of the class
  *   dev_row_max  int32  [B,num_classes,H]    -1 when the row has no pixel of the class
@@ -484,6 +484,64 @@ int unetpp_dog_band_u8(unetpp_engine* e, const uint8_t* dev_gray, const uint8_t*
                        void* stream);
 int unetpp_count_nonzero_u8(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, uint32_t* dev_counts,
                             void* stream);
+
+/* ---- measurements on the device: diameters, thickness profile, defect summary ---------------------------------------
+ * The step the reference's production loop ends in (infer_video_production.py:198-226): compute_diameter_metrics,
+ * compute_thickness_profile and analyze_defects (src/utils/geometry_enhanced.py:113-330) and
+ * diameter_profile_from_masks (src/utils/geometry.py:28-64).  Their component filters, hole mask and labelling are
+ * unetpp_components(_filter) and unetpp_morphology above; the entries here are what is left: widths per row, their
+ * smoothing, the valid rows and medians, and the reduction of a statistics table.  unet_amd/geometry.py is the NumPy
+ * form.  All three are asynchronous on `stream` and allocate nothing.
+ *
+ * unetpp_row_widths: _compute_width_per_row(smooth=False) (geometry_enhanced.py:61-67; _width_per_row, geometry.py:7-18)
+ * of two binary planes, and the mask.sum() behind the coverages (geometry_enhanced.py:152-153, :271).  Planes as for
+ * unetpp_morphology: foreground of dev_mask0 is (mask == match0), or (mask != 0) for match0 < 0; likewise dev_mask1 /
+ * match1.  The two pointers may be the same tensor (cable and tape of one class mask); dev_mask1 may be NULL (plane 1
+ * is then empty).  Masks uint8 [B,h,w], any 1 <= h, w <= 65535.
+ *   dev_widths float32 [B,2,h] = last - first + 1 over the foreground columns of the row, 0 for an empty row
+ *                               (integers <= 65535: exact)
+ *   dev_area   uint32  [B,2]   = foreground pixels of each plane (zeroed by the call on the same stream)
+ *
+ * unetpp_width_profile: the rest of compute_diameter_metrics / compute_thickness_profile (geometry_enhanced.py:144-168,
+ * :211-219) for dev_widths float32 [B,2,h], h <= 4096 (UNETPP_E_INVALID above: one workgroup holds a frame's widths).
+ *   smoothing  cv2.GaussianBlur(widths.reshape(-1, 1), (1, k), sigmaX=0) with the kernel given as `taps`: n_taps (odd,
+ *              1..127) float32 values in HOST memory (read during the call), finite and symmetric.  BORDER_REFLECT_101
+ *              (cv2.borderInterpolate, with its loop for h <= n_taps / 2).  OpenCV's symmetric column filter, every
+ *              operation rounded to float32, no contraction, r = n_taps / 2:
+ *                s = taps[r] * w[y];  for j = 1 .. r ascending:  s = s + taps[r + j] * (w[y + j] + w[y - j])
+ *              n_taps = 1 with taps[0] = 1 is the identity.  cv2's own kernel values and the summation order of its
+ *              SIMD paths are not pinned by this project's tests.
+ *   dev_smoothed float32 [B,2,h]  the smoothed widths
+ *   dev_valid    uint8   [B,h]    smoothed plane 0 > 0 && smoothed plane 1 > 0
+ *   dev_delta    float32 [B,h]    smoothed plane 1 - smoothed plane 0; may be NULL
+ *   dev_out      [B] records      valid_rows = the number of valid rows; when valid_rows >= min_valid_rows, dc_px / dt_px =
+ *                                 np.median of smoothed plane 0 / 1 over the valid rows as a float32 array forms it (the
+ *                                 middle element; for an even count (a + b) rounded to float32, then halved); otherwise
+ *                                 both are 0, the reference's early return.  min_valid_rows >= 1 (UNETPP_E_INVALID for
+ *                                 0: the reference would take the median of nothing).
+ *
+ * unetpp_components_summary: the reductions analyze_defects makes of a statistics table (geometry_enhanced.py:291-294,
+ * :302-309) from dev_num [B] and dev_stats [B,capacity,5] of unetpp_components.  dev_out int64 [B,4]:
+ *   [0] max(0, num - 1), the component count; exact even when num > capacity
+ *   [1] the number of labels 1 .. min(num, capacity) - 1 with area >= min_area
+ *   [2] the sum of those areas
+ *   [3] the largest area of any of these labels (0 when there is none)
+ * dev_stats may be NULL (unetpp_components run without stats): [1..3] are then 0.
+ *
+ * Errors: UNETPP_E_INVALID for a bad shape, an even n_taps, n_taps > 127, taps that are not finite or not symmetric,
+ * min_valid_rows < 1, capacity < 2, NULL where not allowed. */
+typedef struct unetpp_width_profile_out {
+  float dc_px, dt_px;
+  int32_t valid_rows;
+} unetpp_width_profile_out;
+
+int unetpp_row_widths(unetpp_engine* e, const uint8_t* dev_mask0, int match0, const uint8_t* dev_mask1, int match1,
+                      int batch, int h, int w, float* dev_widths, uint32_t* dev_area, void* stream);
+int unetpp_width_profile(unetpp_engine* e, const float* dev_widths, int batch, int h, const float* taps, int n_taps,
+                         int min_valid_rows, float* dev_smoothed, uint8_t* dev_valid, float* dev_delta,
+                         unetpp_width_profile_out* dev_out, void* stream);
+int unetpp_components_summary(unetpp_engine* e, const int32_t* dev_num, const int32_t* dev_stats, int batch, int capacity,
+                              int64_t min_area, int64_t* dev_out, void* stream);
 
 #ifdef __cplusplus
 }

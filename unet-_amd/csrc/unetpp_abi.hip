@@ -35,6 +35,7 @@
 #include "convt2x2_mfma.h"
 #include "edges.h"
 #include "edges_multi.h"
+#include "geometry.h"
 #include "morphology.h"
 #include "tapmm_ws.h"
 
@@ -1637,6 +1638,59 @@ int unetpp_count_nonzero_u8(unetpp_engine* e, const uint8_t* dev_mask, int batch
   HIP_TRY(e, hipMemsetAsync(dev_counts, 0, (size_t)batch * sizeof(uint32_t), s));
   hipLaunchKernelGGL(count_nonzero_kernel, dim3((unsigned)((hw + CC_CHUNK - 1) / CC_CHUNK), (unsigned)batch), dim3(ED_THREADS), 0, s, dev_mask, hw,
                      (int)(hw % 16 == 0 && (uintptr_t)dev_mask % 16 == 0), (unsigned*)dev_counts);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+// ---- measurements: row widths, width profile, component summary (geometry.h) -------------------------------------------
+int unetpp_row_widths(unetpp_engine* e, const uint8_t* dev_mask0, int match0, const uint8_t* dev_mask1, int match1, int batch, int h,
+                      int w, float* dev_widths, uint32_t* dev_area, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_mask0 || !dev_widths || !dev_area) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (batch < 1 || batch > 65535 || h < 1 || w < 1 || h > 65535 || w > 65535) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if (match0 > 255 || match1 > 255) return fail(e, UNETPP_E_INVALID, "match class %d / %d out of range", match0, match1);
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(e, hipMemsetAsync(dev_area, 0, (size_t)batch * 2 * sizeof(uint32_t), s));
+  const int vec0 = w % 16 == 0 && (uintptr_t)dev_mask0 % 16 == 0, vec1 = w % 16 == 0 && (uintptr_t)dev_mask1 % 16 == 0;
+  hipLaunchKernelGGL(row_widths_kernel, dim3((unsigned)((h + GEO_ROWS_PER_WG - 1) / GEO_ROWS_PER_WG), (unsigned)batch), dim3(GEO_THREADS), 0, s,
+                     dev_mask0, match0, dev_mask1, match1, h, w, vec0, vec1, dev_widths, (unsigned*)dev_area);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_width_profile(unetpp_engine* e, const float* dev_widths, int batch, int h, const float* taps, int n_taps, int min_valid_rows,
+                         float* dev_smoothed, uint8_t* dev_valid, float* dev_delta, unetpp_width_profile_out* dev_out, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_widths || !taps || !dev_smoothed || !dev_valid || !dev_out) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (batch < 1 || batch > 65535 || h < 1) return fail(e, UNETPP_E_INVALID, "bad shape %dx%d", batch, h);
+  if (h > GEO_MAX_ROWS) return fail(e, UNETPP_E_INVALID, "width_profile: %d rows, at most %d", h, GEO_MAX_ROWS);
+  if (n_taps < 1 || n_taps > GEO_MAX_TAPS || n_taps % 2 == 0) return fail(e, UNETPP_E_INVALID, "n_taps %d: odd, 1..%d", n_taps, GEO_MAX_TAPS);
+  if (min_valid_rows < 1) return fail(e, UNETPP_E_INVALID, "min_valid_rows %d: at least 1", min_valid_rows);
+  const int r = n_taps / 2;
+  GeoTaps gt{};
+  for (int j = 0; j <= r; ++j) {
+    if (!std::isfinite(taps[r + j]) || !(taps[r + j] == taps[r - j])) return fail(e, UNETPP_E_INVALID, "taps must be finite and symmetric");
+    gt.t[j] = taps[r + j];
+  }
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  static_assert(sizeof(unetpp_width_profile_out) == sizeof(GeoProfileOut), "width profile record");
+  hipLaunchKernelGGL(width_profile_kernel, dim3((unsigned)batch), dim3(GEO_THREADS), 2 * (size_t)(h + 2 * r) * sizeof(float), s, dev_widths, h,
+                     gt, r, min_valid_rows, dev_smoothed, dev_valid, dev_delta, (GeoProfileOut*)dev_out);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_components_summary(unetpp_engine* e, const int32_t* dev_num, const int32_t* dev_stats, int batch, int capacity, int64_t min_area,
+                              int64_t* dev_out, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_num || !dev_out) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (batch < 1 || batch > 65535) return fail(e, UNETPP_E_INVALID, "bad batch %d", batch);
+  if (capacity < 2) return fail(e, UNETPP_E_INVALID, "capacity %d: at least 2 rows (background + one component)", capacity);
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(components_summary_kernel, dim3((unsigned)batch), dim3(GEO_THREADS), 0, (hipStream_t)stream, (const int*)dev_num,
+                     (const int*)dev_stats, capacity, (long long)min_area, (long long*)dev_out);
   HIP_TRY(e, hipGetLastError());
   return UNETPP_OK;
 }

@@ -2,7 +2,8 @@
 everything between "a BGR video frame" and "uint8 class masks at frame size, clipped to the ROI".
 `segment_frames` starts from frames already at model resolution; `process_frames` also runs the two
 cv2.resize steps either side on the device (those two restate OpenCV's published
-algorithm and are parity-unpinned, see oracle/unetpp_oracle.py).
+algorithm and are parity-unpinned, see oracle/unetpp_oracle.py).  `measure_frames` is the tail of the production loop
+(infer_video_production.py:198-226): the diameter metrics and the defect analysis of every frame of a batch.
 """
 from __future__ import annotations
 
@@ -66,3 +67,43 @@ def process_frames(model, frames_bgr_u8, target_size=(512, 512), roi="fixed", de
     cable = model.resize_masks(pred, (fw, fh), match_class=1, roi=roi)
     tape = model.resize_masks(pred, (fw, fh), match_class=2, roi=roi)
     return pred, cable, tape
+
+
+_DIAMETER_FIELDS = ("dc_px", "dt_px", "delta_d_px", "dc_mm", "dt_mm", "delta_d_mm", "valid_rows", "cable_coverage", "tape_coverage")
+_DEFECT_FIELDS = ("tape_hole_ratio", "tape_num_holes", "tape_coverage", "cable_num_components", "tape_num_components",
+                  "tape_largest_area_ratio", "total_defect_area")
+_INT_FIELDS = {"valid_rows", "tape_num_holes", "cable_num_components", "tape_num_components", "total_defect_area"}
+
+
+def measure_frames(model, pred, mm_per_px=0.05, defect_classes=(3, 4, 5, 6), max_components=8192):
+    """The tail of process_frame (infer_video_production.py:198-226) for a uint8 CUDA class mask [B,H,W] (e.g. from
+    segment()): compute_diameter_metrics(pred, 1, 2, mm_per_px), `None` where valid_rows < 20, else analyze_defects(pred,
+    1, 2, defect_classes).  Everything is computed on the device for the whole batch; ONE read-back brings the scalars.
+    Returns a list of B records, each None or
+      {"diameter": {DiameterMetrics' fields}, "defect_analysis": {DefectAnalysis' fields, defect_areas a {class: area}
+       dict}, "delta_d_mm": diameter.delta_d_mm, "wrap_diameter_mm": diameter.dt_mm}
+    as plain Python numbers: what FrameResult carries besides timestamp_ns and frame_id, ready for the window
+    aggregator.  RuntimeError for a frame with more than max_components - 1 components in one of its labellings."""
+    import torch
+    k = int(max_components)
+    defect_classes = [int(c) for c in defect_classes]
+    dia, over_d = model._diameter_metrics(pred, 1, 2, mm_per_px, 20, 31, 50, None, k)
+    dfa, over_a = model._analyze_defects(pred, 1, 2, defect_classes, 10, k)
+    cols = [dia[f] for f in _DIAMETER_FIELDS] + [dfa[f] for f in _DEFECT_FIELDS]
+    cols += [dfa["defect_areas"][:, i] for i in range(len(defect_classes))] + [over_d | over_a]
+    table = torch.stack([c.to(torch.float64) for c in cols], dim=1).cpu().tolist()     # integers here are far below 2^53: exact
+    out = []
+    for i, row in enumerate(table):
+        if row[-1]:
+            raise RuntimeError(f"measure_frames: frame {i} has more than max_components - 1 = {k - 1} components in one of its "
+                               f"labellings: raise max_components")
+        conv = lambda f, v: int(v) if f in _INT_FIELDS else v
+        d = {f: conv(f, v) for f, v in zip(_DIAMETER_FIELDS, row)}
+        if d["valid_rows"] < 20:
+            out.append(None)
+            continue
+        a = {f: conv(f, v) for f, v in zip(_DEFECT_FIELDS, row[len(_DIAMETER_FIELDS):])}
+        base = len(_DIAMETER_FIELDS) + len(_DEFECT_FIELDS)
+        a["defect_areas"] = {c: int(row[base + j]) for j, c in enumerate(defect_classes)}
+        out.append({"diameter": d, "defect_analysis": a, "delta_d_mm": d["delta_d_mm"], "wrap_diameter_mm": d["dt_mm"]})
+    return out

@@ -584,6 +584,234 @@ class NestedUNet:
                                        f"max_components = {k}: raise max_components")
         return num_holes, hole_area
 
+    # ------------------------------------------------------------------ measurements (unet_amd/geometry.py is the NumPy form)
+    @staticmethod
+    def _stream(t):
+        import torch
+        return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+    @staticmethod
+    def _raise_overflow(over, k, what):
+        """`over` bool [B] on the device (one read-back, synchronises): the frames whose labelling overflowed."""
+        bad = over.nonzero().flatten().cpu().tolist()
+        if bad:
+            raise RuntimeError(f"{what}: frame {bad[0]} has more than max_components - 1 = {k - 1} components in one of its "
+                               f"labellings: raise max_components")
+
+    def row_widths(self, mask0, match0: int = -1, mask1=None, match1: int = -1):
+        """_compute_width_per_row(smooth=False) (src/utils/geometry_enhanced.py:61-67) of two binary planes of uint8
+        CUDA masks [B,H,W] in one launch: plane 0 = (mask0 == match0), plane 1 = (mask1 == match1) (match < 0: != 0;
+        mask1 may be mask0 itself, or None for an empty plane 1).  Returns (widths float32 [B,2,H] = last - first + 1
+        over the foreground columns of a row, 0 for an empty row; area int64 [B,2] = foreground pixels)."""
+        import torch
+        mask0 = self._edge_input(mask0, "mask0")
+        if mask1 is not None:
+            same = mask1 is mask0
+            mask1 = mask0 if same else self._edge_input(mask1, "mask1")
+            if mask1.shape != mask0.shape:
+                raise RuntimeError(f"mask1 {tuple(mask1.shape)} does not match mask0 {tuple(mask0.shape)}")
+        b, h, w = mask0.shape
+        widths = torch.empty((b, 2, h), dtype=torch.float32, device=mask0.device)
+        area = torch.empty((b, 2), dtype=torch.int32, device=mask0.device)            # uint32 bits
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = _lib.load().unetpp_row_widths(self._handle, p(mask0), int(match0), p(mask1), int(match1), b, h, w, p(widths), p(area),
+                                           self._stream(mask0))
+        if rc != 0:
+            self._raise(rc)
+        return widths, area.to(torch.int64) & 0xFFFFFFFF
+
+    def width_profile(self, widths, kernel_size: int = 31, min_valid_rows: int = 20, taps=None, want_delta: bool = True):
+        """The smoothing, valid rows and medians of compute_diameter_metrics (geometry_enhanced.py:144-168) for raw widths
+        float32 CUDA [B,2,H] (row_widths), H <= 4096, one launch.  The kernel is geometry.gaussian_taps_f32(kernel_size)
+        (an even size becomes size + 1, <= 1 means none) or `taps` (odd, at most 127 symmetric float32 values, e.g.
+        cv2.getGaussianKernel's own).  Returns (smoothed float32 [B,2,H], valid uint8 [B,H], delta float32 [B,H] =
+        plane 1 - plane 0 or None, dc_px float32 [B], dt_px float32 [B], valid_rows int32 [B]); the medians are 0 where
+        valid_rows < min_valid_rows."""
+        import torch
+        from . import geometry as ge
+        t = ge.resolve_taps(kernel_size, taps)
+        if int(min_valid_rows) < 1:
+            raise ValueError(f"min_valid_rows must be at least 1, got {min_valid_rows!r}")
+        if not (isinstance(widths, torch.Tensor) and widths.is_cuda and widths.dtype == torch.float32 and widths.dim() == 3 and
+                widths.shape[1] == 2):
+            raise RuntimeError("widths must be a float32 CUDA tensor [B,2,H]")
+        if self._device_index is None:
+            self.to(widths.device)
+        if widths.device.index != self._device_index:
+            raise RuntimeError(f"widths on {widths.device}, engine on cuda:{self._device_index}")
+        self._ensure_engine(1, self._SIZE_MULTIPLE, self._SIZE_MULTIPLE)
+        widths = widths.contiguous()
+        b, _, h = widths.shape
+        if h > ge.MAX_ROWS:
+            raise ValueError(f"width_profile: {h} rows, at most {ge.MAX_ROWS}")
+        dev = widths.device
+        smoothed = torch.empty_like(widths)
+        valid = torch.empty((b, h), dtype=torch.uint8, device=dev)
+        delta = torch.empty((b, h), dtype=torch.float32, device=dev) if want_delta else None
+        out = torch.empty((b, 3), dtype=torch.int32, device=dev)                      # {float dc_px, dt_px; int32 valid_rows}
+        p = lambda x: ctypes.c_void_p(x.data_ptr()) if x is not None else None
+        rc = _lib.load().unetpp_width_profile(self._handle, p(widths), b, h, t.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), len(t),
+                                              int(min_valid_rows), p(smoothed), p(valid), p(delta), p(out), self._stream(widths))
+        if rc != 0:
+            self._raise(rc)
+        med = out[:, :2].view(torch.float32)
+        return smoothed, valid, delta, med[:, 0], med[:, 1], out[:, 2]
+
+    def components_summary(self, num, stats, min_area: int = 0):
+        """The reductions analyze_defects makes of a statistics table (geometry_enhanced.py:291-294, :302-309) from `num`
+        int32 [B] and `stats` int32 [B,K,5] of components() (stats may be None): int64 [B,4] on the device =
+        (max(0, num - 1); labels 1..min(num, K)-1 with area >= min_area; the sum of those areas; the largest area)."""
+        import torch
+        if not (isinstance(num, torch.Tensor) and num.is_cuda and num.dtype == torch.int32 and num.dim() == 1):
+            raise RuntimeError("num must be an int32 CUDA tensor [B]")
+        b = num.shape[0]
+        if stats is None:
+            k = 2
+        else:
+            if not (isinstance(stats, torch.Tensor) and stats.is_cuda and stats.dtype == torch.int32 and stats.dim() == 3 and
+                    stats.shape[0] == b and stats.shape[2] == 5):
+                raise RuntimeError("stats must be an int32 CUDA tensor [B,K,5]")
+            stats, k = stats.contiguous(), stats.shape[1]
+        if self._device_index is None:
+            self.to(num.device)
+        self._ensure_engine(1, self._SIZE_MULTIPLE, self._SIZE_MULTIPLE)
+        num = num.contiguous()
+        out = torch.empty((b, 4), dtype=torch.int64, device=num.device)
+        p = lambda x: ctypes.c_void_p(x.data_ptr()) if x is not None else None
+        rc = _lib.load().unetpp_components_summary(self._handle, p(num), p(stats), b, k, int(min_area), p(out), self._stream(num))
+        if rc != 0:
+            self._raise(rc)
+        return out
+
+    def _filter_largest(self, pred, match_class, min_area, k):
+        """filter_components(rule='largest', check=False) that also hands back `num`: (uint8 [B,H,W], int32 [B])."""
+        import torch
+        labels, num, stats, sums, ws, stream = self._components(pred, match_class, 8, k, True)
+        b, h, w = labels.shape
+        params = _lib.CcRule(float(min_area), 50.0, 300.0, 0.3, 1.6, 0.3, float(w))
+        out = torch.empty((b, h, w), dtype=torch.uint8, device=labels.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        rc = _lib.load().unetpp_components_filter(self._handle, p(labels), p(num), p(stats), p(sums), b, h, w, k,
+                                                  _lib.CC_RULES["largest"], ctypes.byref(params), 1, p(out), p(ws), stream)
+        if rc != 0:
+            self._raise(rc)
+        return out, num
+
+    def _profile_of_largest(self, pred, cls0, cls1, min_area, kernel_size, taps, min_valid_rows, k, want_delta):
+        from . import geometry as ge
+        t = ge.resolve_taps(kernel_size, taps)
+        pred = self._edge_input(pred, "pred")
+        if pred.shape[1] > ge.MAX_ROWS:
+            raise ValueError(f"{pred.shape[1]} rows, at most {ge.MAX_ROWS}")
+        m0, n0 = self._filter_largest(pred, int(cls0), min_area, k)
+        m1, n1 = self._filter_largest(pred, int(cls1), min_area, k)
+        widths, area = self.row_widths(m0, -1, m1, -1)
+        return self.width_profile(widths, 1, min_valid_rows, t, want_delta) + (area, (n0 > k) | (n1 > k))
+
+    def _diameter_metrics(self, pred, cable_cls, tape_cls, mm_per_px, min_valid_rows, kernel_size, min_area, taps, k):
+        import torch
+        if int(min_valid_rows) < 1:
+            raise ValueError(f"min_valid_rows must be at least 1, got {min_valid_rows!r}")
+        _, _, _, dc, dt, rows, area, over = self._profile_of_largest(pred, cable_cls, tape_cls, min_area, kernel_size, taps,
+                                                                     min_valid_rows, k, False)
+        mm = float(mm_per_px)
+        dc_px, dt_px = dc.to(torch.float64), dt.to(torch.float64)          # float(np.float32 median)
+        dc_mm, dt_mm = dc_px * mm, dt_px * mm
+        # a tensor divisor: torch divides by a Python scalar through its reciprocal, which is not the reference's quotient
+        cov = area.to(torch.float64) / torch.full_like(area, pred.shape[1] * pred.shape[2], dtype=torch.float64)
+        return {"dc_px": dc_px, "dt_px": dt_px, "delta_d_px": dt_px - dc_px, "dc_mm": dc_mm, "dt_mm": dt_mm,
+                "delta_d_mm": dt_mm - dc_mm, "valid_rows": rows.to(torch.int64), "cable_coverage": cov[:, 0],
+                "tape_coverage": cov[:, 1]}, over
+
+    def diameter_metrics(self, pred, cable_cls: int = 1, tape_cls: int = 2, mm_per_px: float = 0.05, min_valid_rows: int = 20,
+                         kernel_size: int = 31, min_area=50, taps=None, max_components: int = 8192, check: bool = True):
+        """compute_diameter_metrics(pred_mask, cable_cls, tape_cls, mm_per_px, min_valid_rows)
+        (src/utils/geometry_enhanced.py:113-185; kernel_size=31 and min_area=50 are the function's constants) for a uint8
+        CUDA class mask [B,H,W], H <= 4096, nothing but the result leaving the device: the largest component of each
+        class (filter_components, rule='largest'), one row_widths launch, one width_profile launch.  Returns a dict of
+        [B] device tensors with DiameterMetrics' field names: dc_px, dt_px, delta_d_px, dc_mm, dt_mm, delta_d_mm,
+        cable_coverage, tape_coverage float64 (formed as the reference forms them: float(float32 median), dt - dc,
+        px * mm_per_px, dt_mm - dc_mm, area / (H W)), valid_rows int64.  Where valid_rows < min_valid_rows the six
+        diameters are 0.  `taps` replaces gaussian_taps_f32(kernel_size), e.g. by cv2.getGaussianKernel's own values.
+        max_components and check as for filter_components (check=True: one read-back, synchronises)."""
+        k = int(max_components)
+        out, over = self._diameter_metrics(pred, cable_cls, tape_cls, mm_per_px, min_valid_rows, kernel_size, min_area, taps, k)
+        if check:
+            self._raise_overflow(over, k, "diameter_metrics")
+        return out
+
+    def thickness_profile(self, pred, cable_cls: int = 1, tape_cls: int = 2, mm_per_px: float = 0.05, kernel_size: int = 31, taps=None):
+        """compute_thickness_profile (src/utils/geometry_enhanced.py:188-225; no component filter) for a uint8 CUDA class
+        mask [B,H,W], H <= 4096: {'delta_d_mm': float32 [B,H] = (tape - cable) * float32(mm_per_px), 'valid_mask': bool
+        [B,H]} on the device (y_coords is arange(H)).  Two launches."""
+        import torch
+        from . import geometry as ge
+        t = ge.resolve_taps(kernel_size, taps)
+        pred = self._edge_input(pred, "pred")
+        if pred.shape[1] > ge.MAX_ROWS:
+            raise ValueError(f"{pred.shape[1]} rows, at most {ge.MAX_ROWS}")
+        widths, _ = self.row_widths(pred, int(cable_cls), pred, int(tape_cls))
+        _, valid, delta, _, _, _ = self.width_profile(widths, 1, 1, t, True)
+        mm = torch.tensor(float(np.float32(mm_per_px)), dtype=torch.float32, device=pred.device)
+        return {"delta_d_mm": delta * mm, "valid_mask": valid != 0}
+
+    def diameter_profile(self, pred, cable_cls: int, wrap_cls: int, kernel_size: int = 31, taps=None, max_components: int = 8192,
+                         check: bool = True):
+        """diameter_profile_from_masks(pred, cable_cls, wrap_cls) (src/utils/geometry.py:28-64, used by
+        src/infer/postprocess.py:29) for a uint8 CUDA class mask [B,H,W], H <= 4096: the largest component of each class
+        with no area floor, the widths per row, smooth_1d(., 31).  {'w_cable_px', 'w_wrap_px': float32 [B,H], 'valid':
+        uint8 [B,H]} on the device."""
+        k = int(max_components)
+        sm, valid, _, _, _, _, _, over = self._profile_of_largest(pred, cable_cls, wrap_cls, 0, kernel_size, taps, 1, k, False)
+        if check:
+            self._raise_overflow(over, k, "diameter_profile")
+        return {"w_cable_px": sm[:, 0], "w_wrap_px": sm[:, 1], "valid": valid}
+
+    def _analyze_defects(self, pred, cable_cls, tape_cls, defect_classes, hole_min_size, k):
+        import torch
+        from . import morphology as mo
+        pred = self._edge_input(pred, "pred")
+        defect_classes = [int(c) for c in defect_classes]
+        b, h, w = pred.shape
+        holes = self._morph_launch(self._morph_named("holes", (), mo.program_holes), pred, int(tape_cls), None, -1, 1)
+        _, tnum, tstats, _, _, _ = self._components(pred, int(tape_cls), 8, k, True)
+        tape = self.components_summary(tnum, tstats, 0)
+        _, hnum, hstats, _, _, _ = self._components(holes, -1, 8, k, True)
+        hole = self.components_summary(hnum, hstats, int(hole_min_size))
+        _, cnum, _, _, _, _ = self._components(pred, int(cable_cls), 8, k, False)
+        cable = self.components_summary(cnum, None, 0)
+        _, area = self.row_widths(pred, int(tape_cls))
+        tape_area = area[:, 0]
+        areas = torch.zeros((b, len(defect_classes)), dtype=torch.int64, device=pred.device)
+        known = [(i, c) for i, c in enumerate(defect_classes) if 0 <= c < self.num_classes]
+        if known:
+            counts, _ = self.mask_stats(pred)
+            areas[:, [i for i, _ in known]] = counts[:, [c for _, c in known]]
+        fa = tape_area.to(torch.float64)
+        ratio = torch.where(tape[:, 0] > 0, tape[:, 3].to(torch.float64) / fa, torch.zeros_like(fa))
+        return {"tape_hole_ratio": hole[:, 2].to(torch.float64) / tape_area.clamp(min=1).to(torch.float64),
+                "tape_num_holes": hole[:, 1], "tape_coverage": fa / torch.full_like(fa, h * w), "cable_num_components": cable[:, 0],
+                "tape_num_components": tape[:, 0], "tape_largest_area_ratio": ratio, "defect_areas": areas,
+                "total_defect_area": areas.sum(1)}, (tnum > k) | (hnum > k)
+
+    def analyze_defects(self, pred, cable_cls: int = 1, tape_cls: int = 2, defect_classes=(3, 4, 5, 6), hole_min_size: int = 10,
+                        max_components: int = 8192, check: bool = True):
+        """analyze_defects(pred_mask, cable_cls, tape_cls, defect_classes, hole_min_size)
+        (src/utils/geometry_enhanced.py:246-330) for a uint8 CUDA class mask [B,H,W], every step a launch: the hole mask
+        (close(tape, ELLIPSE (5,5)) - tape), the components of tape, holes and cable, components_summary of each, the
+        tape area (row_widths) and the class counts (mask_stats).  Returns a dict of device tensors with DefectAnalysis'
+        field names: tape_hole_ratio (hole area / max(tape area, 1)), tape_coverage, tape_largest_area_ratio (0 without
+        tape) float64 [B]; tape_num_holes, cable_num_components, tape_num_components, total_defect_area int64 [B];
+        defect_areas int64 [B, len(defect_classes)] in the order of defect_classes.  A defect class >= the engine's
+        num_classes has area 0.  The component counts are exact whatever max_components is; the hole statistics and
+        the largest tape area cover the first max_components - 1 labels: check=True (one read-back, synchronises)
+        raises RuntimeError for a frame with more."""
+        k = int(max_components)
+        out, over = self._analyze_defects(pred, cable_cls, tape_cls, defect_classes, hole_min_size, k)
+        if check:
+            self._raise_overflow(over, k, "analyze_defects")
+        return out
+
     # ------------------------------------------------------------------ stage-2 burr detection
     def _edge_input(self, img, what="gray", channels=None):
         """A contiguous uint8 CUDA image batch on the engine's device, with the engine made ready."""

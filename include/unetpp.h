@@ -543,6 +543,51 @@ int unetpp_width_profile(unetpp_engine* e, const float* dev_widths, int batch, i
 int unetpp_components_summary(unetpp_engine* e, const int32_t* dev_num, const int32_t* dev_stats, int batch, int capacity,
                               int64_t min_area, int64_t* dev_out, void* stream);
 
+/* ---- sliding-window inference on the device: gather tiles, gate, blend -------------------------------------------------
+ * SlidingWindowInference.predict (tools/inference_binary_patch.py:19-115) and OptimizedSlidingWindowInference.predict
+ * (tools/inference_binary_optimized.py:21-113) around the network: cut frames into overlapping patch_size squares,
+ * resize each to the network's size t, and fold the network's per-patch maps back into one image.  unet_amd/tiling.py
+ * is the NumPy form and builds the plan.  The plan is separable: patch (i, j) has its top-left corner at
+ * (origins_y[i], origins_x[j]) and index i * n_x + j inside its frame (the reference's loop order); both arrays are in
+ * HOST memory, read during the call, 1 <= n_y, n_x <= 64 (UNETPP_E_UNSUPPORTED above).  All three calls are asynchronous
+ * on `stream`; the first call with a new (patch_size, t) pair builds two small device tables and synchronises once.
+ *
+ * unetpp_tile_gather_u8: dev_frames uint8 [B,h,w,3] -> dev_patches uint8 [B * n_y * n_x, t, t, 3] in one launch:
+ *   crop    source index s of a patch maps to image coordinate origin + s;
+ *   pad     np.pad(mode="reflect") at the bottom and right: a coordinate k >= h reads 2 (h - 1) - k.  Every origin must
+ *           satisfy 0 <= origin < h and origin + patch_size - 1 <= 2 (h - 1) (likewise for w): padding of h or more is
+ *           UNETPP_E_UNSUPPORTED;
+ *   resize  cv2.resize(patch, (t, t), INTER_LINEAR) for uint8, the arithmetic of unetpp_resize_linear_u8; t ==
+ *           patch_size is the identity; t a multiple of 4;
+ *   channel_order  UNETPP_TILE_BGR copies the channels, UNETPP_TILE_RGB reverses them, so that either way the patches
+ *           are BGR, which UNETPP_IN_U8_NHWC_BGR expects.
+ *
+ * unetpp_tile_gate_f32: the window gate (inference_binary_optimized.py:91-98) for dev_maps float32 [n, classes, t, t]:
+ *   dev_scores float32 [n] = the maximum over the patch of class gate_class; dev_include uint8 [n] = score >= gate_thr
+ *   (both float32).  t a multiple of 2, dev_maps 16-byte aligned.
+ *
+ * unetpp_tile_blend_f32: dev_maps float32 [B * n_y * n_x, classes, t, t] -> dev_mask uint8 [B,h,w] and, unless NULL,
+ *   dev_output float32 [B,h,w,classes].  Per pixel, for every patch that covers it (and whose dev_include byte is
+ *   non-zero; dev_include may be NULL), in plan order: the sample of cv2.resize(map, (patch_size, patch_size),
+ *   INTER_LINEAR) at the patch-local coordinate, with float coefficients 1 - fx and fx: horizontal S[s0] * a0 + S[s1] *
+ *   a1 on the two source rows, then the vertical pass, every product and sum rounded to float32; added to a float32
+ *   accumulator per class.  Then acc / (count + 1e-8f) (IEEE division; count is the number of patches added) and the
+ *   first maximum over the classes.  A pixel no included patch covers gives 0 and class 0.  The order is fixed per pixel,
+ *   so there are no atomics and the bits do not depend on scheduling.  1 <= classes <= 8 (UNETPP_E_UNSUPPORTED above).
+ *
+ * Errors: UNETPP_E_INVALID for NULL where not allowed, a bad shape, an origin outside the frame, a bad gate_class or
+ * channel_order.  No kernel is launched when an error is returned. */
+enum { UNETPP_TILE_BGR = 0, UNETPP_TILE_RGB = 1 };
+
+int unetpp_tile_gather_u8(unetpp_engine* e, const uint8_t* dev_frames, int batch, int h, int w, const int32_t* origins_y,
+                          int n_y, const int32_t* origins_x, int n_x, int patch_size, int t, int channel_order,
+                          uint8_t* dev_patches, void* stream);
+int unetpp_tile_gate_f32(unetpp_engine* e, const float* dev_maps, int n, int classes, int t, int gate_class, float gate_thr,
+                         float* dev_scores, uint8_t* dev_include, void* stream);
+int unetpp_tile_blend_f32(unetpp_engine* e, const float* dev_maps, int batch, int classes, int t, const int32_t* origins_y,
+                          int n_y, const int32_t* origins_x, int n_x, int patch_size, const uint8_t* dev_include, int h, int w,
+                          uint8_t* dev_mask, float* dev_output, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunetpp_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["unetpp_abi.hip"]
-HEADERS = ["conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "components.h", "morphology.h", "edges.h", "edges_multi.h", "geometry.h", os.path.join("..", "..", "include", "unetpp.h")]
+HEADERS = ["conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "components.h", "morphology.h", "edges.h", "edges_multi.h", "geometry.h", "tiling.h", os.path.join("..", "..", "include", "unetpp.h")]
 
 # every symbol include/unetpp.h declares
 ABI_SYMBOLS = [
@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "unetpp_laplacian_band_u8", "unetpp_components_filter_box",
     "unetpp_edges_union_workspace_bytes", "unetpp_edges_union_u8", "unetpp_dog_band_u8", "unetpp_count_nonzero_u8",
     "unetpp_row_widths", "unetpp_width_profile", "unetpp_components_summary",
+    "unetpp_tile_gather_u8", "unetpp_tile_gate_f32", "unetpp_tile_blend_f32",
 ]
 
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
@@ -229,6 +230,9 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     lib.unetpp_row_widths.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp]; lib.unetpp_row_widths.restype = ci
     lib.unetpp_width_profile.argtypes = [vp, vp, ci, ci, f32p, ci, ci, vp, vp, vp, vp, vp]; lib.unetpp_width_profile.restype = ci
     lib.unetpp_components_summary.argtypes = [vp, vp, vp, ci, ci, ctypes.c_int64, vp, vp]; lib.unetpp_components_summary.restype = ci
+    lib.unetpp_tile_gather_u8.argtypes = [vp, vp, ci, ci, ci, i32p, ci, i32p, ci, ci, ci, ci, vp, vp]; lib.unetpp_tile_gather_u8.restype = ci
+    lib.unetpp_tile_gate_f32.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_float, vp, vp, vp]; lib.unetpp_tile_gate_f32.restype = ci
+    lib.unetpp_tile_blend_f32.argtypes = [vp, vp, ci, ci, ci, i32p, ci, i32p, ci, ci, vp, ci, ci, vp, vp, vp]; lib.unetpp_tile_blend_f32.restype = ci
     ver = lib.unetpp_version().decode()
     if ver.endswith(" +wsdbg") and os.environ.get("UNETPP_ALLOW_DBG_LIB"):
         ver = ver[:-len(" +wsdbg")]            # measurement build with phase ablations (scripts/ws_ablate.sh)

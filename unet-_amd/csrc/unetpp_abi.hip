@@ -38,6 +38,7 @@
 #include "geometry.h"
 #include "morphology.h"
 #include "tapmm_ws.h"
+#include "tiling.h"
 
 using namespace unetpp;
 
@@ -1866,6 +1867,26 @@ void linear_table(int n_src, int n_dst, std::vector<int>& t) {
     t[4 * d + 0] = s0; t[4 * d + 1] = std::min(s0 + 1, n_src - 1); t[4 * d + 2] = (int)a0; t[4 * d + 3] = (int)a1;
   }
 }
+// The same indices with the float coefficients 1 - fx and fx of the float32 resize (tiling.h): entry = {s0, s1,
+// bits(1 - fx), bits(fx)}.
+void linear_table_f32(int n_src, int n_dst, std::vector<int>& t) {
+#pragma clang fp contract(off)
+  t.resize((size_t)n_dst * 4);
+  const double inv_scale = (double)n_dst / (double)n_src;
+  const double scale = 1.0 / inv_scale;
+  for (int d = 0; d < n_dst; ++d) {
+    float fx = (float)((d + 0.5) * scale - 0.5);
+    int s0 = (int)floorf(fx);
+    fx -= (float)s0;
+    if (s0 < 0) { fx = 0.f; s0 = 0; }
+    if (s0 >= n_src - 1) { fx = 0.f; s0 = n_src - 1; }
+    const float a0 = 1.f - fx;
+    int b0, b1;
+    std::memcpy(&b0, &a0, sizeof b0);
+    std::memcpy(&b1, &fx, sizeof b1);
+    t[4 * d + 0] = s0; t[4 * d + 1] = std::min(s0 + 1, n_src - 1); t[4 * d + 2] = b0; t[4 * d + 3] = b1;
+  }
+}
 // resizeNN's index table: min(floor(d * (1 / (n_dst / n_src))), n_src - 1) in double.
 void nearest_table(int n_src, int n_dst, std::vector<int>& t) {
 #pragma clang fp contract(off)
@@ -1880,7 +1901,7 @@ int resize_table(unetpp_engine* e, int kind, int n_src, int n_dst, void** out) {
   auto it = e->resize_tabs.find(key);
   if (it == e->resize_tabs.end()) {
     std::vector<int> t;
-    if (kind == 0) linear_table(n_src, n_dst, t); else nearest_table(n_src, n_dst, t);
+    if (kind == 0) linear_table(n_src, n_dst, t); else if (kind == 1) nearest_table(n_src, n_dst, t); else linear_table_f32(n_src, n_dst, t);
     void* d = nullptr;
     HIP_TRY(e, hipMalloc(&d, t.size() * sizeof(int)));
     hipError_t r = hipMemcpy(d, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice);
@@ -1928,6 +1949,98 @@ int unetpp_resize_nearest_roi_u8(unetpp_engine* e, const uint8_t* dev_src, int b
   const unsigned gx = (unsigned)((dst_w + 1023) / 1024);
   hipLaunchKernelGGL(resize_nearest_roi_u8_kernel, dim3(gx, (unsigned)dst_h, (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
                      dev_src, src_h, src_w, dev_dst, dst_h, dst_w, (const int*)xo, (const int*)yo, match_class, x1, y1, x2, y2);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+// ---- sliding-window inference: gather tiles, gate, blend (tiling.h) ------------------------------------------
+}  // extern "C"
+namespace {
+// Checks a separable plan against the frame and copies it.  Everything the kernels index with is validated here.
+int tile_plan_check(unetpp_engine* e, int h, int w, const int32_t* oy, int n_y, const int32_t* ox, int n_x, int patch_size,
+                    bool reflect, TilePlan* plan) {
+  if (!oy || !ox) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (h < 1 || w < 1 || h > 65535 || w > 65535 || patch_size < 1 || patch_size > 65535)
+    return fail(e, UNETPP_E_INVALID, "bad shape %dx%d, patch_size %d", h, w, patch_size);
+  if (n_y < 1 || n_x < 1) return fail(e, UNETPP_E_INVALID, "empty plan %dx%d", n_y, n_x);
+  if (n_y > TILE_MAX_AXIS || n_x > TILE_MAX_AXIS)
+    return fail(e, UNETPP_E_UNSUPPORTED, "plan of %dx%d patches: at most %d per axis", n_y, n_x, TILE_MAX_AXIS);
+  plan->ny = n_y; plan->nx = n_x;
+  for (int a = 0; a < 2; ++a) {
+    const int n = a ? w : h, cnt = a ? n_x : n_y;
+    const int32_t* o = a ? ox : oy;
+    for (int i = 0; i < cnt; ++i) {
+      if (o[i] < 0 || o[i] >= n) return fail(e, UNETPP_E_INVALID, "origin %d outside an axis of %d", o[i], n);
+      if (reflect && o[i] + patch_size - 1 > 2 * (n - 1))
+        return fail(e, UNETPP_E_UNSUPPORTED, "patch of %d at %d on an axis of %d: reflect padding of the axis length or more", patch_size, o[i], n);
+      (a ? plan->ox : plan->oy)[i] = o[i];
+    }
+  }
+  return UNETPP_OK;
+}
+}  // namespace
+extern "C" {
+
+int unetpp_tile_gather_u8(unetpp_engine* e, const uint8_t* dev_frames, int batch, int h, int w, const int32_t* origins_y, int n_y,
+                          const int32_t* origins_x, int n_x, int patch_size, int t, int channel_order, uint8_t* dev_patches,
+                          void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_frames || !dev_patches) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (batch < 1 || t < 4 || t % 4 || t > 16384) return fail(e, UNETPP_E_INVALID, "bad batch %d or patch size %d (a multiple of 4)", batch, t);
+  if (channel_order != UNETPP_TILE_BGR && channel_order != UNETPP_TILE_RGB) return fail(e, UNETPP_E_INVALID, "channel_order %d", channel_order);
+  TilePlan plan;
+  int rc = tile_plan_check(e, h, w, origins_y, n_y, origins_x, n_x, patch_size, true, &plan);
+  if (rc) return rc;
+  if ((long long)batch * n_y * n_x > 65535) return fail(e, UNETPP_E_INVALID, "%d x %d x %d patches: at most 65535 per call", batch, n_y, n_x);
+  if ((size_t)h * w * 3 > 0x7fffffffULL) return fail(e, UNETPP_E_INVALID, "frame too large");
+  ENTER_DEVICE(e);
+  void* tab = nullptr;
+  rc = resize_table(e, 0, patch_size, t, &tab); if (rc) return rc;
+  hipLaunchKernelGGL(tile_gather_u8_kernel, dim3((unsigned)((t * 3 + 1023) / 1024), (unsigned)t, (unsigned)(batch * n_y * n_x)),
+                     dim3(TILE_THREADS), 0, (hipStream_t)stream, dev_frames, h, w, plan, t, (int)(channel_order == UNETPP_TILE_RGB),
+                     (const int4*)tab, (const int4*)tab, dev_patches);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_tile_gate_f32(unetpp_engine* e, const float* dev_maps, int n, int classes, int t, int gate_class, float gate_thr,
+                         float* dev_scores, uint8_t* dev_include, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_maps || !dev_scores || !dev_include) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (n < 1 || classes < 1 || t < 2 || t % 2 || t > 16384) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%dx%d", n, classes, t, t);
+  if (gate_class < 0 || gate_class >= classes) return fail(e, UNETPP_E_INVALID, "gate_class %d not in [0,%d)", gate_class, classes);
+  if ((uintptr_t)dev_maps % 16) return fail(e, UNETPP_E_INVALID, "dev_maps must be 16-byte aligned");
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(tile_gate_f32_kernel, dim3((unsigned)n), dim3(TILE_THREADS), 0, (hipStream_t)stream, dev_maps, classes, t, gate_class,
+                     gate_thr, dev_scores, dev_include);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_tile_blend_f32(unetpp_engine* e, const float* dev_maps, int batch, int classes, int t, const int32_t* origins_y, int n_y,
+                          const int32_t* origins_x, int n_x, int patch_size, const uint8_t* dev_include, int h, int w,
+                          uint8_t* dev_mask, float* dev_output, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_maps || !dev_mask) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (batch < 1 || batch > 65535 || classes < 1 || t < 1 || t > 16384) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%dx%d", batch, classes, t, t);
+  if (classes > TILE_MAX_CLASSES) return fail(e, UNETPP_E_UNSUPPORTED, "%d classes: at most %d", classes, TILE_MAX_CLASSES);
+  TilePlan plan;
+  int rc = tile_plan_check(e, h, w, origins_y, n_y, origins_x, n_x, patch_size, false, &plan);
+  if (rc) return rc;
+  ENTER_DEVICE(e);
+  void* tab = nullptr;
+  rc = resize_table(e, 2, t, patch_size, &tab); if (rc) return rc;
+  const dim3 grid((unsigned)((w + TILE_WAVE - 1) / TILE_WAVE), (unsigned)((h + TILE_BLEND_ROWS - 1) / TILE_BLEND_ROWS), (unsigned)batch);
+#define TILE_BLEND_CASE(C)                                                                                                       \
+  case C:                                                                                                                        \
+    hipLaunchKernelGGL(tile_blend_f32_kernel<C>, grid, dim3(TILE_THREADS), 0, (hipStream_t)stream, dev_maps, plan, patch_size, t, \
+                       (const int4*)tab, (const int4*)tab, dev_include, h, w, dev_mask, dev_output);                             \
+    break
+  switch (classes) {
+    TILE_BLEND_CASE(1); TILE_BLEND_CASE(2); TILE_BLEND_CASE(3); TILE_BLEND_CASE(4);
+    TILE_BLEND_CASE(5); TILE_BLEND_CASE(6); TILE_BLEND_CASE(7); TILE_BLEND_CASE(8);
+  }
+#undef TILE_BLEND_CASE
   HIP_TRY(e, hipGetLastError());
   return UNETPP_OK;
 }

@@ -1178,6 +1178,153 @@ class NestedUNet:
         deep-supervision output k, from a pruned pass (see forward)."""
         return self._run(x, False, False, False, True, output=output)[4]
 
+    # ------------------------------------------------------------------ sliding-window inference (unet_amd/tiling.py is the NumPy form)
+    @staticmethod
+    def _c_origins(plan):
+        ys, xs = np.asarray(plan.ys, np.int32), np.asarray(plan.xs, np.int32)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        return ys, xs, ys.ctypes.data_as(i32p), xs.ctypes.data_as(i32p)
+
+    @staticmethod
+    def _check_plan(plan, h, w, patch_size):
+        from . import tiling as tl
+        if plan.n_patches == 0:
+            raise ValueError(f"the plan for {h}x{w} at patch_size {patch_size} has no patch")
+        if len(plan.ys) > tl.MAX_AXIS or len(plan.xs) > tl.MAX_AXIS:
+            raise ValueError(f"unsupported: a plan of {len(plan.ys)}x{len(plan.xs)} patches, at most {tl.MAX_AXIS} per axis")
+
+    def _check_target_size(self, target_size):
+        t = int(target_size)
+        if t < self._SIZE_MULTIPLE or t % self._SIZE_MULTIPLE:
+            raise ValueError(f"target_size must be a positive multiple of {self._SIZE_MULTIPLE}, got {target_size!r}")
+        return t
+
+    def gather_tiles(self, frames, patch_size: int = 384, stride: int = 192, target_size: int = 256, channel_order: str = "rgb"):
+        """The patch batch of SlidingWindowInference.predict (tools/inference_binary_patch.py:56-82) for uint8 CUDA frames
+        [B,H,W,3], in one launch: crop at tiling.tile_plan's origins, reflect padding at the bottom and right, cv2's uint8
+        INTER_LINEAR resize to target_size.  Returns uint8 [B * P, T, T, 3] (frame-major, plan order inside a frame) in
+        BGR, what forward / segment / predict_proba take: channel_order="rgb" (the reference's predict gets RGB frames)
+        reverses the channels, "bgr" keeps them."""
+        import torch
+        from . import tiling as tl
+        if channel_order not in tl.CHANNEL_ORDERS:
+            raise ValueError(f"channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
+        t = self._check_target_size(target_size)
+        frames = self._edge_input(frames, "frames", 3)
+        b, h, w, _ = frames.shape
+        plan = tl.tile_plan(h, w, patch_size, stride)
+        self._check_plan(plan, h, w, patch_size)
+        tl.check_padding(h, w, int(patch_size))
+        ys, xs, pys, pxs = self._c_origins(plan)
+        out = torch.empty((b * plan.n_patches, t, t, 3), dtype=torch.uint8, device=frames.device)
+        rc = _lib.load().unetpp_tile_gather_u8(self._handle, ctypes.c_void_p(frames.data_ptr()), b, h, w, pys, len(ys), pxs, len(xs),
+                                               int(patch_size), t, tl.CHANNEL_ORDERS[channel_order], ctypes.c_void_p(out.data_ptr()),
+                                               self._stream(frames))
+        if rc != 0:
+            self._raise(rc)
+        return out
+
+    def _check_maps(self, maps):
+        import torch
+        if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.float32 and maps.dim() == 4 and
+                maps.shape[2] == maps.shape[3]):
+            raise RuntimeError("maps must be a float32 CUDA tensor [N,C,T,T]")
+        if self._device_index is None:
+            self.to(maps.device)
+        if maps.device.index != self._device_index:
+            raise RuntimeError(f"maps on {maps.device}, engine on cuda:{self._device_index}")
+        self._ensure_engine(1, self._SIZE_MULTIPLE, self._SIZE_MULTIPLE)
+        return maps.contiguous()
+
+    def tile_gate(self, maps, gate_thr, gate_class: int = 1):
+        """The window gate of OptimizedSlidingWindowInference.predict (tools/inference_binary_optimized.py:91-98) for
+        probability maps float32 CUDA [N,C,T,T]: (include uint8 [N] = score >= gate_thr, scores float32 [N] = the maximum
+        of class gate_class over the patch), one launch, nothing read back."""
+        import torch
+        maps = self._check_maps(maps)
+        n, c, t, _ = maps.shape
+        if not 0 <= int(gate_class) < c:
+            raise ValueError(f"gate_class {gate_class} not in [0,{c})")
+        scores = torch.empty((n,), dtype=torch.float32, device=maps.device)
+        include = torch.empty((n,), dtype=torch.uint8, device=maps.device)
+        rc = _lib.load().unetpp_tile_gate_f32(self._handle, ctypes.c_void_p(maps.data_ptr()), n, c, t, int(gate_class), float(gate_thr),
+                                              ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(include.data_ptr()), self._stream(maps))
+        if rc != 0:
+            self._raise(rc)
+        return include, scores
+
+    def blend_tiles(self, maps, frame_hw, patch_size: int = 384, stride: int = 192, include=None, return_output: bool = True):
+        """The fold of predict (tools/inference_binary_patch.py:98-113) for per-patch maps float32 CUDA [B * P, C, T, T] of
+        B frames of frame_hw = (H, W), in one launch: each map resized to patch_size (float32 INTER_LINEAR), cropped, summed
+        in plan order, divided by count + 1e-8, argmax.  `include` uint8 CUDA [B * P] (tile_gate) drops patches.  Returns
+        (mask uint8 [B,H,W], output float32 [B,H,W,C] or None)."""
+        import torch
+        from . import tiling as tl
+        h, w = int(frame_hw[0]), int(frame_hw[1])
+        plan = tl.tile_plan(h, w, patch_size, stride)
+        self._check_plan(plan, h, w, patch_size)
+        maps = self._check_maps(maps)
+        n, c, t, _ = maps.shape
+        if n % plan.n_patches:
+            raise RuntimeError(f"maps hold {n} patches, the plan for {h}x{w} has {plan.n_patches} per frame")
+        if c > tl.MAX_CLASSES:
+            raise ValueError(f"unsupported: {c} classes, at most {tl.MAX_CLASSES}")
+        b = n // plan.n_patches
+        if include is not None:
+            if not (isinstance(include, torch.Tensor) and include.is_cuda and include.dtype == torch.uint8 and tuple(include.shape) == (n,)):
+                raise RuntimeError(f"include must be a uint8 CUDA tensor [{n}]")
+            include = include.contiguous()
+        ys, xs, pys, pxs = self._c_origins(plan)
+        mask = torch.empty((b, h, w), dtype=torch.uint8, device=maps.device)
+        output = torch.empty((b, h, w, c), dtype=torch.float32, device=maps.device) if return_output else None
+        p = lambda x: ctypes.c_void_p(x.data_ptr()) if x is not None else None
+        rc = _lib.load().unetpp_tile_blend_f32(self._handle, p(maps), b, c, t, pys, len(ys), pxs, len(xs), int(patch_size), p(include),
+                                               h, w, p(mask), p(output), self._stream(maps))
+        if rc != 0:
+            self._raise(rc)
+        return mask, output
+
+    def predict_tiled(self, frames, patch_size: int = 384, stride: int = 192, target_size: int = 256, blend: str = "logits",
+                      gate_thr=None, gate_class: int = 1, channel_order: str = "rgb", return_output: bool = True):
+        """SlidingWindowInference.predict (tools/inference_binary_patch.py:36-115; blend="logits") or
+        OptimizedSlidingWindowInference.predict (tools/inference_binary_optimized.py:40-113; blend="probs", softmax maps,
+        gate_thr=None is use_gating=False) for uint8 CUDA frames [B,H,W,3] of any size, without leaving the device:
+        gather_tiles, the network on the patches of all frames in chunks of at most max_batch, tile_gate, blend_tiles.
+        Returns (mask uint8 [B,H,W], output float32 [B,H,W,C] or None); a plan with no patch gives zeros, as the
+        reference does."""
+        import torch
+        from . import tiling as tl
+        if blend not in tl.BLENDS:
+            raise ValueError(f"blend must be 'logits' or 'probs', got {blend!r}")
+        if gate_thr is not None and blend != "probs":
+            raise ValueError("gate_thr needs blend='probs': the gate score is a probability")
+        if channel_order not in tl.CHANNEL_ORDERS:
+            raise ValueError(f"channel_order must be 'rgb' or 'bgr', got {channel_order!r}")
+        t = self._check_target_size(target_size)
+        frames = self._edge_input(frames, "frames", 3)
+        b, h, w, _ = frames.shape
+        c, dev = self.num_classes, frames.device
+        plan = tl.tile_plan(h, w, patch_size, stride)
+        if plan.n_patches == 0:
+            return (torch.zeros((b, h, w), dtype=torch.uint8, device=dev),
+                    torch.zeros((b, h, w, c), dtype=torch.float32, device=dev) if return_output else None)
+        patches = self.gather_tiles(frames, patch_size, stride, t, channel_order)
+        n = patches.shape[0]
+        maps = torch.empty((n, c, t, t), dtype=torch.float32, device=dev)
+        step = max(1, self._max_batch)
+        for k in range(0, n, step):                 # the engine writes each chunk's maps into its slice: no copy
+            x, fmt, nb, _, _ = self._prepare(patches[k:k + step])
+            dst = ctypes.c_void_p(maps[k:k + nb].data_ptr())
+            outs = _lib.Outputs(dst if blend == "logits" else None, dst if blend == "probs" else None, None, None, None,
+                                _lib.RULES["argmax"], 0.0, 0.0, 0.0, 0.0)
+            rc = _lib.load().unetpp_forward_ex(self._handle, ctypes.c_void_p(x.data_ptr()), fmt, nb, t, t, ctypes.byref(outs), self._stream(x))
+            if rc != 0:
+                raise RuntimeError(self._err(rc))
+        if self._check_range:
+            self.raise_on_range_error()
+        include = None if gate_thr is None else self.tile_gate(maps, gate_thr, gate_class)[0]
+        return self.blend_tiles(maps, (h, w), patch_size, stride, include, return_output)
+
     # ------------------------------------------------------------------ measurement / debug hooks
     def workspace_bytes(self) -> int:
         return int(_lib.load().unetpp_workspace_bytes(self._handle)) if self._handle else 0

@@ -588,6 +588,72 @@ int unetpp_tile_blend_f32(unetpp_engine* e, const float* dev_maps, int batch, in
                           int n_y, const int32_t* origins_x, int n_x, int patch_size, const uint8_t* dev_include, int h, int w,
                           uint8_t* dev_mask, float* dev_output, void* stream);
 
+/* ---- grey-frame enhancement in front of the network: decision, CLAHE, gamma, bilateral filter --------------------------
+ * preprocess_frame of the refactored loop (src/refactor/preprocess.py:12-91, infer_video_refactored.py:346) with
+ * PreprocessConfig's defaults (src/refactor/config.py:44-52): is_grayscale_frame, then for a grey frame
+ * cv2.cvtColor(BGR2GRAY), cv2.createCLAHE(clip, (tiles, tiles)).apply, a 256-entry gamma table, cv2.bilateralFilter(d, 75,
+ * 75) and GRAY2BGR; a colour frame is copied.  unet_amd/enhance.py is the NumPy form, restated from OpenCV's published
+ * algorithms, and every result equals it bit for bit; cv2's own results are not pinned by this project's tests.
+ * Images uint8 on the device, 1 <= h, w <= 65535, h * w <= 2^30.  Everything is asynchronous on `stream`, allocates
+ * nothing and never synchronises with the host: the grey / colour decision stays on the device.
+ *
+ * unetpp_gray_decision: dev_frames uint8 [B,h,w,3] -> dev_sums uint64 [B,3] = the sums of |b - g|, |g - r|, |r - b|
+ *   (8-byte aligned; zeroed by the call) and dev_decisions uint8 [B] = (max(sums) / (h w) < threshold), one double
+ *   division of exact integers: what np.abs(...).mean() < threshold yields.
+ *
+ * unetpp_clahe_u8: OpenCV's CLAHE_Impl::apply for dev_gray uint8 [B,h,w] -> dev_out.  1 <= tiles_x, tiles_y <= 16,
+ *   h > tiles_y, w > tiles_x.  When the grid does not divide BOTH extents the histograms come from the image extended
+ *   with BORDER_REFLECT_101 by tiles_y - h % tiles_y rows and tiles_x - w % tiles_x columns (a whole extra `tiles` in
+ *   an extent that does divide: OpenCV's quirk, kept).  Per tile: clip = max((int)(clip_limit * tileArea / 256), 1)
+ *   (clip_limit <= 0: none), the excess redistributed as OpenCV does, lut[i] = saturate(rint(float(cumsum_i) * (255.f /
+ *   tileArea))).  Per pixel: the bilinear blend of the four surrounding tiles' tables in float32, no contraction.
+ *   dev_luts: NULL, or uint8 [B, tiles_y * tiles_x, 256] (4-byte aligned) that receives the tables.
+ *
+ * unetpp_bilateral_u8: cv2.bilateralFilter's scalar 8-bit loop for dev_gray uint8 [B,h,w] -> dev_out (may not alias),
+ *   BORDER_REFLECT_101, h, w > radius.  `tables` (HOST memory, read during the call): radius 1..4, n_taps offsets
+ *   (dy[k], dx[k]) within the radius, their space weights, 256 colour weights.  Per pixel, over the taps in table order,
+ *   float32 without contraction: w = space_w[k] * color_w[|val - val0|]; sum += val * w; wsum += w; out = rint(sum /
+ *   wsum) with IEEE division.
+ *
+ * unetpp_enhance_u8: the fused sequence, three launches and one memset.  dev_frames uint8 [B,h,w,channels_in]
+ *   (3: BGR, converted with unetpp_gray_u8's constants; 1: grey) -> dev_out uint8 [B,h,w,channels_out] (3: the grey value
+ *   replicated).  mode UNETPP_ENHANCE_ALWAYS enhances every frame (enhance_grayscale_frame); UNETPP_ENHANCE_IF_GREY
+ *   enhances the frames whose decision (as unetpp_gray_decision, `threshold`) is 1 and copies the others
+ *   (preprocess_frame; channels_out must be 3 for 3-channel input; a 1-channel frame always counts as grey).
+ *   gamma_table: NULL, or 256 bytes in HOST memory applied after CLAHE.  tables: NULL (no filter), or as above.
+ *   dev_luts as for unetpp_clahe_u8; dev_decisions: NULL, or uint8 [B] that receives the decisions (1 for every frame
+ *   in UNETPP_ENHANCE_ALWAYS).  dev_workspace: unetpp_enhance_workspace_bytes(batch, h, w, tiles_x, tiles_y) bytes (0
+ *   for a shape or grid outside the limits), 16-byte aligned; also needed by unetpp_clahe_u8.  dev_out may not overlap
+ *   dev_frames.
+ *
+ * unetpp_enhance_layout: the core rows and columns of one workgroup of the last launch (tests place seams with it).
+ *
+ * Errors: UNETPP_E_UNSUPPORTED for a shape, grid or radius outside the limits; UNETPP_E_INVALID for NULL where not
+ * allowed, bad channels or mode, a tap outside the radius, a weight that is negative or not finite, misalignment,
+ * overlap.  No kernel is launched when an error is returned. */
+typedef struct unetpp_bilateral_tables {
+  int32_t radius, n_taps;
+  const float* color_w;      /* [256] */
+  const float* space_w;      /* [n_taps] */
+  const int32_t* dy;         /* [n_taps] */
+  const int32_t* dx;         /* [n_taps] */
+} unetpp_bilateral_tables;
+
+enum { UNETPP_ENHANCE_ALWAYS = 0, UNETPP_ENHANCE_IF_GREY = 1 };
+
+size_t unetpp_enhance_workspace_bytes(int batch, int h, int w, int tiles_x, int tiles_y);
+int unetpp_enhance_layout(int* tile_rows, int* tile_cols);
+int unetpp_gray_decision(unetpp_engine* e, const uint8_t* dev_frames, int batch, int h, int w, double threshold,
+                         uint8_t* dev_decisions, uint64_t* dev_sums, void* stream);
+int unetpp_clahe_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h, int w, double clip_limit, int tiles_x,
+                    int tiles_y, uint8_t* dev_out, uint8_t* dev_luts, void* dev_workspace, void* stream);
+int unetpp_bilateral_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h, int w,
+                        const unetpp_bilateral_tables* tables, uint8_t* dev_out, void* stream);
+int unetpp_enhance_u8(unetpp_engine* e, const uint8_t* dev_frames, int batch, int h, int w, int channels_in, int channels_out,
+                      int mode, double threshold, double clip_limit, int tiles_x, int tiles_y, const uint8_t* gamma_table,
+                      const unetpp_bilateral_tables* tables, uint8_t* dev_out, uint8_t* dev_luts, uint8_t* dev_decisions,
+                      void* dev_workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunetpp_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["unetpp_abi.hip"]
-HEADERS = ["conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "components.h", "morphology.h", "edges.h", "edges_multi.h", "geometry.h", "tiling.h", os.path.join("..", "..", "include", "unetpp.h")]
+HEADERS = ["conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "components.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "geometry.h", "tiling.h", os.path.join("..", "..", "include", "unetpp.h")]
 
 # every symbol include/unetpp.h declares
 ABI_SYMBOLS = [
@@ -32,6 +32,8 @@ ABI_SYMBOLS = [
     "unetpp_edges_union_workspace_bytes", "unetpp_edges_union_u8", "unetpp_dog_band_u8", "unetpp_count_nonzero_u8",
     "unetpp_row_widths", "unetpp_width_profile", "unetpp_components_summary",
     "unetpp_tile_gather_u8", "unetpp_tile_gate_f32", "unetpp_tile_blend_f32",
+    "unetpp_gray_decision", "unetpp_clahe_u8", "unetpp_bilateral_u8", "unetpp_enhance_u8", "unetpp_enhance_workspace_bytes",
+    "unetpp_enhance_layout",
 ]
 
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
@@ -72,6 +74,13 @@ class MorphStep(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("op", "dst", "a", "b", "element", "iterations")]
 
 
+class BilateralTables(ctypes.Structure):
+    """unetpp_bilateral_tables: the weights and taps of the bilateral filter, all in host memory."""
+    _fields_ = [("radius", ctypes.c_int32), ("n_taps", ctypes.c_int32), ("color_w", ctypes.POINTER(ctypes.c_float)),
+                ("space_w", ctypes.POINTER(ctypes.c_float)), ("dy", ctypes.POINTER(ctypes.c_int32)), ("dx", ctypes.POINTER(ctypes.c_int32))]
+
+
+ENHANCE_ALWAYS, ENHANCE_IF_GREY = 0, 1
 MORPH_OPS = {"dilate": 0, "erode": 1, "and": 2, "andnot": 3, "or": 4, "copy": 5}
 RULES = {"argmax": 0, "thresholded_argmax": 1, "strict_bg_check": 2, "exclusive": 3}
 
@@ -233,6 +242,14 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     lib.unetpp_tile_gather_u8.argtypes = [vp, vp, ci, ci, ci, i32p, ci, i32p, ci, ci, ci, ci, vp, vp]; lib.unetpp_tile_gather_u8.restype = ci
     lib.unetpp_tile_gate_f32.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_float, vp, vp, vp]; lib.unetpp_tile_gate_f32.restype = ci
     lib.unetpp_tile_blend_f32.argtypes = [vp, vp, ci, ci, ci, i32p, ci, i32p, ci, ci, vp, ci, ci, vp, vp, vp]; lib.unetpp_tile_blend_f32.restype = ci
+    btp, u8p = ctypes.POINTER(BilateralTables), ctypes.POINTER(ctypes.c_uint8)
+    lib.unetpp_gray_decision.argtypes = [vp, vp, ci, ci, ci, cd, vp, vp, vp]; lib.unetpp_gray_decision.restype = ci
+    lib.unetpp_clahe_u8.argtypes = [vp, vp, ci, ci, ci, cd, ci, ci, vp, vp, vp, vp]; lib.unetpp_clahe_u8.restype = ci
+    lib.unetpp_bilateral_u8.argtypes = [vp, vp, ci, ci, ci, btp, vp, vp]; lib.unetpp_bilateral_u8.restype = ci
+    lib.unetpp_enhance_u8.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cd, cd, ci, ci, u8p, btp, vp, vp, vp, vp, vp]
+    lib.unetpp_enhance_u8.restype = ci
+    lib.unetpp_enhance_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]; lib.unetpp_enhance_workspace_bytes.restype = cs
+    lib.unetpp_enhance_layout.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci)]; lib.unetpp_enhance_layout.restype = ci
     ver = lib.unetpp_version().decode()
     if ver.endswith(" +wsdbg") and os.environ.get("UNETPP_ALLOW_DBG_LIB"):
         ver = ver[:-len(" +wsdbg")]            # measurement build with phase ablations (scripts/ws_ablate.sh)

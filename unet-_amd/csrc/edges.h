@@ -255,14 +255,16 @@ __global__ void __launch_bounds__(ED_THREADS) laplacian_band_kernel(const uint8_
   }
 }
 
-// cv2.cvtColor(BGR2GRAY) of OpenCV 4 for uint8: (3735 B + 19235 G + 9798 R + 16384) >> 15.  One thread per pixel;
-// grid (ceil(HW / 256), B).
+// cv2.cvtColor(BGR2GRAY) of OpenCV 4 for uint8: (3735 B + 19235 G + 9798 R + 16384) >> 15 (also enhance.h)
+__device__ __forceinline__ int gray_of_bgr(int b, int g, int r) { return (3735 * b + 19235 * g + 9798 * r + 16384) >> 15; }
+
+// One thread per pixel; grid (ceil(HW / 256), B).
 __global__ void __launch_bounds__(ED_THREADS) gray_kernel(const uint8_t* __restrict__ bgr, int HW, uint8_t* __restrict__ out) {
   const int i = blockIdx.x * ED_THREADS + threadIdx.x;
   if (i >= HW) return;
   const size_t p = (size_t)blockIdx.y * HW + i;
   const uint8_t* s = bgr + p * 3;
-  out[p] = (uint8_t)((3735 * (int)s[0] + 19235 * (int)s[1] + 9798 * (int)s[2] + 16384) >> 15);
+  out[p] = (uint8_t)gray_of_bgr(s[0], s[1], s[2]);
 }
 
 }  // namespace unetpp

@@ -35,6 +35,7 @@
 #include "convt2x2_mfma.h"
 #include "edges.h"
 #include "edges_multi.h"
+#include "enhance.h"
 #include "geometry.h"
 #include "morphology.h"
 #include "tapmm_ws.h"
@@ -236,12 +237,12 @@ struct LaunchCtx { int device; int num_cus; int ksplit_max = 1, ksplit_min_chunk
 // The conv kernels take more dynamic LDS than the 64 KiB default: raise the function's limit to the whole 160 KiB
 // once per (device, kernel).  The attribute is process-wide state of the HIP runtime and engines may be driven
 // from several threads, so the bookkeeping is locked and the value is the same constant for everybody.
-hipError_t allow_full_lds(const void* kernel, int device) {
+hipError_t allow_full_lds(const void* kernel, int device, int bytes = 160 * 1024) {
   static std::mutex mu;
   static std::set<std::pair<int, const void*>> done;
   std::lock_guard<std::mutex> lock(mu);
   if (done.count({device, kernel})) return hipSuccess;
-  hipError_t st = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipError_t st = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (st == hipSuccess) done.insert({device, kernel});
   return st;
 }
@@ -1694,6 +1695,200 @@ int unetpp_components_summary(unetpp_engine* e, const int32_t* dev_num, const in
                      (const int*)dev_stats, capacity, (long long)min_area, (long long*)dev_out);
   HIP_TRY(e, hipGetLastError());
   return UNETPP_OK;
+}
+
+// ---- grey-frame enhancement: decision, CLAHE, gamma, bilateral filter (enhance.h) ---------------------------------------
+}  // extern "C"
+namespace {
+struct EnhWorkspace { size_t gray, hist, sums, luts, decisions, total; };
+
+bool enh_shape_ok(int batch, int h, int w) {
+  return batch >= 1 && batch <= 65535 && h >= 1 && w >= 1 && h <= 65535 && w <= 65535 && (size_t)h * w <= (1u << 30);
+}
+// CLAHE_Impl::apply's geometry (enhance.clahe_geometry); false outside 1 <= tiles <= 16, h > tiles_y, w > tiles_x
+bool enh_grid(int h, int w, int tiles_x, int tiles_y, EnhGrid* g) {
+  if (tiles_x < 1 || tiles_y < 1 || tiles_x > EN_MAX_GRID || tiles_y > EN_MAX_GRID || h <= tiles_y || w <= tiles_x) return false;
+  const bool divides = w % tiles_x == 0 && h % tiles_y == 0;
+  g->tiles_x = tiles_x; g->tiles_y = tiles_y;
+  g->ext_w = divides ? w : w + tiles_x - w % tiles_x;
+  g->ext_h = divides ? h : h + tiles_y - h % tiles_y;
+  g->tw = g->ext_w / tiles_x; g->th = g->ext_h / tiles_y;
+  return true;
+}
+bool enh_layout(int batch, int h, int w, int tiles_x, int tiles_y, EnhWorkspace* ws) {
+  EnhGrid g;
+  if (!enh_shape_ok(batch, h, w) || !enh_grid(h, w, tiles_x, tiles_y, &g)) return false;
+  const size_t tiles = (size_t)tiles_x * tiles_y;
+  ws->gray = 0;
+  ws->hist = align_up((size_t)batch * h * w, 256);
+  ws->sums = ws->hist + (size_t)batch * tiles * 256 * sizeof(unsigned);       // directly behind: one memset clears both
+  ws->luts = align_up(ws->sums + (size_t)batch * 3 * sizeof(unsigned long long), 256);
+  ws->decisions = ws->luts + (size_t)batch * tiles * 256;
+  ws->total = align_up(ws->decisions + (size_t)batch, 256);
+  return true;
+}
+// Everything the apply kernel indexes its LDS with is checked here.  tables == NULL: no filter.
+int enh_tables(unetpp_engine* e, const uint8_t* gamma_table, const unetpp_bilateral_tables* tables, int h, int w, EnhTables* T) {
+  std::memset(T, 0, sizeof *T);
+  if (gamma_table) { std::memcpy(T->gamma, gamma_table, 256); T->has_gamma = 1; }
+  if (!tables) return UNETPP_OK;
+  if (!tables->color_w || !tables->space_w || !tables->dy || !tables->dx) return fail(e, UNETPP_E_INVALID, "bilateral tables: null array");
+  const int r = tables->radius, n = tables->n_taps;
+  if (r < 1 || r > EN_MAX_R) return fail(e, UNETPP_E_UNSUPPORTED, "bilateral radius %d: 1..%d", r, EN_MAX_R);
+  if (h <= r || w <= r) return fail(e, UNETPP_E_UNSUPPORTED, "image %dx%d: needs h, w > radius %d", h, w, r);
+  if (n < 1 || n > (2 * r + 1) * (2 * r + 1)) return fail(e, UNETPP_E_INVALID, "bilateral n_taps %d: 1..%d", n, (2 * r + 1) * (2 * r + 1));
+  for (int k = 0; k < n; ++k) {
+    if (std::abs(tables->dy[k]) > r || std::abs(tables->dx[k]) > r) return fail(e, UNETPP_E_INVALID, "bilateral tap %d lies outside the radius %d", k, r);
+    if (!std::isfinite(tables->space_w[k]) || tables->space_w[k] < 0) return fail(e, UNETPP_E_INVALID, "bilateral space weight %d is not finite and non-negative", k);
+    T->space_w[k] = tables->space_w[k]; T->dy[k] = (signed char)tables->dy[k]; T->dx[k] = (signed char)tables->dx[k];
+  }
+  for (int i = 0; i < 256; ++i) {
+    if (!std::isfinite(tables->color_w[i]) || tables->color_w[i] < 0) return fail(e, UNETPP_E_INVALID, "bilateral colour weight %d is not finite and non-negative", i);
+    T->color_w[i] = tables->color_w[i];
+  }
+  T->n_taps = n; T->radius = r;
+  return UNETPP_OK;
+}
+bool enh_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const char* p = (const char*)a; const char* q = (const char*)b;
+  return p < q + nb && q < p + na;
+}
+void enh_launch_stats(hipStream_t s, const uint8_t* src, int batch, int h, int w, int cin, const EnhGrid& g, uint8_t* gray, unsigned* hist,
+                      unsigned long long* sums) {
+  const int area = g.tw * g.th;
+  const dim3 grid((unsigned)((area + EN_CHUNK - 1) / EN_CHUNK), (unsigned)(g.tiles_x * g.tiles_y), (unsigned)batch);
+  hipLaunchKernelGGL(enhance_stats_kernel, grid, dim3(EN_THREADS), 0, s, src, h, w, cin, g, gray, hist, sums);
+}
+// clip_limit * tileArea / 256 in double, truncated, at least 1; 0 = no clipping.  A clip of tileArea or more clips nothing.
+int enh_clip(double clip_limit, int area) {
+  if (!(clip_limit > 0)) return 0;
+  const double c = clip_limit * area / 256;
+  return c >= (double)area ? area : std::max((int)c, 1);
+}
+int enh_launch_apply(unetpp_engine* e, hipStream_t s, const uint8_t* gray, const uint8_t* luts, const uint8_t* decisions, const uint8_t* frames,
+                     int batch, int h, int w, const EnhGrid* g, int cin, int cout, const EnhTables& T, uint8_t* out) {
+  EnhApplyArgs A;
+  std::memset(&A, 0, sizeof A);
+  size_t lds = 0;
+  if (g) {
+    A.g = *g; A.do_clahe = 1;
+    // tiles a window of EN_TH + 2 r rows can touch: ceil(span / th) + 2 (enhance.h), never more than the grid has
+    A.lut_rows = std::min(g->tiles_y, (EN_TH + 2 * T.radius + g->th - 1) / g->th + 2);
+    A.lut_cols = std::min(g->tiles_x, (EN_TW + 2 * T.radius + g->tw - 1) / g->tw + 2);
+    lds = (size_t)A.lut_rows * A.lut_cols * 256;
+  } else {
+    A.g.tiles_x = A.g.tiles_y = A.g.tw = A.g.th = 1;
+  }
+  A.cin = cin; A.cout = cout;
+  A.vec = w % 4 == 0 && (uintptr_t)out % 4 == 0;
+  // the kernel has static LDS too, so the limit asked for is the largest dynamic part (the whole 16 x 16 grid), not all 160 KiB
+  if (lds > 32 * 1024) HIP_TRY(e, allow_full_lds((const void*)enhance_apply_kernel, e->cfg.device, EN_MAX_GRID * EN_MAX_GRID * 256));
+  const dim3 grid((unsigned)((w + EN_TW - 1) / EN_TW), (unsigned)((h + EN_TH - 1) / EN_TH), (unsigned)batch);
+  hipLaunchKernelGGL(enhance_apply_kernel, grid, dim3(EN_THREADS), lds, s, gray, luts, decisions, frames, h, w, A, T, out);
+  return UNETPP_OK;
+}
+}  // namespace
+extern "C" {
+
+size_t unetpp_enhance_workspace_bytes(int batch, int h, int w, int tiles_x, int tiles_y) {
+  EnhWorkspace ws;
+  return enh_layout(batch, h, w, tiles_x, tiles_y, &ws) ? ws.total : 0;
+}
+
+int unetpp_enhance_layout(int* tile_rows, int* tile_cols) {
+  if (!tile_rows || !tile_cols) return fail(nullptr, UNETPP_E_INVALID, "null argument");
+  *tile_rows = EN_TH;
+  *tile_cols = EN_TW;
+  return UNETPP_OK;
+}
+
+int unetpp_gray_decision(unetpp_engine* e, const uint8_t* dev_frames, int batch, int h, int w, double threshold, uint8_t* dev_decisions,
+                         uint64_t* dev_sums, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_frames || !dev_decisions || !dev_sums) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (!enh_shape_ok(batch, h, w)) return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  if ((uintptr_t)dev_sums % 8) return fail(e, UNETPP_E_INVALID, "dev_sums must be 8-byte aligned");
+  if (threshold != threshold) return fail(e, UNETPP_E_INVALID, "threshold is not a number");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  EnhGrid g{1, 1, w, h, h, w};                               // one tile: the image
+  HIP_TRY(e, hipMemsetAsync(dev_sums, 0, (size_t)batch * 3 * sizeof(uint64_t), s));
+  enh_launch_stats(s, dev_frames, batch, h, w, 3, g, nullptr, nullptr, (unsigned long long*)dev_sums);
+  hipLaunchKernelGGL(enhance_decide_kernel, dim3((unsigned)((batch + EN_THREADS - 1) / EN_THREADS)), dim3(EN_THREADS), 0, s,
+                     (const unsigned long long*)dev_sums, batch, (double)h * (double)w, threshold, dev_decisions);
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_bilateral_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h, int w, const unetpp_bilateral_tables* tables,
+                        uint8_t* dev_out, void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_gray || !dev_out || !tables) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (!enh_shape_ok(batch, h, w)) return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  EnhTables T;
+  const int rc = enh_tables(e, nullptr, tables, h, w, &T);
+  if (rc != UNETPP_OK) return rc;
+  const size_t n = (size_t)batch * h * w;
+  if (enh_overlap(dev_gray, n, dev_out, n)) return fail(e, UNETPP_E_INVALID, "dev_out aliases dev_gray: workgroups read halo pixels their neighbours write");
+  ENTER_DEVICE(e);
+  const int lrc = enh_launch_apply(e, (hipStream_t)stream, dev_gray, nullptr, nullptr, nullptr, batch, h, w, nullptr, 1, 1, T, dev_out);
+  if (lrc != UNETPP_OK) return lrc;
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_enhance_u8(unetpp_engine* e, const uint8_t* dev_frames, int batch, int h, int w, int channels_in, int channels_out, int mode,
+                      double threshold, double clip_limit, int tiles_x, int tiles_y, const uint8_t* gamma_table,
+                      const unetpp_bilateral_tables* tables, uint8_t* dev_out, uint8_t* dev_luts, uint8_t* dev_decisions, void* dev_workspace,
+                      void* stream) {
+  if (!e) return UNETPP_E_INVALID;
+  if (!dev_frames || !dev_out || !dev_workspace) return fail(e, UNETPP_E_INVALID, "null argument");
+  if ((channels_in != 1 && channels_in != 3) || (channels_out != 1 && channels_out != 3))
+    return fail(e, UNETPP_E_INVALID, "channels %d -> %d: each 1 or 3", channels_in, channels_out);
+  if (mode != UNETPP_ENHANCE_ALWAYS && mode != UNETPP_ENHANCE_IF_GREY) return fail(e, UNETPP_E_INVALID, "unknown mode %d", mode);
+  if (mode == UNETPP_ENHANCE_IF_GREY && channels_in == 3 && channels_out != 3)
+    return fail(e, UNETPP_E_INVALID, "UNETPP_ENHANCE_IF_GREY copies colour frames through: channels_out must be 3");
+  if (threshold != threshold || clip_limit != clip_limit) return fail(e, UNETPP_E_INVALID, "threshold or clip_limit is not a number");
+  EnhWorkspace ws;
+  if (!enh_layout(batch, h, w, tiles_x, tiles_y, &ws))
+    return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d with a %dx%d grid outside 1 <= tiles <= 16, h > tiles_y, w > tiles_x, h, w <= 65535, h * w <= 2^30",
+                batch, h, w, tiles_x, tiles_y);
+  if ((uintptr_t)dev_workspace % 16) return fail(e, UNETPP_E_INVALID, "dev_workspace must be 16-byte aligned");
+  if (dev_luts && (uintptr_t)dev_luts % 4) return fail(e, UNETPP_E_INVALID, "dev_luts must be 4-byte aligned");
+  EnhGrid g;
+  enh_grid(h, w, tiles_x, tiles_y, &g);
+  EnhTables T;
+  const int rc = enh_tables(e, gamma_table, tables, h, w, &T);
+  if (rc != UNETPP_OK) return rc;
+  const size_t n = (size_t)batch * h * w;
+  if (enh_overlap(dev_frames, n * channels_in, dev_out, n * channels_out))
+    return fail(e, UNETPP_E_INVALID, "dev_out aliases dev_frames: workgroups read halo pixels their neighbours write");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  char* wsp = (char*)dev_workspace;
+  unsigned* hist = (unsigned*)(wsp + ws.hist);
+  unsigned long long* sums = (unsigned long long*)(wsp + ws.sums);
+  uint8_t* luts = dev_luts ? dev_luts : (uint8_t*)(wsp + ws.luts);
+  uint8_t* decisions = dev_decisions ? dev_decisions : (uint8_t*)(wsp + ws.decisions);
+  const bool decide = mode == UNETPP_ENHANCE_IF_GREY && channels_in == 3;      // a one-channel frame is grey by definition
+  const uint8_t* gray = channels_in == 3 ? (const uint8_t*)(wsp + ws.gray) : dev_frames;
+  const int area = g.tw * g.th;
+  HIP_TRY(e, hipMemsetAsync(hist, 0, ws.luts - ws.hist, s));
+  enh_launch_stats(s, dev_frames, batch, h, w, channels_in, g, channels_in == 3 ? (uint8_t*)(wsp + ws.gray) : nullptr, hist,
+                   channels_in == 3 ? sums : nullptr);
+  hipLaunchKernelGGL(clahe_lut_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)batch), dim3(EN_THREADS), 0, s, (const unsigned*)hist,
+                     enh_clip(clip_limit, area), 255.0f / (float)area, luts, (const unsigned long long*)sums, (double)h * (double)w, threshold,
+                     decide ? 0 : 1, (decide || dev_decisions) ? decisions : (uint8_t*)nullptr);
+  const int lrc = enh_launch_apply(e, s, gray, luts, decide ? decisions : nullptr, dev_frames, batch, h, w, &g, channels_in, channels_out, T, dev_out);
+  if (lrc != UNETPP_OK) return lrc;
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+int unetpp_clahe_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h, int w, double clip_limit, int tiles_x, int tiles_y,
+                    uint8_t* dev_out, uint8_t* dev_luts, void* dev_workspace, void* stream) {
+  return unetpp_enhance_u8(e, dev_gray, batch, h, w, 1, 1, UNETPP_ENHANCE_ALWAYS, 0.0, clip_limit, tiles_x, tiles_y, nullptr, nullptr, dev_out,
+                           dev_luts, nullptr, dev_workspace, stream);
 }
 
 // ---- binary morphology programs (morphology.h) ------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """The model-adjacent lines of the reference frame loop (infer_two_stage_burr.py:37-47, 122-127, 292-314):
 everything between "a BGR video frame" and "uint8 class masks at frame size, clipped to the ROI".
-`segment_frames` starts from frames already at model resolution; `process_frames` also runs the two
+`process_frames_refactored` is the head of the refactored loop (infer_video_refactored.py:346-352): the grey-frame
+enhancement and the ROI crop in front of the same steps.  `segment_frames` starts from frames already at model resolution; `process_frames` also runs the two
 cv2.resize steps either side on the device (those two restate OpenCV's published
 algorithm and are parity-unpinned, see oracle/unetpp_oracle.py).  `measure_frames` is the tail of the production loop
 (infer_video_production.py:198-226): the diameter metrics and the defect analysis of every frame of a batch.
@@ -67,6 +68,29 @@ def process_frames(model, frames_bgr_u8, target_size=(512, 512), roi="fixed", de
     cable = model.resize_masks(pred, (fw, fh), match_class=1, roi=roi)
     tape = model.resize_masks(pred, (fw, fh), match_class=2, roi=roi)
     return pred, cable, tape
+
+
+def process_frames_refactored(model, frames_bgr_u8, roi_xywh, input_size=512, *, enable=True, threshold=10.0, device=None, **cfg):
+    """infer_video_refactored.py:346-352 for B raw frames at once, every step on the device and nothing read back:
+    preprocess_frame (src/refactor/preprocess.py:77-91: grey frames enhanced with CLAHE, gamma and the bilateral filter,
+    colour frames copied, decided per frame on the device), crop_roi (:94-113, the slice of roi = (x, y, w, h) clamped to
+    the frame), then process_frames on the crop with target_size = (input_size, input_size) and no ROI clip.  `cfg`:
+    PreprocessConfig's fields as NestedUNet.preprocess_frames takes them (clip_limit, tile_grid, gamma, denoise_method,
+    denoise_strength); `enable` is enable_grayscale_enhance.  Returns (pred uint8 [B,input_size,input_size], mask_cable,
+    mask_tape uint8 [B,crop_h,crop_w])."""
+    import torch
+    from . import enhance as en
+    x = frames_bgr_u8
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not x.is_cuda:
+        x = x.to(device if device is not None else f"cuda:{model._device_index or 0}", non_blocking=True)
+    x1, y1, x2, y2 = en.roi_bounds(int(x.shape[1]), int(x.shape[2]), roi_xywh)
+    if x2 <= x1 or y2 <= y1:
+        raise ValueError(f"roi {tuple(roi_xywh)} does not meet the {int(x.shape[1])}x{int(x.shape[2])} frame")
+    pre = model.preprocess_frames(x, enable, threshold, **cfg)
+    crop = pre[:, y1:y2, x1:x2].contiguous()
+    return process_frames(model, crop, (int(input_size), int(input_size)), roi=None)
 
 
 _DIAMETER_FIELDS = ("dc_px", "dt_px", "delta_d_px", "dc_mm", "dt_mm", "delta_d_mm", "valid_rows", "cable_coverage", "tape_coverage")

@@ -1133,6 +1133,136 @@ class NestedUNet:
         [B,H,W]: bool [B] on the device, np.sum(mask > 0) >= min_total_area per frame.  Nothing is read back."""
         return self.count_nonzero(mask) >= min_total_area
 
+    # ------------------------------------------------------------------ grey-frame enhancement (unet_amd/enhance.py is the NumPy form)
+    @staticmethod
+    def _c_tables(tables):
+        """(unetpp_bilateral_tables, the arrays it points into) for enhance.check_tables' tuple, or (None, None)."""
+        if tables is None:
+            return None, None
+        radius, color_w, space_w, dy, dx = tables
+        f32p, i32p = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)
+        ct = _lib.BilateralTables(radius, len(space_w), color_w.ctypes.data_as(f32p), space_w.ctypes.data_as(f32p),
+                                  dy.ctypes.data_as(i32p), dx.ctypes.data_as(i32p))
+        return ct, (color_w, space_w, dy, dx)
+
+    def _enhance_input(self, frames, what="frames"):
+        """uint8 CUDA [B,H,W,3] or [B,H,W], contiguous, on the engine's device -> (frames, channels)."""
+        import torch
+        if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and
+                (frames.dim() == 3 or (frames.dim() == 4 and frames.shape[-1] == 3))):
+            raise RuntimeError(f"{what} must be a uint8 CUDA tensor [B,H,W,3] or [B,H,W]")
+        return self._edge_input(frames, what, 3 if frames.dim() == 4 else None), (3 if frames.dim() == 4 else 1)
+
+    def _enhance(self, frames, cin, cout, mode, threshold, clip_limit, tile_grid, table, tables, want_luts=False, want_decisions=False):
+        """unetpp_enhance_u8: one memset and three launches on the current stream, nothing read back."""
+        import torch
+        from . import enhance as en
+        b, h, w = frames.shape[:3]
+        tx, ty = en.grid_of(tile_grid)
+        en.check_limits(h, w, (tx, ty), None if tables is None else tables[0])
+        if b > 65535:
+            raise ValueError(f"batch {b}: at most 65535")
+        lib = _lib.load()
+        key = ("enhance", b, h, w, tx, ty)
+        ws = self._cc_workspaces.get(key)
+        if ws is None or ws.device != frames.device:
+            nbytes = int(lib.unetpp_enhance_workspace_bytes(b, h, w, tx, ty))
+            if nbytes == 0:
+                raise RuntimeError(f"enhance: unsupported shape {tuple(frames.shape)} with a {tx}x{ty} grid")
+            ws = self._cc_workspaces[key] = torch.empty(nbytes, dtype=torch.uint8, device=frames.device)
+        dev = frames.device
+        out = torch.empty((b, h, w, 3) if cout == 3 else (b, h, w), dtype=torch.uint8, device=dev)
+        luts = torch.empty((b, ty * tx, 256), dtype=torch.uint8, device=dev) if want_luts else None
+        dec = torch.empty((b,), dtype=torch.uint8, device=dev) if want_decisions else None
+        ct, keep = self._c_tables(tables)
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        rc = lib.unetpp_enhance_u8(self._handle, p(frames), b, h, w, cin, cout, mode, float(threshold), float(clip_limit), tx, ty,
+                                   None if table is None else table.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                   None if ct is None else ctypes.byref(ct), p(out), p(luts), p(dec), p(ws), self._stream(frames))
+        del keep
+        if rc != 0:
+            self._raise(rc)
+        return out, luts, dec
+
+    def is_grayscale(self, frames, threshold: float = 10.0, return_sums: bool = False):
+        """is_grayscale_frame (src/refactor/preprocess.py:12-32) for uint8 CUDA frames [B,H,W,3]: bool [B] on the device,
+        max(sum |b - g|, sum |g - r|, sum |r - b|) / (H W) < threshold as one float64 division of exact integers
+        (enhance.is_grayscale_np).  Frames [B,H,W] count as grey.  return_sums: also the three sums, int64 [B,3]."""
+        import torch
+        frames, cin = self._enhance_input(frames)
+        b, h, w = frames.shape[:3]
+        if cin == 1:
+            dec = torch.ones((b,), dtype=torch.bool, device=frames.device)
+            return (dec, torch.zeros((b, 3), dtype=torch.int64, device=frames.device)) if return_sums else dec
+        dec = torch.empty((b,), dtype=torch.uint8, device=frames.device)
+        sums = torch.empty((b, 3), dtype=torch.int64, device=frames.device)      # uint64 bits, far below 2^63
+        rc = _lib.load().unetpp_gray_decision(self._handle, ctypes.c_void_p(frames.data_ptr()), b, h, w, float(threshold),
+                                              ctypes.c_void_p(dec.data_ptr()), ctypes.c_void_p(sums.data_ptr()), self._stream(frames))
+        if rc != 0:
+            self._raise(rc)
+        return (dec != 0, sums) if return_sums else dec != 0
+
+    def clahe(self, gray, clip_limit: float = 2.0, tile_grid=(8, 8), return_luts: bool = False):
+        """cv2.createCLAHE(clip_limit, tile_grid).apply(gray) for uint8 CUDA images [B,H,W] as OpenCV's CLAHE_Impl::apply
+        computes it (enhance.clahe_np; cv2's own result is unpinned).  tile_grid = (tilesX, tilesY) or one number, 1..16
+        per side, H > tilesY, W > tilesX.  return_luts: also the per-tile tables uint8 [B, tilesY * tilesX, 256]."""
+        gray = self._edge_input(gray)
+        out, luts, _ = self._enhance(gray, 1, 1, _lib.ENHANCE_ALWAYS, 0.0, clip_limit, tile_grid, None, None, want_luts=return_luts)
+        return (out, luts) if return_luts else out
+
+    def bilateral_filter(self, gray, d: int = 5, sigma_color: float = 75.0, sigma_space: float = 75.0, tables=None):
+        """cv2.bilateralFilter(gray, d, sigma_color, sigma_space) for uint8 CUDA images [B,H,W] as OpenCV's scalar 8-bit
+        loop computes it (enhance.bilateral_np; cv2's own result is unpinned), radius <= 4 (d <= 9), H, W > radius.
+        tables: enhance.bilateral_tables' tuple instead, e.g. with cv2's own weights or tap order."""
+        import torch
+        from . import enhance as en
+        tables = en.check_tables(en.bilateral_tables(d, sigma_color, sigma_space) if tables is None else tables)
+        gray = self._edge_input(gray)
+        b, h, w = gray.shape
+        en.check_limits(h, w, None, tables[0])
+        out = torch.empty_like(gray)
+        ct, keep = self._c_tables(tables)
+        rc = _lib.load().unetpp_bilateral_u8(self._handle, ctypes.c_void_p(gray.data_ptr()), b, h, w, ctypes.byref(ct),
+                                             ctypes.c_void_p(out.data_ptr()), self._stream(gray))
+        del keep
+        if rc != 0:
+            self._raise(rc)
+        return out
+
+    def enhance_grayscale(self, frames, *, clip_limit: float = 2.0, tile_grid=8, gamma: float = 0.8, denoise_method: str = "bilateral",
+                          denoise_strength: int = 5, channels_out: int = 3):
+        """enhance_grayscale_frame (src/refactor/preprocess.py:35-74) for uint8 CUDA frames [B,H,W,3] (BGR) or [B,H,W]:
+        BGR2GRAY, CLAHE, the gamma table, cv2.bilateralFilter(denoise_strength, 75, 75), GRAY2BGR -> uint8 [B,H,W,3]
+        (channels_out = 1: [B,H,W]); every frame is enhanced.  Defaults are PreprocessConfig's.  One memset and three
+        launches, nothing read back (enhance.enhance_grayscale_np is the NumPy form).  denoise_method other than
+        'bilateral' filters nothing, as in the reference; 'fastNlMeans' is a ValueError."""
+        from . import enhance as en
+        if channels_out not in (1, 3):
+            raise ValueError(f"channels_out must be 1 or 3, got {channels_out!r}")
+        tables = en.denoise_tables(denoise_method, denoise_strength)
+        tables = None if tables is None else en.check_tables(tables)
+        frames, cin = self._enhance_input(frames)
+        return self._enhance(frames, cin, int(channels_out), _lib.ENHANCE_ALWAYS, 0.0, clip_limit, tile_grid, en.gamma_table(gamma), tables)[0]
+
+    def preprocess_frames(self, frames, enable: bool = True, threshold: float = 10.0, *, clip_limit: float = 2.0, tile_grid=8,
+                          gamma: float = 0.8, denoise_method: str = "bilateral", denoise_strength: int = 5, return_decisions: bool = False):
+        """preprocess_frame (src/refactor/preprocess.py:77-91) for a batch of uint8 CUDA frames [B,H,W,3]: the frames
+        is_grayscale_frame calls grey are enhanced (enhance_grayscale), the others copied, decided per frame ON THE DEVICE
+        -- no synchronisation and no read-back between the first and the last launch.  enable=False
+        (PreprocessConfig.enable_grayscale_enhance) copies every frame.  Frames [B,H,W] always count as grey and come
+        back as [B,H,W,3].  return_decisions: also bool [B], True where a frame was enhanced."""
+        import torch
+        from . import enhance as en
+        tables = en.denoise_tables(denoise_method, denoise_strength)
+        tables = None if tables is None else en.check_tables(tables)
+        frames, cin = self._enhance_input(frames)
+        if not enable:
+            out = frames.clone() if cin == 3 else frames[..., None].expand(-1, -1, -1, 3).contiguous()
+            return (out, torch.zeros((frames.shape[0],), dtype=torch.bool, device=frames.device)) if return_decisions else out
+        out, _, dec = self._enhance(frames, cin, 3, _lib.ENHANCE_IF_GREY, threshold, clip_limit, tile_grid, en.gamma_table(gamma), tables,
+                                    want_decisions=return_decisions)
+        return (out, dec != 0) if return_decisions else out
+
     def resize_frames(self, frames, size_hw):
         """cv2.resize(frame, (W, H), interpolation=cv2.INTER_LINEAR) for uint8 CUDA frames [B,h,w,C] -> [B,H,W,C]
         (preprocess_image, infer_two_stage_burr.py:124).  Chain with segment(): the BGR->RGB swap and /255 run

@@ -4,8 +4,6 @@
 set -e
 cd "$(dirname "$0")/../.."
 PREC=${2:-exact}
-H=$(python -c 'from unet_amd import _lib; print(_lib.source_hash())')
-FLAGS=$(python -c 'from unet_amd import _lib; print(" ".join(_lib.CXXFLAGS))')
 run() {
   for b in 1 16; do
     echo "== $1 batch $b"
@@ -13,6 +11,6 @@ run() {
   done
 }
 run base
-(cd unet-_amd/csrc && /opt/rocm/bin/hipcc $FLAGS -shared -fPIC $1 -DUNETPP_SRC_HASH=\"$H\" -o ../libunetpp_hip.so unetpp_abi.hip)
+python -c 'import sys; from unet_amd import _lib; _lib.build(defines=[d[2:] for d in sys.argv[1].split()])' "$1"
 run "$1"
 UNETPP_FORCE_BUILD=1 python __graft_entry__.py > /dev/null

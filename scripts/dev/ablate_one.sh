@@ -4,9 +4,7 @@
 set -e
 cd "$(dirname "$0")/../.."
 BITS=$1; shift
-H=$(python -c 'from unet_amd import _lib; print(_lib.source_hash())')
-FLAGS=$(python -c 'from unet_amd import _lib; print(" ".join(_lib.CXXFLAGS))')
-(cd unet-_amd/csrc && /opt/rocm/bin/hipcc $FLAGS -shared -fPIC -DUNETPP_WS_DBG=1 -DUNETPP_SRC_HASH=\"$H\" -o ../libunetpp_hip.so unetpp_abi.hip)
+python -c 'from unet_amd import _lib; _lib.build(defines=["UNETPP_WS_DBG=1"])'
 for l in "$@"; do
   for d in 0 $BITS; do
     printf "%s dbg=%s: " $l $d

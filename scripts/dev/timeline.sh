@@ -4,9 +4,7 @@
 # usage (GPU box, repo root): [PREC=exact8] [BATCH=1] scripts/dev/timeline.sh
 set -e
 cd "$(dirname "$0")/../.."
-H=$(python -c 'from unet_amd import _lib; print(_lib.source_hash())')
-FLAGS=$(python -c 'from unet_amd import _lib; print(" ".join(_lib.CXXFLAGS))')
-(cd unet-_amd/csrc && /opt/rocm/bin/hipcc $FLAGS -shared -fPIC -DUNETPP_WS_DBG=1 -DUNETPP_SRC_HASH=\"$H\" -o ../libunetpp_hip.so unetpp_abi.hip)
+python -c 'from unet_amd import _lib; _lib.build(defines=["UNETPP_WS_DBG=1"])'
 UNETPP_ALLOW_DBG_LIB=1 UNETPP_WS_STAMPS=all timeout -k 10 120 python - <<PY 2>&1 | grep "timeline\|wall" || true
 import sys, time, torch
 sys.path.insert(0, ".")

@@ -283,6 +283,13 @@ def test_layout_and_workspace_queries_without_a_device():
         assert 6 * b * h * w <= n <= 6 * b * h * w + 4 * b * (h * w // 4096 + 1) + 4 * 256      # parent + map + flags (+ chunk counts)
     for b, h, w in ((0, 64, 64), (1, 7, 64), (1, 64, 7), (1, 65536, 8), (1, 40000, 40000)):
         assert lib.unetpp_canny_workspace_bytes(b, h, w) == 0
+    # the totals where the 256-byte rounding of a part decides, and the shapes either side of a limit
+    for (b, h, w), n in {(1, 8, 8): 1024, (1, 9, 9): 1280, (1, 33, 129): 26112, (16, 33, 129): 409600, (1, 512, 512): 1573120,
+                         (1, 32768, 32768): 6443499520, (1, 32768, 32769): 0, (1, 8, 7): 0, (1, 7, 800): 0, (1, 65535, 1): 0,
+                         (65536, 8, 8): 0}.items():
+        assert lib.unetpp_canny_workspace_bytes(b, h, w) == n, (b, h, w)
+    lib.unetpp_edges_union_workspace_bytes.restype = ctypes.c_size_t
+    assert [lib.unetpp_edges_union_workspace_bytes(b) for b in (0, 1, 64, 65, 65535, 65536)] == [0, 256, 256, 512, 262144, 0]
 
 
 def test_methods_check_their_arguments_without_a_device():

@@ -166,6 +166,15 @@ def test_binding_lists_the_component_symbols():
     assert _lib.CC_RULES == cc.RULES
     assert [n for n, _ in _lib.CcRule._fields_] == ["min_area", "min_width", "max_width", "min_height_ratio", "min_aspect",
                                                     "max_center_offset", "roi_width"]
+    # the workspace totals where the 256-byte rounding of a part decides, and the shapes either side of a limit (no device)
+    import ctypes
+    lib = ctypes.CDLL(_lib.build())
+    lib.unetpp_components_workspace_bytes.restype = ctypes.c_size_t
+    for (b, h, w, cap), n in {(1, 1, 1, 2): 768, (1, 8, 8, 2): 768, (1, 8, 8, 8192): 8704, (1, 33, 129, 2): 17664,
+                              (1, 33, 129, 8192): 25600, (16, 33, 129, 2): 273152, (1, 65535, 1, 2): 262656, (65535, 1, 1, 2): 655360,
+                              (1, 512, 512, 2): 1049088, (1, 32768, 32768, 2): 4296016128, (1, 32768, 32769, 2): 0,
+                              (1, 8, 8, 1): 0, (0, 8, 8, 2): 0, (65536, 1, 1, 2): 0, (1, 65536, 8, 2): 0}.items():
+        assert lib.unetpp_components_workspace_bytes(b, h, w, cap) == n, (b, h, w, cap)
 
 
 def test_methods_check_their_arguments_without_a_device():

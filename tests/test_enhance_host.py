@@ -168,3 +168,14 @@ def test_limits_and_fastnlmeans():
     f = en.make_enhance_scene(20, 24, 0)
     assert np.array_equal(en.enhance_grayscale_np(f, denoise_method="median"), en.enhance_grayscale_np(f, denoise_method="none"))
     assert np.array_equal(en.crop_roi_np(f, (-3, 5, 10, 100)), f[5:20, 0:7])
+    # the workspace totals where the 256-byte rounding of a part decides, and the shapes either side of a limit (no device)
+    import ctypes
+    from unet_amd import _lib
+    lib = ctypes.CDLL(_lib.build())
+    lib.unetpp_enhance_workspace_bytes.restype = ctypes.c_size_t
+    for (b, h, w, tx, ty), n in {(1, 2, 2, 1, 1): 2048, (1, 17, 17, 1, 1): 2304, (1, 16, 16, 8, 8): 82688, (1, 17, 17, 8, 8): 82944,
+                                 (1, 33, 129, 8, 8): 86784, (1, 33, 129, 16, 16): 332544, (16, 33, 129, 8, 8): 1379840,
+                                 (1, 512, 512, 8, 8): 344576, (1, 32768, 32768, 8, 8): 1073824256, (1, 32768, 32769, 8, 8): 0,
+                                 (1, 1, 1, 1, 1): 0, (1, 16, 16, 16, 16): 0, (1, 33, 129, 17, 1): 0, (1, 33, 129, 1, 17): 0,
+                                 (1, 33, 129, 0, 1): 0, (1, 65536, 8, 1, 1): 0, (0, 33, 129, 8, 8): 0, (65536, 33, 129, 8, 8): 0}.items():
+        assert lib.unetpp_enhance_workspace_bytes(b, h, w, tx, ty) == n, (b, h, w, tx, ty)

@@ -13,8 +13,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunetpp_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["unetpp_abi.hip"]
-HEADERS = ["conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "components.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "geometry.h", "tiling.h", os.path.join("..", "..", "include", "unetpp.h")]
+SOURCES = ["unetpp_abi.hip", "unetpp_postproc.hip"]      # the engine; the post-processing entry points
+HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "frame_kernels.h", "components.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "geometry.h", "tiling.h", os.path.join("..", "..", "include", "unetpp.h")]
 
 # every symbol include/unetpp.h declares
 ABI_SYMBOLS = [
@@ -134,15 +134,19 @@ def _hipcc():
     return cand if os.path.exists(cand) else shutil.which("hipcc")
 
 
-def build(force: bool = False, verbose: bool = False) -> str:
-    """hipcc --offload-arch=gfx950 -> unet-_amd/libunetpp_hip.so (cross-compiles without a GPU)."""
-    if not force and not _stale():
+def build(force: bool = False, verbose: bool = False, defines=()) -> str:
+    """hipcc --offload-arch=gfx950 -> unet-_amd/libunetpp_hip.so (cross-compiles without a GPU).
+
+    defines: extra preprocessor symbols ("NAME" or "NAME=VALUE") of a measurement build (scripts/ws_ablate.sh and its
+    kin); such a build is always compiled.  With UNETPP_WS_DBG among them the library tags itself "+wsdbg" and does not
+    count as the product build: built_hash() and load() refuse it unless UNETPP_ALLOW_DBG_LIB is set."""
+    if not force and not defines and not _stale():
         return LIB_PATH
     hipcc = _hipcc()
     if not hipcc:
         raise RuntimeError("hipcc not found: cannot build libunetpp_hip.so")
     tmp = f"{LIB_PATH}.{os.getpid()}.tmp"      # several ranks may build at once: write aside, then rename atomically
-    cmd = [hipcc] + CXXFLAGS + ["-shared", "-fPIC", f'-DUNETPP_SRC_HASH="{source_hash()}"',
+    cmd = [hipcc] + CXXFLAGS + ["-shared", "-fPIC", f'-DUNETPP_SRC_HASH="{source_hash()}"'] + [f"-D{d}" for d in defines] + [
            "-o", tmp] + [os.path.join(CSRC, s) for s in SOURCES]
     if verbose:
         print(" ".join(cmd).replace(tmp, LIB_PATH), flush=True)

@@ -354,7 +354,6 @@ __device__ __forceinline__ void pack_store_rows8(const float (&v)[16], half_t* d
   }
 }
 
-constexpr int HEAD_MAX_CLASSES = 16;
 constexpr int HEAD_FUSED_MAX_CLASSES = 8;   // the fused head keeps all logits in registers
 
 // UPF = fused bilinear upsample (reference unetpp.py:76,112-116: cat([skip, self.up(low)])): the second source `in1`

@@ -1,0 +1,902 @@
+// unetpp_postproc.hip — the post-processing entry points of the C ABI (include/unetpp.h): mask statistics, connected
+// components and their filters, the grey-level burr detectors, measurements, grey-frame enhancement, morphology, the two
+// resizes and the tiling of sliding-window inference.  Each entry checks its arguments and queues kernels on the caller's
+// stream.  Of an engine this file sees unetpp_engine_common (abi_common.h) and nothing else: no tensor, layer, arena or stream.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <tuple>
+#include <utility>
+#include <vector>
+
+#include "abi_common.h"
+#include "components.h"
+#include "edges.h"
+#include "edges_multi.h"
+#include "enhance.h"
+#include "frame_kernels.h"
+#include "geometry.h"
+#include "morphology.h"
+#include "tiling.h"
+
+using namespace unetpp;
+
+// ---- the vocabulary of the checks and launches: written once, each entry passes its own limits ---------------------------
+namespace {
+
+#define REQUIRE_ARGS(e, all_given)           \
+  if (!(e)) return UNETPP_E_INVALID;         \
+  if (!(all_given)) return fail(e, UNETPP_E_INVALID, "null argument")
+
+// every entry ends with it: a launch the runtime refused shows here
+int launched(unetpp_engine* e) {
+  HIP_TRY(e, hipGetLastError());
+  return UNETPP_OK;
+}
+
+// The limits differ between entries on purpose: the smallest side an algorithm takes, the largest a grid dimension or a
+// 16-bit coordinate holds, h * w <= 2^30 where pixel indices are 32-bit.  batch is always a grid dimension.
+struct ShapeLimits { int min_side, max_side; bool pixel_cap; };
+constexpr int MAX_DIM = 65535;
+constexpr ShapeLimits MASK_SHAPE{1, MAX_DIM, true}, EDGE_SHAPE{8, MAX_DIM, true}, BAND_SHAPE{2, MAX_DIM, true},
+                      GRAY_SHAPE{1, INT_MAX, true}, ROWS_SHAPE{1, MAX_DIM, false};
+bool shape_ok(int batch, int h, int w, const ShapeLimits& lim) {
+  return batch >= 1 && batch <= MAX_DIM && h >= lim.min_side && w >= lim.min_side && h <= lim.max_side && w <= lim.max_side &&
+         (!lim.pixel_cap || (size_t)h * w <= (1u << 30));
+}
+
+// do [a, a + na) and [b, b + nb) share a byte
+bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+  const char* p = (const char*)a; const char* q = (const char*)b;
+  return p < q + nb && q < p + na;
+}
+
+// may a kernel use 16-byte loads / stores: rows (or images) of n bytes behind 16-byte aligned pointers
+template <class... P>
+int vec16(int n, const P*... p) { return n % 16 == 0 && (((uintptr_t)p | ... | (uintptr_t)0) % 16) == 0; }
+
+dim3 tile_grid(int w, int h, int tw, int th, int batch) {
+  return dim3((unsigned)((w + tw - 1) / tw), (unsigned)((h + th - 1) / th), (unsigned)batch);
+}
+
+// Hands out the byte offsets of a workspace's parts in order, each on a 256-byte boundary; `end` is the total so far.
+struct Carve {
+  size_t end = 0;
+  size_t take(size_t bytes) { const size_t at = end; end = align_up(end + bytes, 256); return at; }
+};
+
+}  // namespace
+
+// One C block to the end of the file: the entry points, and next to each family its own checks and layouts (static).
+extern "C" {
+
+int unetpp_mask_stats(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, uint32_t* dev_counts,
+                      int32_t* dev_row_min, int32_t* dev_row_max, void* stream) {
+  REQUIRE_ARGS(e, dev_mask && dev_counts && dev_row_min && dev_row_max);
+  if (batch < 1 || h < 1 || w < 1) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int C = unetpp_common(e)->cfg.num_classes;
+  HIP_TRY(e, hipMemsetAsync(dev_counts, 0, (size_t)batch * C * sizeof(uint32_t), s));
+  hipLaunchKernelGGL(mask_stats_kernel, dim3((unsigned)h, (unsigned)batch), dim3(256), 0, s, dev_mask, C, h, w,
+                     (unsigned*)dev_counts, (int*)dev_row_min, (int*)dev_row_max);
+  return launched(e);
+}
+
+// ---- connected components + the reference's component filters (components.h) -----------------------------------
+struct CcWorkspace {
+  size_t parent = 0, chunks = 0, keep = 0, total = 0;   // byte offsets
+  int nchunk = 0;
+};
+static bool cc_layout(int batch, int h, int w, int capacity, CcWorkspace* ws) {
+  if (!shape_ok(batch, h, w, MASK_SHAPE) || capacity < 2) return false;
+  const size_t hw = (size_t)h * w;
+  ws->nchunk = (int)((hw + CC_CHUNK - 1) / CC_CHUNK);
+  Carve c;
+  ws->parent = c.take(hw * batch * sizeof(int));
+  ws->chunks = c.take((size_t)ws->nchunk * batch * sizeof(int));
+  ws->keep = c.take((size_t)capacity * batch);
+  ws->total = c.end;
+  return true;
+}
+// The labelling chain both users share: union-find inside the tiles, merge across their borders, path compression.
+// Afterwards parent[] holds every pixel's root (-1: background) and chunks[] the number of roots in each raster chunk.
+static void launch_roots(hipStream_t s, const uint8_t* mask, int batch, int h, int w, int match_class, int conn8, int mask_vec, int nchunk,
+                         int* parent, int* chunks) {
+  const dim3 blk(CC_THREADS), tiles = tile_grid(w, h, CC_TW, CC_TH, batch);
+  const int ntx = (int)tiles.x, nty = (int)tiles.y, hw = h * w;
+  hipLaunchKernelGGL(cc_tile_kernel, tiles, blk, 0, s, mask, h, w, match_class, conn8, mask_vec, parent);
+  const long long items = (long long)(nty - 1) * w + 2LL * (ntx - 1) * h;
+  if (items > 0)
+    hipLaunchKernelGGL(cc_merge_kernel, dim3((unsigned)((items + CC_THREADS - 1) / CC_THREADS), (unsigned)batch), blk, 0, s, parent, h, w,
+                       conn8, nty - 1, ntx - 1);
+  hipLaunchKernelGGL(cc_compress_kernel, dim3((unsigned)nchunk, (unsigned)batch), blk, 0, s, parent, hw, (int)(hw % 4 == 0), chunks);
+}
+// The launches both filters end with: keep[] = the components the rule keeps, then dev_out = out_value where a pixel's label is kept.
+static int launch_select_apply(unetpp_engine* e, hipStream_t s, const int32_t* dev_labels, const int32_t* dev_num, const int32_t* dev_stats,
+                               const uint64_t* dev_sums, int batch, int h, int w, int capacity, int rule, const CcRule& r, uint8_t out_value,
+                               uint8_t* dev_out, void* dev_workspace) {
+  CcWorkspace ws;
+  if (!cc_layout(batch, h, w, capacity, &ws)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  ENTER_DEVICE(e);
+  const int hw = h * w;
+  uint8_t* keep = (uint8_t*)dev_workspace + ws.keep;
+  hipLaunchKernelGGL(cc_select_kernel, dim3((unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_num, (const int*)dev_stats,
+                     (const unsigned long long*)dev_sums, h, capacity, rule, r, keep);
+  hipLaunchKernelGGL(cc_apply_kernel, dim3((unsigned)ws.nchunk, (unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_labels,
+                     (const uint8_t*)keep, hw, capacity, vec16(hw, dev_labels, dev_out), (unsigned)out_value, dev_out);
+  return launched(e);
+}
+
+size_t unetpp_components_workspace_bytes(int batch, int h, int w, int capacity) {
+  CcWorkspace ws;
+  return cc_layout(batch, h, w, capacity, &ws) ? ws.total : 0;
+}
+
+int unetpp_components(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, int match_class, int connectivity,
+                      int capacity, int32_t* dev_labels, int32_t* dev_num, int32_t* dev_stats, uint64_t* dev_sums,
+                      void* dev_workspace, void* stream) {
+  REQUIRE_ARGS(e, dev_mask && dev_labels && dev_num && dev_workspace);
+  if ((dev_stats == nullptr) != (dev_sums == nullptr)) return fail(e, UNETPP_E_INVALID, "dev_stats and dev_sums go together (both or neither)");
+  if (connectivity != 4 && connectivity != 8) return fail(e, UNETPP_E_INVALID, "connectivity must be 4 or 8, got %d", connectivity);
+  if (capacity < 2) return fail(e, UNETPP_E_INVALID, "capacity %d: at least 2 rows (background + one component)", capacity);
+  if (match_class > 255) return fail(e, UNETPP_E_INVALID, "match_class %d out of range", match_class);
+  CcWorkspace ws;
+  if (!cc_layout(batch, h, w, capacity, &ws)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if ((uintptr_t)dev_workspace % 16) return fail(e, UNETPP_E_INVALID, "dev_workspace must be 16-byte aligned");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w, conn8 = connectivity == 8;
+  int* parent = (int*)((char*)dev_workspace + ws.parent);
+  int* chunks = (int*)((char*)dev_workspace + ws.chunks);
+  const dim3 blk(CC_THREADS), per_px((unsigned)ws.nchunk, (unsigned)batch);
+  if (dev_stats) {
+    HIP_TRY(e, hipMemsetAsync(dev_stats, 0, (size_t)batch * capacity * 5 * sizeof(int32_t), s));
+    HIP_TRY(e, hipMemsetAsync(dev_sums, 0, (size_t)batch * capacity * 2 * sizeof(uint64_t), s));
+  }
+  launch_roots(s, dev_mask, batch, h, w, match_class, conn8, vec16(w, dev_mask), ws.nchunk, parent, chunks);
+  const int par_vec = hw % 4 == 0;             // the workspace is 16-byte aligned and `parent` starts it
+  hipLaunchKernelGGL(cc_scan_kernel, dim3((unsigned)batch), blk, 0, s, chunks, ws.nchunk, (int*)dev_num);
+  hipLaunchKernelGGL(cc_number_kernel, per_px, blk, 0, s, parent, hw, par_vec, (const int*)chunks);
+  const int lab_vec = par_vec && (uintptr_t)dev_labels % 16 == 0;
+  hipLaunchKernelGGL(cc_relabel_kernel, per_px, blk, 0, s, (const int*)parent, h, w, capacity, lab_vec, (int*)dev_labels, (int*)dev_stats,
+                     (unsigned long long*)dev_sums);
+  if (dev_stats)
+    hipLaunchKernelGGL(cc_finish_stats_kernel, dim3((unsigned)((capacity + CC_THREADS - 1) / CC_THREADS), (unsigned)batch), blk, 0, s,
+                       (int*)dev_stats, h, w, capacity);
+  return launched(e);
+}
+
+int unetpp_components_filter(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num, const int32_t* dev_stats,
+                             const uint64_t* dev_sums, int batch, int h, int w, int capacity, int rule, const unetpp_cc_rule* params,
+                             uint8_t out_value, uint8_t* dev_out, void* dev_workspace, void* stream) {
+  REQUIRE_ARGS(e, dev_labels && dev_num && dev_stats && dev_sums && params && dev_out && dev_workspace);
+  if (rule != UNETPP_CC_LARGEST && rule != UNETPP_CC_SPATIAL && rule != UNETPP_CC_CABLE_SHAPE) return fail(e, UNETPP_E_INVALID, "unknown rule %d", rule);
+  if (capacity < 2) return fail(e, UNETPP_E_INVALID, "capacity %d: at least 2 rows (background + one component)", capacity);
+  if (rule == UNETPP_CC_CABLE_SHAPE && !(params->roi_width > 0)) return fail(e, UNETPP_E_INVALID, "roi_width must be positive");
+  CcRule r{params->min_area, params->min_width, params->max_width, params->min_height_ratio, params->min_aspect,
+           params->max_center_offset, params->roi_width};
+  return launch_select_apply(e, (hipStream_t)stream, dev_labels, dev_num, dev_stats, dev_sums, batch, h, w, capacity, rule, r, out_value, dev_out,
+                             dev_workspace);
+}
+
+int unetpp_components_filter_box(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num, const int32_t* dev_stats,
+                                 int batch, int h, int w, int capacity, const unetpp_cc_box_rule* params, uint8_t out_value,
+                                 uint8_t* dev_out, void* dev_workspace, void* stream) {
+  REQUIRE_ARGS(e, dev_labels && dev_num && dev_stats && params && dev_out && dev_workspace);
+  if (capacity < 2) return fail(e, UNETPP_E_INVALID, "capacity %d: at least 2 rows (background + one component)", capacity);
+  if (std::isnan(params->min_area) || std::isnan(params->max_area) || std::isnan(params->max_aspect) || std::isnan(params->min_side))
+    return fail(e, UNETPP_E_INVALID, "box rule: NaN parameter");
+  CcRule r{};
+  r.min_area = params->min_area; r.max_area = params->max_area; r.max_aspect = params->max_aspect; r.min_side = params->min_side;
+  return launch_select_apply(e, (hipStream_t)stream, dev_labels, dev_num, dev_stats, nullptr, batch, h, w, capacity, (int)CC_RULE_BOX, r, out_value,
+                             dev_out, dev_workspace);      // the box rule reads no sums
+}
+
+// ---- grey-level front end of the burr detection (edges.h) -----------------------------------------------------------
+struct CannyWorkspace {
+  size_t parent = 0, chunks = 0, map = 0, flags = 0, total = 0;   // byte offsets
+  int nchunk = 0;
+};
+static bool canny_layout(int batch, int h, int w, CannyWorkspace* ws) {
+  if (!shape_ok(batch, h, w, EDGE_SHAPE)) return false;
+  const size_t hw = (size_t)h * w;
+  ws->nchunk = (int)((hw + CC_CHUNK - 1) / CC_CHUNK);
+  Carve c;
+  ws->parent = c.take(hw * batch * sizeof(int));
+  ws->chunks = c.take((size_t)ws->nchunk * batch * sizeof(int));
+  ws->map = c.take(hw * batch);
+  ws->flags = c.take(hw * batch);
+  ws->total = c.end;
+  return true;
+}
+// The blur / Canny family tells a call that makes no sense from a shape its kernels do not take.
+static int edge_shape_check(unetpp_engine* e, int batch, int h, int w) {
+  if (batch < 1 || h < 1 || w < 1) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if (!shape_ok(batch, h, w, EDGE_SHAPE)) return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside 8 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  return UNETPP_OK;
+}
+// taps == NULL: no blur (the identity tap).  Otherwise n_taps odd, <= 7, every tap in [0,256], sum 256, symmetric or not.
+static int edge_taps(unetpp_engine* e, const int32_t* taps, int n_taps, EdgeTaps* out) {
+  std::memset(out, 0, sizeof *out);
+  if (!taps) { out->n = 1; out->t[0] = 256; return UNETPP_OK; }
+  if (n_taps < 1 || n_taps % 2 == 0) return fail(e, UNETPP_E_INVALID, "n_taps %d: must be odd and positive", n_taps);
+  if (n_taps > ED_MAX_TAPS) return fail(e, UNETPP_E_UNSUPPORTED, "n_taps %d: at most %d", n_taps, ED_MAX_TAPS);
+  int sum = 0;
+  for (int k = 0; k < n_taps; ++k) {
+    if (taps[k] < 0 || taps[k] > 256) return fail(e, UNETPP_E_INVALID, "tap %d = %d not in [0,256]", k, (int)taps[k]);
+    out->t[k] = taps[k];
+    sum += taps[k];
+  }
+  if (sum != 256) return fail(e, UNETPP_E_INVALID, "taps sum to %d, not 256", sum);
+  out->n = n_taps;
+  return UNETPP_OK;
+}
+
+int unetpp_gray_u8(unetpp_engine* e, const uint8_t* dev_bgr, int batch, int h, int w, uint8_t* dev_gray, void* stream) {
+  REQUIRE_ARGS(e, dev_bgr && dev_gray);
+  if (!shape_ok(batch, h, w, GRAY_SHAPE)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  ENTER_DEVICE(e);
+  const int hw = h * w;
+  hipLaunchKernelGGL(gray_kernel, dim3((unsigned)((hw + ED_THREADS - 1) / ED_THREADS), (unsigned)batch), dim3(ED_THREADS), 0, (hipStream_t)stream,
+                     dev_bgr, hw, dev_gray);
+  return launched(e);
+}
+
+int unetpp_canny_layout(int h, int w, int* tile_rows, int* tile_cols) {
+  if (!tile_rows || !tile_cols) return fail(nullptr, UNETPP_E_INVALID, "null argument");
+  if (!shape_ok(1, h, w, EDGE_SHAPE)) return fail(nullptr, UNETPP_E_UNSUPPORTED, "bad shape %dx%d", h, w);
+  *tile_rows = ED_TH;
+  *tile_cols = ED_TW;
+  return UNETPP_OK;
+}
+
+size_t unetpp_canny_workspace_bytes(int batch, int h, int w) {
+  CannyWorkspace ws;
+  return canny_layout(batch, h, w, &ws) ? ws.total : 0;
+}
+
+int unetpp_gaussian_blur_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h, int w, const int32_t* taps, int n_taps,
+                            uint8_t* dev_out, void* stream) {
+  REQUIRE_ARGS(e, dev_gray && dev_out && taps);
+  if (const int rc = edge_shape_check(e, batch, h, w)) return rc;
+  EdgeTaps T;
+  if (const int rc = edge_taps(e, taps, n_taps, &T)) return rc;
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_gray, n, dev_out, n)) return fail(e, UNETPP_E_INVALID, "dev_out aliases dev_gray: workgroups read halo pixels their neighbours write");
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(edge_map_kernel<true>, tile_grid(w, h, ED_TW, ED_TH, batch), dim3(ED_THREADS), 0, (hipStream_t)stream, dev_gray, h, w, T, 0,
+                     0, vec16(w, dev_out), dev_out);
+  return launched(e);
+}
+
+int unetpp_canny_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h, int w, const int32_t* taps, int n_taps, double low,
+                    double high, uint8_t* dev_out, void* dev_workspace, void* stream) {
+  REQUIRE_ARGS(e, dev_gray && dev_out && dev_workspace);
+  if (const int rc = edge_shape_check(e, batch, h, w)) return rc;
+  CannyWorkspace ws;
+  canny_layout(batch, h, w, &ws);                            // fails for a bad shape only
+  if (!(low >= 0) || !(high >= 0)) return fail(e, UNETPP_E_INVALID, "thresholds must be non-negative numbers");
+  if ((uintptr_t)dev_workspace % 16) return fail(e, UNETPP_E_INVALID, "dev_workspace must be 16-byte aligned");
+  EdgeTaps T;
+  if (const int rc = edge_taps(e, taps, n_taps, &T)) return rc;
+  if (low > high) std::swap(low, high);                      // cv2.Canny does the same
+  const int ilow = (int)std::floor(std::min(low, 1e6)), ihigh = (int)std::floor(std::min(high, 1e6));
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  int* parent = (int*)((char*)dev_workspace + ws.parent);
+  int* chunks = (int*)((char*)dev_workspace + ws.chunks);
+  uint8_t* map = (uint8_t*)dev_workspace + ws.map;
+  uint8_t* flags = (uint8_t*)dev_workspace + ws.flags;
+  static_assert(ED_TW == CC_TW && ED_TH == CC_TH && ED_THREADS == CC_THREADS, "the edge map is labelled in cc_tile_kernel's tiles");
+  const dim3 blk(ED_THREADS), per_px((unsigned)ws.nchunk, (unsigned)batch);
+  HIP_TRY(e, hipMemsetAsync(flags, 0, (size_t)batch * hw, s));
+  const int row_vec = vec16(w);                              // map starts on a 256-byte boundary of the workspace
+  hipLaunchKernelGGL(edge_map_kernel<false>, tile_grid(w, h, ED_TW, ED_TH, batch), blk, 0, s, dev_gray, h, w, T, ilow, ihigh, row_vec, map);
+  launch_roots(s, map, batch, h, w, -1, 1, row_vec, ws.nchunk, parent, chunks);
+  hipLaunchKernelGGL(edge_seed_kernel, per_px, blk, 0, s, (const uint8_t*)map, (const int*)parent, hw, vec16(hw), flags);
+  hipLaunchKernelGGL(edge_apply_kernel, per_px, blk, 0, s, (const int*)parent, (const uint8_t*)flags, hw, (int)(hw % 4 == 0),
+                     vec16(hw, dev_out), dev_out);
+  return launched(e);
+}
+
+int unetpp_laplacian_band_u8(unetpp_engine* e, const uint8_t* dev_gray, const uint8_t* dev_band, int batch, int h, int w, int threshold,
+                             uint8_t* dev_out, void* stream) {
+  REQUIRE_ARGS(e, dev_gray && dev_band && dev_out);
+  if (!shape_ok(batch, h, w, BAND_SHAPE)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_gray, n, dev_out, n)) return fail(e, UNETPP_E_INVALID, "dev_out aliases dev_gray: threads read neighbours that others write");
+  ENTER_DEVICE(e);
+  const long long items = (long long)h * ((w + CC_PX - 1) / CC_PX);
+  hipLaunchKernelGGL(laplacian_band_kernel, dim3((unsigned)((items + ED_THREADS - 1) / ED_THREADS), (unsigned)batch), dim3(ED_THREADS), 0,
+                     (hipStream_t)stream, dev_gray, dev_band, h, w, threshold, vec16(w, dev_band, dev_out), dev_out);
+  return launched(e);
+}
+
+// ---- the multi-scale and the DoG burr detectors, has_burr (edges_multi.h) ---------------------------------------
+size_t unetpp_edges_union_workspace_bytes(int batch) {
+  return batch >= 1 && batch <= 65535 ? align_up((size_t)batch * sizeof(uint32_t), 256) : 0;
+}
+
+int unetpp_edges_union_u8(unetpp_engine* e, const uint8_t* dev_gray, const uint8_t* dev_canny, int batch, int h, int w,
+                          int sobel_threshold, int laplacian_threshold, void* dev_workspace, uint8_t* dev_out, void* stream) {
+  REQUIRE_ARGS(e, dev_gray && dev_canny && dev_workspace && dev_out);
+  if (const int rc = edge_shape_check(e, batch, h, w)) return rc;
+  if ((uintptr_t)dev_workspace % 16) return fail(e, UNETPP_E_INVALID, "dev_workspace must be 16-byte aligned");
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_gray, n, dev_out, n)) return fail(e, UNETPP_E_INVALID, "dev_out aliases dev_gray: workgroups read halo pixels their neighbours write");
+  if (dev_out != dev_canny && overlaps(dev_canny, n, dev_out, n))
+    return fail(e, UNETPP_E_INVALID, "dev_out overlaps dev_canny: in place means the same pointer");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  unsigned* smax = (unsigned*)dev_workspace;
+  const dim3 blk(ED_THREADS), tiles = tile_grid(w, h, ED_TW, ED_TH, batch);
+  const int sthr = std::min(std::max(sobel_threshold, -1), 255), lthr = std::min(std::max(laplacian_threshold, -1), 255);
+  HIP_TRY(e, hipMemsetAsync(smax, 0, (size_t)batch * sizeof(unsigned), s));
+  hipLaunchKernelGGL(sobel_max_kernel, tiles, blk, 0, s, dev_gray, h, w, smax);
+  hipLaunchKernelGGL(edge_union_kernel, tiles, blk, 0, s, dev_gray, dev_canny, h, w, (const unsigned*)smax, sthr, lthr,
+                     vec16(w, dev_canny, dev_out), dev_out);
+  return launched(e);
+}
+
+int unetpp_dog_band_u8(unetpp_engine* e, const uint8_t* dev_gray, const uint8_t* dev_band, int batch, int h, int w, const int32_t* taps1,
+                       int n1, const int32_t* taps2, int n2, int threshold, uint8_t* dev_out, void* stream) {
+  REQUIRE_ARGS(e, dev_gray && dev_band && dev_out && taps1 && taps2);
+  if (const int rc = edge_shape_check(e, batch, h, w)) return rc;
+  EdgeTaps T1, T2;
+  if (const int rc = edge_taps(e, taps1, n1, &T1)) return rc;
+  if (const int rc = edge_taps(e, taps2, n2, &T2)) return rc;
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_gray, n, dev_out, n) || overlaps(dev_band, n, dev_out, n))
+    return fail(e, UNETPP_E_INVALID, "dev_out aliases an input: workgroups read halo pixels their neighbours write");
+  DogTaps D;
+  std::memset(&D, 0, sizeof D);
+  for (int k = 0; k < T1.n; ++k) D.t1[ED_MAX_R - T1.n / 2 + k] = T1.t[k];
+  for (int k = 0; k < T2.n; ++k) D.t2[ED_MAX_R - T2.n / 2 + k] = T2.t[k];
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(dog_band_kernel, tile_grid(w, h, ED_TW, ED_TH, batch), dim3(ED_THREADS), 0, (hipStream_t)stream, dev_gray, dev_band, h, w, D,
+                     std::min(std::max(threshold, -1), 255), vec16(w, dev_band, dev_out), dev_out);
+  return launched(e);
+}
+
+int unetpp_count_nonzero_u8(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, uint32_t* dev_counts, void* stream) {
+  REQUIRE_ARGS(e, dev_mask && dev_counts);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  HIP_TRY(e, hipMemsetAsync(dev_counts, 0, (size_t)batch * sizeof(uint32_t), s));
+  hipLaunchKernelGGL(count_nonzero_kernel, dim3((unsigned)((hw + CC_CHUNK - 1) / CC_CHUNK), (unsigned)batch), dim3(ED_THREADS), 0, s, dev_mask, hw,
+                     vec16(hw, dev_mask), (unsigned*)dev_counts);
+  return launched(e);
+}
+
+// ---- measurements: row widths, width profile, component summary (geometry.h) -------------------------------------------
+int unetpp_row_widths(unetpp_engine* e, const uint8_t* dev_mask0, int match0, const uint8_t* dev_mask1, int match1, int batch, int h,
+                      int w, float* dev_widths, uint32_t* dev_area, void* stream) {
+  REQUIRE_ARGS(e, dev_mask0 && dev_widths && dev_area);
+  if (!shape_ok(batch, h, w, ROWS_SHAPE)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if (match0 > 255 || match1 > 255) return fail(e, UNETPP_E_INVALID, "match class %d / %d out of range", match0, match1);
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(e, hipMemsetAsync(dev_area, 0, (size_t)batch * 2 * sizeof(uint32_t), s));
+  hipLaunchKernelGGL(row_widths_kernel, dim3((unsigned)((h + GEO_ROWS_PER_WG - 1) / GEO_ROWS_PER_WG), (unsigned)batch), dim3(GEO_THREADS), 0, s,
+                     dev_mask0, match0, dev_mask1, match1, h, w, vec16(w, dev_mask0), vec16(w, dev_mask1), dev_widths, (unsigned*)dev_area);
+  return launched(e);
+}
+
+int unetpp_width_profile(unetpp_engine* e, const float* dev_widths, int batch, int h, const float* taps, int n_taps, int min_valid_rows,
+                         float* dev_smoothed, uint8_t* dev_valid, float* dev_delta, unetpp_width_profile_out* dev_out, void* stream) {
+  REQUIRE_ARGS(e, dev_widths && taps && dev_smoothed && dev_valid && dev_out);
+  if (batch < 1 || batch > 65535 || h < 1) return fail(e, UNETPP_E_INVALID, "bad shape %dx%d", batch, h);
+  if (h > GEO_MAX_ROWS) return fail(e, UNETPP_E_INVALID, "width_profile: %d rows, at most %d", h, GEO_MAX_ROWS);
+  if (n_taps < 1 || n_taps > GEO_MAX_TAPS || n_taps % 2 == 0) return fail(e, UNETPP_E_INVALID, "n_taps %d: odd, 1..%d", n_taps, GEO_MAX_TAPS);
+  if (min_valid_rows < 1) return fail(e, UNETPP_E_INVALID, "min_valid_rows %d: at least 1", min_valid_rows);
+  const int r = n_taps / 2;
+  GeoTaps gt{};
+  for (int j = 0; j <= r; ++j) {
+    if (!std::isfinite(taps[r + j]) || !(taps[r + j] == taps[r - j])) return fail(e, UNETPP_E_INVALID, "taps must be finite and symmetric");
+    gt.t[j] = taps[r + j];
+  }
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  static_assert(sizeof(unetpp_width_profile_out) == sizeof(GeoProfileOut), "width profile record");
+  hipLaunchKernelGGL(width_profile_kernel, dim3((unsigned)batch), dim3(GEO_THREADS), 2 * (size_t)(h + 2 * r) * sizeof(float), s, dev_widths, h,
+                     gt, r, min_valid_rows, dev_smoothed, dev_valid, dev_delta, (GeoProfileOut*)dev_out);
+  return launched(e);
+}
+
+int unetpp_components_summary(unetpp_engine* e, const int32_t* dev_num, const int32_t* dev_stats, int batch, int capacity, int64_t min_area,
+                              int64_t* dev_out, void* stream) {
+  REQUIRE_ARGS(e, dev_num && dev_out);
+  if (batch < 1 || batch > 65535) return fail(e, UNETPP_E_INVALID, "bad batch %d", batch);
+  if (capacity < 2) return fail(e, UNETPP_E_INVALID, "capacity %d: at least 2 rows (background + one component)", capacity);
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(components_summary_kernel, dim3((unsigned)batch), dim3(GEO_THREADS), 0, (hipStream_t)stream, (const int*)dev_num,
+                     (const int*)dev_stats, capacity, (long long)min_area, (long long*)dev_out);
+  return launched(e);
+}
+
+// ---- grey-frame enhancement: decision, CLAHE, gamma, bilateral filter (enhance.h) ---------------------------------------
+struct EnhWorkspace { size_t gray, hist, sums, luts, decisions, total; };
+
+// CLAHE_Impl::apply's geometry (enhance.clahe_geometry); false outside 1 <= tiles <= 16, h > tiles_y, w > tiles_x
+static bool enh_grid(int h, int w, int tiles_x, int tiles_y, EnhGrid* g) {
+  if (tiles_x < 1 || tiles_y < 1 || tiles_x > EN_MAX_GRID || tiles_y > EN_MAX_GRID || h <= tiles_y || w <= tiles_x) return false;
+  const bool divides = w % tiles_x == 0 && h % tiles_y == 0;
+  g->tiles_x = tiles_x; g->tiles_y = tiles_y;
+  g->ext_w = divides ? w : w + tiles_x - w % tiles_x;
+  g->ext_h = divides ? h : h + tiles_y - h % tiles_y;
+  g->tw = g->ext_w / tiles_x; g->th = g->ext_h / tiles_y;
+  return true;
+}
+static bool enh_layout(int batch, int h, int w, int tiles_x, int tiles_y, EnhWorkspace* ws) {
+  EnhGrid g;
+  if (!shape_ok(batch, h, w, MASK_SHAPE) || !enh_grid(h, w, tiles_x, tiles_y, &g)) return false;
+  const size_t tiles = (size_t)tiles_x * tiles_y;
+  Carve c;
+  ws->gray = c.take((size_t)batch * h * w);
+  ws->hist = c.take((size_t)batch * tiles * 256 * sizeof(unsigned));
+  ws->sums = c.take((size_t)batch * 3 * sizeof(unsigned long long));          // directly behind hist (whole KiB): one memset clears both
+  ws->luts = c.take((size_t)batch * tiles * 256);
+  ws->decisions = c.take((size_t)batch);
+  ws->total = c.end;
+  return true;
+}
+// Everything the apply kernel indexes its LDS with is checked here.  tables == NULL: no filter.
+static int enh_tables(unetpp_engine* e, const uint8_t* gamma_table, const unetpp_bilateral_tables* tables, int h, int w, EnhTables* T) {
+  std::memset(T, 0, sizeof *T);
+  if (gamma_table) { std::memcpy(T->gamma, gamma_table, 256); T->has_gamma = 1; }
+  if (!tables) return UNETPP_OK;
+  if (!tables->color_w || !tables->space_w || !tables->dy || !tables->dx) return fail(e, UNETPP_E_INVALID, "bilateral tables: null array");
+  const int r = tables->radius, n = tables->n_taps;
+  if (r < 1 || r > EN_MAX_R) return fail(e, UNETPP_E_UNSUPPORTED, "bilateral radius %d: 1..%d", r, EN_MAX_R);
+  if (h <= r || w <= r) return fail(e, UNETPP_E_UNSUPPORTED, "image %dx%d: needs h, w > radius %d", h, w, r);
+  if (n < 1 || n > (2 * r + 1) * (2 * r + 1)) return fail(e, UNETPP_E_INVALID, "bilateral n_taps %d: 1..%d", n, (2 * r + 1) * (2 * r + 1));
+  for (int k = 0; k < n; ++k) {
+    if (std::abs(tables->dy[k]) > r || std::abs(tables->dx[k]) > r) return fail(e, UNETPP_E_INVALID, "bilateral tap %d lies outside the radius %d", k, r);
+    if (!std::isfinite(tables->space_w[k]) || tables->space_w[k] < 0) return fail(e, UNETPP_E_INVALID, "bilateral space weight %d is not finite and non-negative", k);
+    T->space_w[k] = tables->space_w[k]; T->dy[k] = (signed char)tables->dy[k]; T->dx[k] = (signed char)tables->dx[k];
+  }
+  for (int i = 0; i < 256; ++i) {
+    if (!std::isfinite(tables->color_w[i]) || tables->color_w[i] < 0) return fail(e, UNETPP_E_INVALID, "bilateral colour weight %d is not finite and non-negative", i);
+    T->color_w[i] = tables->color_w[i];
+  }
+  T->n_taps = n; T->radius = r;
+  return UNETPP_OK;
+}
+static void enh_launch_stats(hipStream_t s, const uint8_t* src, int batch, int h, int w, int cin, const EnhGrid& g, uint8_t* gray, unsigned* hist,
+                             unsigned long long* sums) {
+  const int area = g.tw * g.th;
+  const dim3 grid((unsigned)((area + EN_CHUNK - 1) / EN_CHUNK), (unsigned)(g.tiles_x * g.tiles_y), (unsigned)batch);
+  hipLaunchKernelGGL(enhance_stats_kernel, grid, dim3(EN_THREADS), 0, s, src, h, w, cin, g, gray, hist, sums);
+}
+// clip_limit * tileArea / 256 in double, truncated, at least 1; 0 = no clipping.  A clip of tileArea or more clips nothing.
+static int enh_clip(double clip_limit, int area) {
+  if (!(clip_limit > 0)) return 0;
+  const double c = clip_limit * area / 256;
+  return c >= (double)area ? area : std::max((int)c, 1);
+}
+static int enh_launch_apply(unetpp_engine* e, hipStream_t s, const uint8_t* gray, const uint8_t* luts, const uint8_t* decisions, const uint8_t* frames,
+                            int batch, int h, int w, const EnhGrid* g, int cin, int cout, const EnhTables& T, uint8_t* out) {
+  EnhApplyArgs A;
+  std::memset(&A, 0, sizeof A);
+  size_t lds = 0;
+  if (g) {
+    A.g = *g; A.do_clahe = 1;
+    // tiles a window of EN_TH + 2 r rows can touch: ceil(span / th) + 2 (enhance.h), never more than the grid has
+    A.lut_rows = std::min(g->tiles_y, (EN_TH + 2 * T.radius + g->th - 1) / g->th + 2);
+    A.lut_cols = std::min(g->tiles_x, (EN_TW + 2 * T.radius + g->tw - 1) / g->tw + 2);
+    lds = (size_t)A.lut_rows * A.lut_cols * 256;
+  } else {
+    A.g.tiles_x = A.g.tiles_y = A.g.tw = A.g.th = 1;
+  }
+  A.cin = cin; A.cout = cout;
+  A.vec = w % 4 == 0 && (uintptr_t)out % 4 == 0;
+  // the kernel has static LDS too, so the limit asked for is the largest dynamic part (the whole 16 x 16 grid), not all 160 KiB
+  if (lds > 32 * 1024) HIP_TRY(e, allow_full_lds((const void*)enhance_apply_kernel, unetpp_common(e)->cfg.device, EN_MAX_GRID * EN_MAX_GRID * 256));
+  hipLaunchKernelGGL(enhance_apply_kernel, tile_grid(w, h, EN_TW, EN_TH, batch), dim3(EN_THREADS), lds, s, gray, luts, decisions, frames, h, w, A, T, out);
+  return UNETPP_OK;
+}
+
+size_t unetpp_enhance_workspace_bytes(int batch, int h, int w, int tiles_x, int tiles_y) {
+  EnhWorkspace ws;
+  return enh_layout(batch, h, w, tiles_x, tiles_y, &ws) ? ws.total : 0;
+}
+
+int unetpp_enhance_layout(int* tile_rows, int* tile_cols) {
+  if (!tile_rows || !tile_cols) return fail(nullptr, UNETPP_E_INVALID, "null argument");
+  *tile_rows = EN_TH;
+  *tile_cols = EN_TW;
+  return UNETPP_OK;
+}
+
+int unetpp_gray_decision(unetpp_engine* e, const uint8_t* dev_frames, int batch, int h, int w, double threshold, uint8_t* dev_decisions,
+                         uint64_t* dev_sums, void* stream) {
+  REQUIRE_ARGS(e, dev_frames && dev_decisions && dev_sums);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  if ((uintptr_t)dev_sums % 8) return fail(e, UNETPP_E_INVALID, "dev_sums must be 8-byte aligned");
+  if (threshold != threshold) return fail(e, UNETPP_E_INVALID, "threshold is not a number");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  EnhGrid g{1, 1, w, h, h, w};                               // one tile: the image
+  HIP_TRY(e, hipMemsetAsync(dev_sums, 0, (size_t)batch * 3 * sizeof(uint64_t), s));
+  enh_launch_stats(s, dev_frames, batch, h, w, 3, g, nullptr, nullptr, (unsigned long long*)dev_sums);
+  hipLaunchKernelGGL(enhance_decide_kernel, dim3((unsigned)((batch + EN_THREADS - 1) / EN_THREADS)), dim3(EN_THREADS), 0, s,
+                     (const unsigned long long*)dev_sums, batch, (double)h * (double)w, threshold, dev_decisions);
+  return launched(e);
+}
+
+int unetpp_bilateral_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h, int w, const unetpp_bilateral_tables* tables,
+                        uint8_t* dev_out, void* stream) {
+  REQUIRE_ARGS(e, dev_gray && dev_out && tables);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  EnhTables T;
+  if (const int rc = enh_tables(e, nullptr, tables, h, w, &T)) return rc;
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_gray, n, dev_out, n)) return fail(e, UNETPP_E_INVALID, "dev_out aliases dev_gray: workgroups read halo pixels their neighbours write");
+  ENTER_DEVICE(e);
+  const int lrc = enh_launch_apply(e, (hipStream_t)stream, dev_gray, nullptr, nullptr, nullptr, batch, h, w, nullptr, 1, 1, T, dev_out);
+  return lrc != UNETPP_OK ? lrc : launched(e);
+}
+
+int unetpp_enhance_u8(unetpp_engine* e, const uint8_t* dev_frames, int batch, int h, int w, int channels_in, int channels_out, int mode,
+                      double threshold, double clip_limit, int tiles_x, int tiles_y, const uint8_t* gamma_table,
+                      const unetpp_bilateral_tables* tables, uint8_t* dev_out, uint8_t* dev_luts, uint8_t* dev_decisions, void* dev_workspace,
+                      void* stream) {
+  REQUIRE_ARGS(e, dev_frames && dev_out && dev_workspace);
+  if ((channels_in != 1 && channels_in != 3) || (channels_out != 1 && channels_out != 3))
+    return fail(e, UNETPP_E_INVALID, "channels %d -> %d: each 1 or 3", channels_in, channels_out);
+  if (mode != UNETPP_ENHANCE_ALWAYS && mode != UNETPP_ENHANCE_IF_GREY) return fail(e, UNETPP_E_INVALID, "unknown mode %d", mode);
+  if (mode == UNETPP_ENHANCE_IF_GREY && channels_in == 3 && channels_out != 3)
+    return fail(e, UNETPP_E_INVALID, "UNETPP_ENHANCE_IF_GREY copies colour frames through: channels_out must be 3");
+  if (threshold != threshold || clip_limit != clip_limit) return fail(e, UNETPP_E_INVALID, "threshold or clip_limit is not a number");
+  EnhWorkspace ws;
+  if (!enh_layout(batch, h, w, tiles_x, tiles_y, &ws))
+    return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d with a %dx%d grid outside 1 <= tiles <= 16, h > tiles_y, w > tiles_x, h, w <= 65535, h * w <= 2^30",
+                batch, h, w, tiles_x, tiles_y);
+  if ((uintptr_t)dev_workspace % 16) return fail(e, UNETPP_E_INVALID, "dev_workspace must be 16-byte aligned");
+  if (dev_luts && (uintptr_t)dev_luts % 4) return fail(e, UNETPP_E_INVALID, "dev_luts must be 4-byte aligned");
+  EnhGrid g;
+  enh_grid(h, w, tiles_x, tiles_y, &g);
+  EnhTables T;
+  if (const int rc = enh_tables(e, gamma_table, tables, h, w, &T)) return rc;
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_frames, n * channels_in, dev_out, n * channels_out))
+    return fail(e, UNETPP_E_INVALID, "dev_out aliases dev_frames: workgroups read halo pixels their neighbours write");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  char* wsp = (char*)dev_workspace;
+  unsigned* hist = (unsigned*)(wsp + ws.hist);
+  unsigned long long* sums = (unsigned long long*)(wsp + ws.sums);
+  uint8_t* luts = dev_luts ? dev_luts : (uint8_t*)(wsp + ws.luts);
+  uint8_t* decisions = dev_decisions ? dev_decisions : (uint8_t*)(wsp + ws.decisions);
+  const bool decide = mode == UNETPP_ENHANCE_IF_GREY && channels_in == 3;      // a one-channel frame is grey by definition
+  const uint8_t* gray = channels_in == 3 ? (const uint8_t*)(wsp + ws.gray) : dev_frames;
+  const int area = g.tw * g.th;
+  HIP_TRY(e, hipMemsetAsync(hist, 0, ws.luts - ws.hist, s));
+  enh_launch_stats(s, dev_frames, batch, h, w, channels_in, g, channels_in == 3 ? (uint8_t*)(wsp + ws.gray) : nullptr, hist,
+                   channels_in == 3 ? sums : nullptr);
+  hipLaunchKernelGGL(clahe_lut_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)batch), dim3(EN_THREADS), 0, s, (const unsigned*)hist,
+                     enh_clip(clip_limit, area), 255.0f / (float)area, luts, (const unsigned long long*)sums, (double)h * (double)w, threshold,
+                     decide ? 0 : 1, (decide || dev_decisions) ? decisions : (uint8_t*)nullptr);
+  const int lrc = enh_launch_apply(e, s, gray, luts, decide ? decisions : nullptr, dev_frames, batch, h, w, &g, channels_in, channels_out, T, dev_out);
+  return lrc != UNETPP_OK ? lrc : launched(e);
+}
+
+int unetpp_clahe_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h, int w, double clip_limit, int tiles_x, int tiles_y,
+                    uint8_t* dev_out, uint8_t* dev_luts, void* dev_workspace, void* stream) {
+  return unetpp_enhance_u8(e, dev_gray, batch, h, w, 1, 1, UNETPP_ENHANCE_ALWAYS, 0.0, clip_limit, tiles_x, tiles_y, nullptr, nullptr, dev_out,
+                           dev_luts, nullptr, dev_workspace, stream);
+}
+
+// ---- binary morphology programs (morphology.h) ------------------------------------------------------------------
+struct MorphPlan {
+  MorphArgs args;
+  dim3 grid;
+  size_t lds_bytes = 0;
+};
+
+// Checks a program and lays its tiles out.  Everything the kernel indexes with is validated here.
+static int morph_plan(unetpp_engine* e, int batch, int h, int w, const unetpp_morph_element* elements, int n_elements,
+                      const unetpp_morph_step* steps, int n_steps, int result_plane, MorphPlan* plan) {
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if (n_elements < 0 || n_elements > MORPH_MAX_ELEMENTS || (n_elements > 0 && !elements))
+    return fail(e, UNETPP_E_INVALID, "n_elements %d not in [0,%d]", n_elements, MORPH_MAX_ELEMENTS);
+  if (n_steps < 0 || n_steps > MORPH_MAX_STEPS || (n_steps > 0 && !steps))
+    return fail(e, UNETPP_E_INVALID, "n_steps %d not in [0,%d]", n_steps, MORPH_MAX_STEPS);
+  MorphArgs& A = plan->args;
+  std::memset(&A, 0, sizeof A);
+  int ax[MORPH_MAX_ELEMENTS], ay[MORPH_MAX_ELEMENTS];
+  for (int k = 0; k < n_elements; ++k) {
+    const unetpp_morph_element& el = elements[k];
+    if (el.kw < 1 || el.kh < 1 || !el.host_data) return fail(e, UNETPP_E_INVALID, "element %d: bad size %dx%d or NULL data", k, el.kw, el.kh);
+    if (el.kw > MORPH_MAX_K || el.kh > MORPH_MAX_K)
+      return fail(e, UNETPP_E_UNSUPPORTED, "element %d is %dx%d: too large, at most %dx%d", k, el.kw, el.kh, MORPH_MAX_K, MORPH_MAX_K);
+    ax[k] = el.ax < 0 ? el.kw / 2 : el.ax;
+    ay[k] = el.ay < 0 ? el.kh / 2 : el.ay;
+    if (ax[k] >= el.kw || ay[k] >= el.kh) return fail(e, UNETPP_E_INVALID, "element %d: anchor (%d,%d) outside %dx%d", k, el.ax, el.ay, el.kw, el.kh);
+    MorphElem& E = A.elem[k];
+    for (int i = 0; i < el.kh; ++i) {
+      const uint8_t* r = el.host_data + (size_t)i * el.kw;
+      int first = -1, last = -1, count = 0;
+      for (int j = 0; j < el.kw; ++j)
+        if (r[j]) { if (first < 0) first = j; last = j; ++count; }
+      if (!count) continue;
+      if (count != last - first + 1)
+        return fail(e, UNETPP_E_UNSUPPORTED, "element %d is not row-convex: the non-zeros of row %d are not one run", k, i);
+      E.row[E.nrows++] = MorphRow{(signed char)(i - ay[k]), (signed char)(first - ax[k]), (signed char)(last - ax[k]), 0};
+    }
+    if (!E.nrows) return fail(e, UNETPP_E_INVALID, "element %d is empty (all zero)", k);
+    std::sort(E.row, E.row + E.nrows, [](const MorphRow& p, const MorphRow& q) {
+      return std::make_tuple(p.lo, p.hi, p.dy) < std::make_tuple(q.lo, q.hi, q.dy);
+    });
+  }
+  bool written[MORPH_USER_PLANES] = {true, true, false, false};     // plane 1 is all zero without a second mask
+  auto plane_ok = [](int p) { return p >= 0 && p < MORPH_USER_PLANES; };
+  int up = 0, down = 0, left = 0, right = 0;
+  for (int s = 0; s < n_steps; ++s) {
+    const unetpp_morph_step& st = steps[s];
+    if (st.op < UNETPP_MORPH_DILATE || st.op > UNETPP_MORPH_COPY) return fail(e, UNETPP_E_INVALID, "step %d: unknown op %d", s, st.op);
+    const bool morph = st.op == UNETPP_MORPH_DILATE || st.op == UNETPP_MORPH_ERODE;
+    const bool binary = st.op == UNETPP_MORPH_AND || st.op == UNETPP_MORPH_ANDNOT || st.op == UNETPP_MORPH_OR;
+    if (!plane_ok(st.dst) || !plane_ok(st.a) || (binary && !plane_ok(st.b)))
+      return fail(e, UNETPP_E_INVALID, "step %d: plane index out of range [0,%d)", s, MORPH_USER_PLANES);
+    if (!written[st.a] || (binary && !written[st.b]))
+      return fail(e, UNETPP_E_INVALID, "step %d reads scratch plane %d before any step has written it", s, !written[st.a] ? st.a : st.b);
+    MorphStep& D = A.step[s];
+    D.op = st.op; D.dst = st.dst; D.a = st.a; D.b = binary ? st.b : st.a; D.elem = 0; D.iters = 1;
+    if (morph) {
+      if (st.element < 0 || st.element >= n_elements) return fail(e, UNETPP_E_INVALID, "step %d: element index %d not in [0,%d)", s, st.element, n_elements);
+      if (st.iterations < 1) return fail(e, UNETPP_E_INVALID, "step %d: iterations must be at least 1, got %d", s, st.iterations);
+      if (st.iterations > MORPH_MAX_REACH) return fail(e, UNETPP_E_UNSUPPORTED, "step %d: iterations %d beyond %d", s, st.iterations, MORPH_MAX_REACH);
+      D.elem = st.element; D.iters = st.iterations;
+      const unetpp_morph_element& el = elements[st.element];
+      up += st.iterations * ay[st.element]; down += st.iterations * (el.kh - 1 - ay[st.element]);
+      left += st.iterations * ax[st.element]; right += st.iterations * (el.kw - 1 - ax[st.element]);
+      if (up + down > MORPH_MAX_REACH || left + right > MORPH_MAX_REACH)
+        return fail(e, UNETPP_E_UNSUPPORTED, "the program's reach (sum of iterations * (k - 1) over its dilates and erodes) exceeds %d pixels "
+                    "(vertical %d, horizontal %d)", MORPH_MAX_REACH, up + down, left + right);
+    }
+    written[st.dst] = true;
+  }
+  if (!plane_ok(result_plane) || !written[result_plane])
+    return fail(e, UNETPP_E_INVALID, "result_plane %d is out of range or never written", result_plane);
+  A.n_steps = n_steps; A.result = result_plane;
+  A.H = h; A.W = w; A.wpr = (w + 63) / 64;
+  const int halo = up + down;
+  int band_max;
+  if (A.wpr * (halo + 1) <= MORPH_PLANE_WORDS) {            // bands of full-width rows: no horizontal halo
+    A.cw = A.wpr; A.hl = 0; A.tw = A.wpr;
+    band_max = MORPH_PLANE_WORDS / A.wpr - halo;
+    // enough workgroups to fill the device before the bands grow: at most as much halo as core, never below 16 rows
+    int band = std::min(std::max(halo, 16), band_max);
+    while ((long long)batch * ((h + band - 1) / band) > 2048 && band * 2 <= band_max) band *= 2;
+    band = std::min(band, h);
+    // one thread per word and pass: grow the band until the window's words fill whole passes of the workgroup
+    int unit = MORPH_THREADS;
+    for (int a = MORPH_THREADS, b = A.wpr; b;) { const int r = a % b; a = b; b = r; unit = MORPH_THREADS / a; }
+    const int rows_up = (band + halo + unit - 1) / unit * unit;
+    if (rows_up - halo <= std::min(band_max, h)) band = rows_up - halo;
+    A.band = band;
+  } else {                                                  // tiles with a halo on all four sides: the best core share
+    const int hl = (left + 63) / 64, hr = (right + 63) / 64;
+    double best = -1.0;
+    for (int cw = 1; cw <= std::min(A.wpr, 64); ++cw) {
+      const int bm = std::min(MORPH_PLANE_WORDS / (cw + hl + hr) - halo, h);
+      if (bm < 1) break;
+      const double share = (double)cw * bm / ((double)(cw + hl + hr) * (bm + halo));
+      if (share > best) { best = share; A.cw = cw; A.band = bm; }
+    }
+    A.hl = hl; A.tw = A.cw + hl + hr;
+  }
+  A.up = up; A.rows = A.band + halo;
+  plan->grid = tile_grid(A.wpr, h, A.cw, A.band, batch);
+  plan->lds_bytes = (size_t)MORPH_PLANES * A.rows * A.tw * sizeof(unsigned long long);
+  if (A.band < 1 || A.rows * A.tw > MORPH_PLANE_WORDS) return fail(e, UNETPP_E_STATE, "internal: morphology tile layout");
+  return UNETPP_OK;
+}
+
+int unetpp_morphology_layout(int batch, int h, int w, const unetpp_morph_element* elements, int n_elements,
+                             const unetpp_morph_step* steps, int n_steps, int* band_rows, int* tile_cols) {
+  if (!band_rows || !tile_cols) return fail(nullptr, UNETPP_E_INVALID, "null argument");
+  MorphPlan plan;
+  if (const int rc = morph_plan(nullptr, batch, h, w, elements, n_elements, steps, n_steps, n_steps > 0 ? steps[n_steps - 1].dst : 0, &plan)) return rc;
+  *band_rows = plan.args.band;
+  *tile_cols = plan.args.cw * 64;
+  return UNETPP_OK;
+}
+
+int unetpp_morphology(unetpp_engine* e, const uint8_t* dev_mask0, int match0, const uint8_t* dev_mask1, int match1, int batch,
+                      int h, int w, const unetpp_morph_element* elements, int n_elements, const unetpp_morph_step* steps,
+                      int n_steps, int result_plane, uint8_t out_value, uint8_t* dev_out, void* stream) {
+  REQUIRE_ARGS(e, dev_mask0 && dev_out);
+  if (match0 > 255 || match1 > 255) return fail(e, UNETPP_E_INVALID, "match_class %d out of range", match0 > 255 ? match0 : match1);
+  MorphPlan plan;
+  if (const int rc = morph_plan(e, batch, h, w, elements, n_elements, steps, n_steps, result_plane, &plan)) return rc;
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_mask0, n, dev_out, n) || (dev_mask1 && overlaps(dev_mask1, n, dev_out, n)))
+    return fail(e, UNETPP_E_INVALID, "dev_out aliases an input mask: every workgroup reads the halo rows its neighbours write");
+  ENTER_DEVICE(e);
+  MorphArgs& A = plan.args;
+  A.match0 = match0; A.match1 = match1; A.out_value = out_value;
+  A.vec0 = vec16(w, dev_mask0); A.vec1 = vec16(w, dev_mask1); A.vec_out = vec16(w, dev_out);
+  hipLaunchKernelGGL(morph_program_kernel, plan.grid, dim3(MORPH_THREADS), plan.lds_bytes, (hipStream_t)stream, dev_mask0, dev_mask1,
+                     dev_out, A);
+  return launched(e);
+}
+
+// ---- frame glue: cv2.resize either side of the model ----------------------------------
+// resizeGeneric_'s INTER_LINEAR index/coefficient tables (OpenCV imgproc/src/resize.cpp): double index math, float
+// fraction.  Entry = {s0, s1, a0, a1} with a = saturate_cast<short>(c * 2048), round-half-even, for the uint8 resize; with
+// as_f32 the same indices and the bits of the float coefficients 1 - fx and fx of the float32 resize (tiling.h).
+static void linear_table(int n_src, int n_dst, bool as_f32, std::vector<int>& t) {
+#pragma clang fp contract(off)
+  t.resize((size_t)n_dst * 4);
+  const double inv_scale = (double)n_dst / (double)n_src;
+  const double scale = 1.0 / inv_scale;
+  for (int d = 0; d < n_dst; ++d) {
+    float fx = (float)((d + 0.5) * scale - 0.5);
+    int s0 = (int)floorf(fx);
+    fx -= (float)s0;
+    if (s0 < 0) { fx = 0.f; s0 = 0; }
+    if (s0 >= n_src - 1) { fx = 0.f; s0 = n_src - 1; }
+    const float c0 = 1.f - fx;
+    int a0, a1;
+    if (as_f32) {
+      std::memcpy(&a0, &c0, sizeof a0);
+      std::memcpy(&a1, &fx, sizeof a1);
+    } else {
+      a0 = (int)std::min(32767L, std::max(-32768L, lrintf(c0 * 2048.f)));
+      a1 = (int)std::min(32767L, std::max(-32768L, lrintf(fx * 2048.f)));
+    }
+    t[4 * d + 0] = s0; t[4 * d + 1] = std::min(s0 + 1, n_src - 1); t[4 * d + 2] = a0; t[4 * d + 3] = a1;
+  }
+}
+// resizeNN's index table: min(floor(d * (1 / (n_dst / n_src))), n_src - 1) in double.
+static void nearest_table(int n_src, int n_dst, std::vector<int>& t) {
+#pragma clang fp contract(off)
+  t.resize((size_t)n_dst);
+  const double inv = (double)n_dst / (double)n_src;
+  const double ifx = 1.0 / inv;
+  for (int d = 0; d < n_dst; ++d) t[d] = std::min((int)floor(d * ifx), n_src - 1);
+}
+// Device copy of a table, built on first use (that first call synchronises: a blocking hipMemcpy).
+static int resize_table(unetpp_engine* e, int kind, int n_src, int n_dst, void** out) {
+  auto& tabs = unetpp_common(e)->resize_tabs;
+  auto key = std::make_tuple(kind, n_src, n_dst);
+  auto it = tabs.find(key);
+  if (it == tabs.end()) {
+    std::vector<int> t;
+    if (kind == 1) nearest_table(n_src, n_dst, t); else linear_table(n_src, n_dst, kind == 2, t);
+    void* d = nullptr;
+    HIP_TRY(e, hipMalloc(&d, t.size() * sizeof(int)));
+    hipError_t r = hipMemcpy(d, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (r != hipSuccess) { (void)hipFree(d); return fail(e, UNETPP_E_HIP, "hipMemcpy(resize table): %s", hipGetErrorString(r)); }
+    it = tabs.emplace(key, d).first;
+  }
+  *out = it->second;
+  return UNETPP_OK;
+}
+
+int unetpp_resize_linear_u8(unetpp_engine* e, const uint8_t* dev_src, int batch, int src_h, int src_w, int channels,
+                            uint8_t* dev_dst, int dst_h, int dst_w, void* stream) {
+  REQUIRE_ARGS(e, dev_src && dev_dst);
+  if (batch < 1 || src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || channels < 1 || channels > 4)
+    return fail(e, UNETPP_E_INVALID, "bad resize shape %dx%dx%dx%d -> %dx%d", batch, src_h, src_w, channels, dst_h, dst_w);
+  if (batch > 65535 || dst_h > 65535 || (size_t)src_h * src_w * channels > 0x7fffffffULL)
+    return fail(e, UNETPP_E_INVALID, "resize shape too large");
+  ENTER_DEVICE(e);
+  void *xt = nullptr, *yt = nullptr;
+  if (const int rc = resize_table(e, 0, src_w, dst_w, &xt)) return rc;
+  if (const int rc = resize_table(e, 0, src_h, dst_h, &yt)) return rc;
+  const unsigned gx = (unsigned)((dst_w * channels + 1023) / 1024);
+  hipLaunchKernelGGL(resize_linear_u8_kernel, dim3(gx, (unsigned)dst_h, (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
+                     dev_src, src_h, src_w, channels, dev_dst, dst_h, dst_w, (const int4*)xt, (const int4*)yt);
+  return launched(e);
+}
+
+int unetpp_resize_nearest_roi_u8(unetpp_engine* e, const uint8_t* dev_src, int batch, int src_h, int src_w, int match_class,
+                                 uint8_t* dev_dst, int dst_h, int dst_w, int x1, int y1, int x2, int y2, void* stream) {
+  REQUIRE_ARGS(e, dev_src && dev_dst);
+  if (batch < 1 || src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1)
+    return fail(e, UNETPP_E_INVALID, "bad resize shape %dx%dx%d -> %dx%d", batch, src_h, src_w, dst_h, dst_w);
+  if (batch > 65535 || dst_h > 65535) return fail(e, UNETPP_E_INVALID, "resize shape too large");
+  if (x1 < 0 || y1 < 0 || x2 < 0 || y2 < 0) return fail(e, UNETPP_E_INVALID, "negative ROI bound (%d, %d, %d, %d)", x1, y1, x2, y2);
+  if (match_class > 255) return fail(e, UNETPP_E_INVALID, "match_class %d out of range", match_class);
+  ENTER_DEVICE(e);
+  void *xo = nullptr, *yo = nullptr;
+  if (const int rc = resize_table(e, 1, src_w, dst_w, &xo)) return rc;
+  if (const int rc = resize_table(e, 1, src_h, dst_h, &yo)) return rc;
+  const unsigned gx = (unsigned)((dst_w + 1023) / 1024);
+  hipLaunchKernelGGL(resize_nearest_roi_u8_kernel, dim3(gx, (unsigned)dst_h, (unsigned)batch), dim3(256), 0, (hipStream_t)stream,
+                     dev_src, src_h, src_w, dev_dst, dst_h, dst_w, (const int*)xo, (const int*)yo, match_class, x1, y1, x2, y2);
+  return launched(e);
+}
+
+// ---- sliding-window inference: gather tiles, gate, blend (tiling.h) ------------------------------------------
+// Checks a separable plan against the frame and copies it.  Everything the kernels index with is validated here.
+static int tile_plan_check(unetpp_engine* e, int h, int w, const int32_t* oy, int n_y, const int32_t* ox, int n_x, int patch_size,
+                           bool reflect, TilePlan* plan) {
+  if (!oy || !ox) return fail(e, UNETPP_E_INVALID, "null argument");
+  if (!shape_ok(1, h, w, ROWS_SHAPE) || patch_size < 1 || patch_size > 65535)
+    return fail(e, UNETPP_E_INVALID, "bad shape %dx%d, patch_size %d", h, w, patch_size);
+  if (n_y < 1 || n_x < 1) return fail(e, UNETPP_E_INVALID, "empty plan %dx%d", n_y, n_x);
+  if (n_y > TILE_MAX_AXIS || n_x > TILE_MAX_AXIS)
+    return fail(e, UNETPP_E_UNSUPPORTED, "plan of %dx%d patches: at most %d per axis", n_y, n_x, TILE_MAX_AXIS);
+  plan->ny = n_y; plan->nx = n_x;
+  for (int a = 0; a < 2; ++a) {
+    const int n = a ? w : h, cnt = a ? n_x : n_y;
+    const int32_t* o = a ? ox : oy;
+    for (int i = 0; i < cnt; ++i) {
+      if (o[i] < 0 || o[i] >= n) return fail(e, UNETPP_E_INVALID, "origin %d outside an axis of %d", o[i], n);
+      if (reflect && o[i] + patch_size - 1 > 2 * (n - 1))
+        return fail(e, UNETPP_E_UNSUPPORTED, "patch of %d at %d on an axis of %d: reflect padding of the axis length or more", patch_size, o[i], n);
+      (a ? plan->ox : plan->oy)[i] = o[i];
+    }
+  }
+  return UNETPP_OK;
+}
+
+int unetpp_tile_gather_u8(unetpp_engine* e, const uint8_t* dev_frames, int batch, int h, int w, const int32_t* origins_y, int n_y,
+                          const int32_t* origins_x, int n_x, int patch_size, int t, int channel_order, uint8_t* dev_patches,
+                          void* stream) {
+  REQUIRE_ARGS(e, dev_frames && dev_patches);
+  if (batch < 1 || t < 4 || t % 4 || t > 16384) return fail(e, UNETPP_E_INVALID, "bad batch %d or patch size %d (a multiple of 4)", batch, t);
+  if (channel_order != UNETPP_TILE_BGR && channel_order != UNETPP_TILE_RGB) return fail(e, UNETPP_E_INVALID, "channel_order %d", channel_order);
+  TilePlan plan;
+  if (const int rc = tile_plan_check(e, h, w, origins_y, n_y, origins_x, n_x, patch_size, true, &plan)) return rc;
+  if ((long long)batch * n_y * n_x > 65535) return fail(e, UNETPP_E_INVALID, "%d x %d x %d patches: at most 65535 per call", batch, n_y, n_x);
+  if ((size_t)h * w * 3 > 0x7fffffffULL) return fail(e, UNETPP_E_INVALID, "frame too large");
+  ENTER_DEVICE(e);
+  void* tab = nullptr;
+  if (const int rc = resize_table(e, 0, patch_size, t, &tab)) return rc;
+  hipLaunchKernelGGL(tile_gather_u8_kernel, dim3((unsigned)((t * 3 + 1023) / 1024), (unsigned)t, (unsigned)(batch * n_y * n_x)),
+                     dim3(TILE_THREADS), 0, (hipStream_t)stream, dev_frames, h, w, plan, t, (int)(channel_order == UNETPP_TILE_RGB),
+                     (const int4*)tab, (const int4*)tab, dev_patches);
+  return launched(e);
+}
+
+int unetpp_tile_gate_f32(unetpp_engine* e, const float* dev_maps, int n, int classes, int t, int gate_class, float gate_thr,
+                         float* dev_scores, uint8_t* dev_include, void* stream) {
+  REQUIRE_ARGS(e, dev_maps && dev_scores && dev_include);
+  if (n < 1 || classes < 1 || t < 2 || t % 2 || t > 16384) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%dx%d", n, classes, t, t);
+  if (gate_class < 0 || gate_class >= classes) return fail(e, UNETPP_E_INVALID, "gate_class %d not in [0,%d)", gate_class, classes);
+  if ((uintptr_t)dev_maps % 16) return fail(e, UNETPP_E_INVALID, "dev_maps must be 16-byte aligned");
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(tile_gate_f32_kernel, dim3((unsigned)n), dim3(TILE_THREADS), 0, (hipStream_t)stream, dev_maps, classes, t, gate_class,
+                     gate_thr, dev_scores, dev_include);
+  return launched(e);
+}
+
+int unetpp_tile_blend_f32(unetpp_engine* e, const float* dev_maps, int batch, int classes, int t, const int32_t* origins_y, int n_y,
+                          const int32_t* origins_x, int n_x, int patch_size, const uint8_t* dev_include, int h, int w,
+                          uint8_t* dev_mask, float* dev_output, void* stream) {
+  REQUIRE_ARGS(e, dev_maps && dev_mask);
+  if (batch < 1 || batch > 65535 || classes < 1 || t < 1 || t > 16384) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%dx%d", batch, classes, t, t);
+  if (classes > TILE_MAX_CLASSES) return fail(e, UNETPP_E_UNSUPPORTED, "%d classes: at most %d", classes, TILE_MAX_CLASSES);
+  TilePlan plan;
+  if (const int rc = tile_plan_check(e, h, w, origins_y, n_y, origins_x, n_x, patch_size, false, &plan)) return rc;
+  ENTER_DEVICE(e);
+  void* tab = nullptr;
+  if (const int rc = resize_table(e, 2, t, patch_size, &tab)) return rc;
+  const dim3 grid = tile_grid(w, h, TILE_WAVE, TILE_BLEND_ROWS, batch);
+#define TILE_BLEND_CASE(C)                                                                                                       \
+  case C:                                                                                                                        \
+    hipLaunchKernelGGL(tile_blend_f32_kernel<C>, grid, dim3(TILE_THREADS), 0, (hipStream_t)stream, dev_maps, plan, patch_size, t, \
+                       (const int4*)tab, (const int4*)tab, dev_include, h, w, dev_mask, dev_output);                             \
+    break
+  switch (classes) {
+    TILE_BLEND_CASE(1); TILE_BLEND_CASE(2); TILE_BLEND_CASE(3); TILE_BLEND_CASE(4);
+    TILE_BLEND_CASE(5); TILE_BLEND_CASE(6); TILE_BLEND_CASE(7); TILE_BLEND_CASE(8);
+  }
+#undef TILE_BLEND_CASE
+  return launched(e);
+}
+
+}  // extern "C"

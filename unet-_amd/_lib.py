@@ -16,26 +16,6 @@ CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["unetpp_abi.hip", "unetpp_postproc.hip"]      # the engine; the post-processing entry points
 HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "frame_kernels.h", "components.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "geometry.h", "tiling.h", os.path.join("..", "..", "include", "unetpp.h")]
 
-# every symbol include/unetpp.h declares
-ABI_SYMBOLS = [
-    "unetpp_create", "unetpp_destroy", "unetpp_last_error", "unetpp_version", "unetpp_weights_blob_bytes",
-    "unetpp_weights_blob_bytes_arch",
-    "unetpp_load_weights", "unetpp_load_weights_device", "unetpp_forward", "unetpp_forward_ex", "unetpp_mask_stats", "unetpp_workspace_bytes",
-    "unetpp_resize_linear_u8", "unetpp_resize_nearest_roi_u8", "unetpp_status",
-    "unetpp_profile_enable", "unetpp_profile_count", "unetpp_profile_read", "unetpp_profile_name",
-    "unetpp_profile_work", "unetpp_debug_read", "unetpp_debug_keep_intermediates",
-    "unetpp_ds_blob_bytes", "unetpp_load_ds_heads", "unetpp_forward_ds",
-    "unetpp_components_workspace_bytes", "unetpp_components", "unetpp_components_filter",
-    "unetpp_morphology", "unetpp_morphology_layout",
-    "unetpp_gray_u8", "unetpp_gaussian_blur_u8", "unetpp_canny_workspace_bytes", "unetpp_canny_layout", "unetpp_canny_u8",
-    "unetpp_laplacian_band_u8", "unetpp_components_filter_box",
-    "unetpp_edges_union_workspace_bytes", "unetpp_edges_union_u8", "unetpp_dog_band_u8", "unetpp_count_nonzero_u8",
-    "unetpp_row_widths", "unetpp_width_profile", "unetpp_components_summary",
-    "unetpp_tile_gather_u8", "unetpp_tile_gate_f32", "unetpp_tile_blend_f32",
-    "unetpp_gray_decision", "unetpp_clahe_u8", "unetpp_bilateral_u8", "unetpp_enhance_u8", "unetpp_enhance_workspace_bytes",
-    "unetpp_enhance_layout",
-]
-
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
 PREC_EXACT, PREC_FAST, PREC_EXACT8 = 0, 1, 2
 PRECISIONS = {"exact": PREC_EXACT, "fast": PREC_FAST, "exact8": PREC_EXACT8}
@@ -91,6 +71,70 @@ class Outputs(ctypes.Structure):
                 ("t_cable", ctypes.c_float), ("t_tape", ctypes.c_float), ("bg_margin", ctypes.c_float),
                 ("ct_margin", ctypes.c_float)]
 
+
+vp, ci, cs, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
+i32p, f32p, u8p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint8)
+btp = ctypes.POINTER(BilateralTables)
+
+# every symbol include/unetpp.h declares: name -> (restype, argtypes); load() applies it
+ABI = {
+    "unetpp_create": (ci, [ctypes.POINTER(Config), ctypes.POINTER(vp)]),
+    "unetpp_destroy": (None, [vp]),
+    "unetpp_last_error": (ctypes.c_char_p, [vp]),
+    "unetpp_version": (ctypes.c_char_p, []),
+    "unetpp_weights_blob_bytes": (cs, [ci, ci]),
+    "unetpp_weights_blob_bytes_arch": (cs, [ci, ci, ci]),
+    "unetpp_load_weights": (ci, [vp, vp, cs]),
+    "unetpp_load_weights_device": (ci, [vp, vp, cs, vp]),
+    "unetpp_forward": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "unetpp_forward_ex": (ci, [vp, vp, ci, ci, ci, ci, ctypes.POINTER(Outputs), vp]),
+    "unetpp_mask_stats": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, vp]),
+    "unetpp_resize_linear_u8": (ci, [vp, vp, ci, ci, ci, ci, vp, ci, ci, vp]),
+    "unetpp_resize_nearest_roi_u8": (ci, [vp, vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, ci, ci, vp]),
+    "unetpp_workspace_bytes": (cs, [vp]),
+    "unetpp_status": (ci, [vp, ctypes.POINTER(ctypes.c_uint32), ci]),
+    "unetpp_profile_enable": (ci, [vp, ci]),
+    "unetpp_profile_count": (ci, [vp]),
+    "unetpp_profile_read": (ci, [vp, f32p, ci]),
+    "unetpp_profile_name": (ctypes.c_char_p, [vp, ci]),
+    "unetpp_profile_work": (ci, [vp, ci, ctypes.POINTER(cd), ctypes.POINTER(cd)]),
+    "unetpp_debug_read": (ctypes.c_longlong, [vp, ctypes.c_char_p, f32p, cs]),
+    "unetpp_debug_keep_intermediates": (ci, [vp, ci]),
+    "unetpp_ds_blob_bytes": (cs, [ci]),
+    "unetpp_load_ds_heads": (ci, [vp, vp, cs]),
+    "unetpp_forward_ds": (ci, [vp, vp, ci, ci, ci, ci, ctypes.POINTER(ctypes.POINTER(Outputs)), vp]),
+    "unetpp_components_workspace_bytes": (cs, [ci, ci, ci, ci]),
+    "unetpp_components": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
+    "unetpp_components_filter": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(CcRule), ctypes.c_uint8, vp, vp, vp]),
+    "unetpp_morphology": (ci, [vp, vp, ci, vp, ci, ci, ci, ci, ctypes.POINTER(MorphElement), ci, ctypes.POINTER(MorphStep), ci, ci,
+                               ctypes.c_uint8, vp, vp]),
+    "unetpp_morphology_layout": (ci, [ci, ci, ci, ctypes.POINTER(MorphElement), ci, ctypes.POINTER(MorphStep), ci,
+                                      ctypes.POINTER(ci), ctypes.POINTER(ci)]),
+    "unetpp_gray_u8": (ci, [vp, vp, ci, ci, ci, vp, vp]),
+    "unetpp_gaussian_blur_u8": (ci, [vp, vp, ci, ci, ci, i32p, ci, vp, vp]),
+    "unetpp_canny_workspace_bytes": (cs, [ci, ci, ci]),
+    "unetpp_canny_layout": (ci, [ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]),
+    "unetpp_canny_u8": (ci, [vp, vp, ci, ci, ci, i32p, ci, cd, cd, vp, vp, vp]),
+    "unetpp_laplacian_band_u8": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp]),
+    "unetpp_components_filter_box": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ctypes.POINTER(CcBoxRule), ctypes.c_uint8, vp, vp, vp]),
+    "unetpp_edges_union_workspace_bytes": (cs, [ci]),
+    "unetpp_edges_union_u8": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]),
+    "unetpp_dog_band_u8": (ci, [vp, vp, vp, ci, ci, ci, i32p, ci, i32p, ci, ci, vp, vp]),
+    "unetpp_count_nonzero_u8": (ci, [vp, vp, ci, ci, ci, vp, vp]),
+    "unetpp_row_widths": (ci, [vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp]),
+    "unetpp_width_profile": (ci, [vp, vp, ci, ci, f32p, ci, ci, vp, vp, vp, vp, vp]),
+    "unetpp_components_summary": (ci, [vp, vp, vp, ci, ci, ctypes.c_int64, vp, vp]),
+    "unetpp_tile_gather_u8": (ci, [vp, vp, ci, ci, ci, i32p, ci, i32p, ci, ci, ci, ci, vp, vp]),
+    "unetpp_tile_gate_f32": (ci, [vp, vp, ci, ci, ci, ci, ctypes.c_float, vp, vp, vp]),
+    "unetpp_tile_blend_f32": (ci, [vp, vp, ci, ci, ci, i32p, ci, i32p, ci, ci, vp, ci, ci, vp, vp, vp]),
+    "unetpp_gray_decision": (ci, [vp, vp, ci, ci, ci, cd, vp, vp, vp]),
+    "unetpp_clahe_u8": (ci, [vp, vp, ci, ci, ci, cd, ci, ci, vp, vp, vp, vp]),
+    "unetpp_bilateral_u8": (ci, [vp, vp, ci, ci, ci, btp, vp, vp]),
+    "unetpp_enhance_u8": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, cd, cd, ci, ci, u8p, btp, vp, vp, vp, vp, vp]),
+    "unetpp_enhance_workspace_bytes": (cs, [ci, ci, ci, ci, ci]),
+    "unetpp_enhance_layout": (ci, [ctypes.POINTER(ci), ctypes.POINTER(ci)]),
+}
+ABI_SYMBOLS = list(ABI)
 
 # -fno-slp-vectorize: the SLP vectoriser turns pairs of float operations into v_pk_mul_f32 / v_pk_fma_f32, and a packed
 # fp32 instruction issued beside another wave's MFMA stream on the same SIMD takes 26-58 cycles instead of 5-7
@@ -186,74 +230,9 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
             raise RuntimeError(f"{LIB_PATH} {what}: build it with __graft_entry__.build(); there is no CPU fallback")
         build()
     lib = ctypes.CDLL(LIB_PATH)
-    vp, ci, cs = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    lib.unetpp_create.argtypes = [ctypes.POINTER(Config), ctypes.POINTER(vp)]; lib.unetpp_create.restype = ci
-    lib.unetpp_destroy.argtypes = [vp]; lib.unetpp_destroy.restype = None
-    lib.unetpp_last_error.argtypes = [vp]; lib.unetpp_last_error.restype = ctypes.c_char_p
-    lib.unetpp_version.argtypes = []; lib.unetpp_version.restype = ctypes.c_char_p
-    lib.unetpp_weights_blob_bytes.argtypes = [ci, ci]; lib.unetpp_weights_blob_bytes.restype = cs
-    lib.unetpp_weights_blob_bytes_arch.argtypes = [ci, ci, ci]; lib.unetpp_weights_blob_bytes_arch.restype = cs
-    lib.unetpp_load_weights.argtypes = [vp, vp, cs]; lib.unetpp_load_weights.restype = ci
-    lib.unetpp_load_weights_device.argtypes = [vp, vp, cs, vp]; lib.unetpp_load_weights_device.restype = ci
-    lib.unetpp_forward.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]; lib.unetpp_forward.restype = ci
-    lib.unetpp_forward_ex.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.POINTER(Outputs), vp]; lib.unetpp_forward_ex.restype = ci
-    lib.unetpp_mask_stats.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp]; lib.unetpp_mask_stats.restype = ci
-    lib.unetpp_resize_linear_u8.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, ci, vp]; lib.unetpp_resize_linear_u8.restype = ci
-    lib.unetpp_resize_nearest_roi_u8.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, ci, ci, vp]
-    lib.unetpp_resize_nearest_roi_u8.restype = ci
-    lib.unetpp_workspace_bytes.argtypes = [vp]; lib.unetpp_workspace_bytes.restype = cs
-    lib.unetpp_status.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32), ci]; lib.unetpp_status.restype = ci
-    lib.unetpp_profile_enable.argtypes = [vp, ci]; lib.unetpp_profile_enable.restype = ci
-    lib.unetpp_profile_count.argtypes = [vp]; lib.unetpp_profile_count.restype = ci
-    lib.unetpp_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ci]; lib.unetpp_profile_read.restype = ci
-    lib.unetpp_profile_name.argtypes = [vp, ci]; lib.unetpp_profile_name.restype = ctypes.c_char_p
-    lib.unetpp_profile_work.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-    lib.unetpp_profile_work.restype = ci
-    lib.unetpp_debug_read.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), cs]
-    lib.unetpp_debug_read.restype = ctypes.c_longlong
-    lib.unetpp_debug_keep_intermediates.argtypes = [vp, ci]; lib.unetpp_debug_keep_intermediates.restype = ci
-    lib.unetpp_ds_blob_bytes.argtypes = [ci]; lib.unetpp_ds_blob_bytes.restype = cs
-    lib.unetpp_load_ds_heads.argtypes = [vp, vp, cs]; lib.unetpp_load_ds_heads.restype = ci
-    lib.unetpp_forward_ds.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.POINTER(ctypes.POINTER(Outputs)), vp]
-    lib.unetpp_forward_ds.restype = ci
-    lib.unetpp_components_workspace_bytes.argtypes = [ci, ci, ci, ci]; lib.unetpp_components_workspace_bytes.restype = cs
-    lib.unetpp_components.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]; lib.unetpp_components.restype = ci
-    lib.unetpp_components_filter.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(CcRule), ctypes.c_uint8, vp, vp, vp]
-    lib.unetpp_components_filter.restype = ci
-    lib.unetpp_morphology.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, ctypes.POINTER(MorphElement), ci, ctypes.POINTER(MorphStep), ci, ci,
-                                      ctypes.c_uint8, vp, vp]
-    lib.unetpp_morphology.restype = ci
-    lib.unetpp_morphology_layout.argtypes = [ci, ci, ci, ctypes.POINTER(MorphElement), ci, ctypes.POINTER(MorphStep), ci,
-                                             ctypes.POINTER(ci), ctypes.POINTER(ci)]
-    lib.unetpp_morphology_layout.restype = ci
-    i32p, cd = ctypes.POINTER(ctypes.c_int32), ctypes.c_double
-    lib.unetpp_gray_u8.argtypes = [vp, vp, ci, ci, ci, vp, vp]; lib.unetpp_gray_u8.restype = ci
-    lib.unetpp_gaussian_blur_u8.argtypes = [vp, vp, ci, ci, ci, i32p, ci, vp, vp]; lib.unetpp_gaussian_blur_u8.restype = ci
-    lib.unetpp_canny_workspace_bytes.argtypes = [ci, ci, ci]; lib.unetpp_canny_workspace_bytes.restype = cs
-    lib.unetpp_canny_layout.argtypes = [ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]; lib.unetpp_canny_layout.restype = ci
-    lib.unetpp_canny_u8.argtypes = [vp, vp, ci, ci, ci, i32p, ci, cd, cd, vp, vp, vp]; lib.unetpp_canny_u8.restype = ci
-    lib.unetpp_laplacian_band_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp, vp]; lib.unetpp_laplacian_band_u8.restype = ci
-    lib.unetpp_components_filter_box.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ctypes.POINTER(CcBoxRule), ctypes.c_uint8, vp, vp, vp]
-    lib.unetpp_components_filter_box.restype = ci
-    lib.unetpp_edges_union_workspace_bytes.argtypes = [ci]; lib.unetpp_edges_union_workspace_bytes.restype = cs
-    lib.unetpp_edges_union_u8.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]; lib.unetpp_edges_union_u8.restype = ci
-    lib.unetpp_dog_band_u8.argtypes = [vp, vp, vp, ci, ci, ci, i32p, ci, i32p, ci, ci, vp, vp]; lib.unetpp_dog_band_u8.restype = ci
-    lib.unetpp_count_nonzero_u8.argtypes = [vp, vp, ci, ci, ci, vp, vp]; lib.unetpp_count_nonzero_u8.restype = ci
-    f32p = ctypes.POINTER(ctypes.c_float)
-    lib.unetpp_row_widths.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp]; lib.unetpp_row_widths.restype = ci
-    lib.unetpp_width_profile.argtypes = [vp, vp, ci, ci, f32p, ci, ci, vp, vp, vp, vp, vp]; lib.unetpp_width_profile.restype = ci
-    lib.unetpp_components_summary.argtypes = [vp, vp, vp, ci, ci, ctypes.c_int64, vp, vp]; lib.unetpp_components_summary.restype = ci
-    lib.unetpp_tile_gather_u8.argtypes = [vp, vp, ci, ci, ci, i32p, ci, i32p, ci, ci, ci, ci, vp, vp]; lib.unetpp_tile_gather_u8.restype = ci
-    lib.unetpp_tile_gate_f32.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_float, vp, vp, vp]; lib.unetpp_tile_gate_f32.restype = ci
-    lib.unetpp_tile_blend_f32.argtypes = [vp, vp, ci, ci, ci, i32p, ci, i32p, ci, ci, vp, ci, ci, vp, vp, vp]; lib.unetpp_tile_blend_f32.restype = ci
-    btp, u8p = ctypes.POINTER(BilateralTables), ctypes.POINTER(ctypes.c_uint8)
-    lib.unetpp_gray_decision.argtypes = [vp, vp, ci, ci, ci, cd, vp, vp, vp]; lib.unetpp_gray_decision.restype = ci
-    lib.unetpp_clahe_u8.argtypes = [vp, vp, ci, ci, ci, cd, ci, ci, vp, vp, vp, vp]; lib.unetpp_clahe_u8.restype = ci
-    lib.unetpp_bilateral_u8.argtypes = [vp, vp, ci, ci, ci, btp, vp, vp]; lib.unetpp_bilateral_u8.restype = ci
-    lib.unetpp_enhance_u8.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cd, cd, ci, ci, u8p, btp, vp, vp, vp, vp, vp]
-    lib.unetpp_enhance_u8.restype = ci
-    lib.unetpp_enhance_workspace_bytes.argtypes = [ci, ci, ci, ci, ci]; lib.unetpp_enhance_workspace_bytes.restype = cs
-    lib.unetpp_enhance_layout.argtypes = [ctypes.POINTER(ci), ctypes.POINTER(ci)]; lib.unetpp_enhance_layout.restype = ci
+    for name, (restype, argtypes) in ABI.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     ver = lib.unetpp_version().decode()
     if ver.endswith(" +wsdbg") and os.environ.get("UNETPP_ALLOW_DBG_LIB"):
         ver = ver[:-len(" +wsdbg")]            # measurement build with phase ablations (scripts/ws_ablate.sh)

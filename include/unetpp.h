@@ -654,6 +654,32 @@ int unetpp_enhance_u8(unetpp_engine* e, const uint8_t* dev_frames, int batch, in
                       const unetpp_bilateral_tables* tables, uint8_t* dev_out, uint8_t* dev_luts, uint8_t* dev_decisions,
                       void* dev_workspace, void* stream);
 
+/* ---- non-local-means denoising: the 'fastNlMeans' denoiser of enhance_grayscale_frame ------------------------------------
+ * cv2.fastNlMeansDenoising(img, None, h, 7, 21) (src/refactor/preprocess.py:68-69) for one 8-bit channel, as OpenCV's
+ * published FastNlMeansDenoisingInvoker<uchar, int, unsigned, DistSquared, int> computes it: the image extended by 13
+ * pixels with BORDER_REFLECT_101; per pixel and per offset (dy, dx) in [-10, 10]^2, D = the sum over the 7 x 7 window of
+ * the squared differences, w = table[D >> 6], est += w * value at the offset, wsum += w; out = (est + wsum / 2) / wsum,
+ * unsigned.  unet_amd/nlmeans.py is the NumPy form and builds the table (nlm_weights); every result equals it bit for bit,
+ * the arithmetic being integer throughout; cv2's own result is not pinned by this project's tests.
+ *
+ * unetpp_nlmeans_u8: dev_src uint8 [B,h,w,channels_in] (channel 0 is filtered) -> dev_out uint8 [B,h,w,channels_out] (the
+ *   result replicated); channels 1 or 3; 14 <= h, w <= 65535, h * w <= 2^30.  Template 7 and search window 21 are compile-time
+ *   constants.  dev_weights_u16: the first n_weights entries of the table as uint16 on the DEVICE, owned by the caller
+ *   (no engine state, no copy inside the call); every later entry counts as 0; 1 <= n_weights <= 8192; entry 0 must be
+ *   positive (it divides) and no entry above 19096 (the sums are 32-bit).  dev_decisions: NULL, or uint8 [B] on the device
+ *   (e.g. from the enhancement call above): a frame with 0 is copied through unchanged, every channel
+ *   (channels_out == channels_in then), with nothing read back.  dev_out may not overlap dev_src.  One launch,
+ *   asynchronous on `stream`.
+ *
+ * unetpp_nlmeans_layout: the rows and columns of output one workgroup owns (tests place seams with it).
+ *
+ * Errors: UNETPP_E_UNSUPPORTED for a shape or n_weights outside the limits; UNETPP_E_INVALID for NULL where not allowed,
+ * bad channels, misalignment, overlap.  No kernel is launched when an error is returned. */
+int unetpp_nlmeans_layout(int* tile_rows, int* tile_cols);
+int unetpp_nlmeans_u8(unetpp_engine* e, const uint8_t* dev_src, int batch, int h, int w, int channels_in, int channels_out,
+                      const uint8_t* dev_decisions, const uint16_t* dev_weights_u16, int n_weights, uint8_t* dev_out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

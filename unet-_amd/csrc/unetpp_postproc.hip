@@ -1,5 +1,5 @@
 // unetpp_postproc.hip — the post-processing entry points of the C ABI (include/unetpp.h): mask statistics, connected
-// components and their filters, the grey-level burr detectors, measurements, grey-frame enhancement, morphology, the two
+// components and their filters, the grey-level burr detectors, measurements, grey-frame enhancement and denoising, morphology, the two
 // resizes and the tiling of sliding-window inference.  Each entry checks its arguments and queues kernels on the caller's
 // stream.  Of an engine this file sees unetpp_engine_common (abi_common.h) and nothing else: no tensor, layer, arena or stream.
 #include <hip/hip_runtime.h>
@@ -21,6 +21,7 @@
 #include "frame_kernels.h"
 #include "geometry.h"
 #include "morphology.h"
+#include "nlmeans.h"
 #include "tiling.h"
 
 using namespace unetpp;
@@ -43,7 +44,7 @@ int launched(unetpp_engine* e) {
 struct ShapeLimits { int min_side, max_side; bool pixel_cap; };
 constexpr int MAX_DIM = 65535;
 constexpr ShapeLimits MASK_SHAPE{1, MAX_DIM, true}, EDGE_SHAPE{8, MAX_DIM, true}, BAND_SHAPE{2, MAX_DIM, true},
-                      GRAY_SHAPE{1, INT_MAX, true}, ROWS_SHAPE{1, MAX_DIM, false};
+                      GRAY_SHAPE{1, INT_MAX, true}, ROWS_SHAPE{1, MAX_DIM, false}, NLM_SHAPE{NLM_MIN_SIDE, MAX_DIM, true};
 bool shape_ok(int batch, int h, int w, const ShapeLimits& lim) {
   return batch >= 1 && batch <= MAX_DIM && h >= lim.min_side && w >= lim.min_side && h <= lim.max_side && w <= lim.max_side &&
          (!lim.pixel_cap || (size_t)h * w <= (1u << 30));
@@ -593,6 +594,36 @@ int unetpp_clahe_u8(unetpp_engine* e, const uint8_t* dev_gray, int batch, int h,
                     uint8_t* dev_out, uint8_t* dev_luts, void* dev_workspace, void* stream) {
   return unetpp_enhance_u8(e, dev_gray, batch, h, w, 1, 1, UNETPP_ENHANCE_ALWAYS, 0.0, clip_limit, tiles_x, tiles_y, nullptr, nullptr, dev_out,
                            dev_luts, nullptr, dev_workspace, stream);
+}
+
+// ---- non-local-means denoising: cv2.fastNlMeansDenoising(img, None, h, 7, 21) (nlmeans.h) ----------------------------------
+int unetpp_nlmeans_layout(int* tile_rows, int* tile_cols) {
+  if (!tile_rows || !tile_cols) return fail(nullptr, UNETPP_E_INVALID, "null argument");
+  *tile_rows = NLM_TILE_H;
+  *tile_cols = NLM_TILE_W;
+  return UNETPP_OK;
+}
+
+int unetpp_nlmeans_u8(unetpp_engine* e, const uint8_t* dev_src, int batch, int h, int w, int channels_in, int channels_out,
+                      const uint8_t* dev_decisions, const uint16_t* dev_weights_u16, int n_weights, uint8_t* dev_out, void* stream) {
+  REQUIRE_ARGS(e, dev_src && dev_weights_u16 && dev_out);
+  if ((channels_in != 1 && channels_in != 3) || (channels_out != 1 && channels_out != 3))
+    return fail(e, UNETPP_E_INVALID, "channels %d -> %d: each 1 or 3", channels_in, channels_out);
+  if (dev_decisions && channels_in != channels_out)
+    return fail(e, UNETPP_E_INVALID, "dev_decisions copies frames through: channels_out must equal channels_in");
+  if (!shape_ok(batch, h, w, NLM_SHAPE))
+    return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside %d <= h, w <= 65535, h * w <= 2^30", batch, h, w, NLM_MIN_SIDE);
+  if (n_weights < 1 || n_weights > NLM_MAX_WEIGHTS)
+    return fail(e, UNETPP_E_UNSUPPORTED, "n_weights %d: the non-zero prefix of the weight table must have 1..%d entries", n_weights, NLM_MAX_WEIGHTS);
+  if ((uintptr_t)dev_weights_u16 % 2) return fail(e, UNETPP_E_INVALID, "dev_weights_u16 must be 2-byte aligned");
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_src, n * channels_in, dev_out, n * channels_out))
+    return fail(e, UNETPP_E_INVALID, "dev_out aliases dev_src: workgroups read halo pixels their neighbours write");
+  ENTER_DEVICE(e);
+  const int vec = w % 4 == 0 && (uintptr_t)dev_out % 4 == 0;
+  hipLaunchKernelGGL(nlmeans_kernel, tile_grid(w, h, NLM_TILE_W, NLM_TILE_H, batch), dim3(NLM_THREADS), 0, (hipStream_t)stream, dev_src, h, w,
+                     channels_in, channels_out, dev_decisions, dev_weights_u16, n_weights, vec, dev_out);
+  return launched(e);
 }
 
 // ---- binary morphology programs (morphology.h) ------------------------------------------------------------------

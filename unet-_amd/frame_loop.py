@@ -72,8 +72,9 @@ def process_frames(model, frames_bgr_u8, target_size=(512, 512), roi="fixed", de
 
 def process_frames_refactored(model, frames_bgr_u8, roi_xywh, input_size=512, *, enable=True, threshold=10.0, device=None, **cfg):
     """infer_video_refactored.py:346-352 for B raw frames at once, every step on the device and nothing read back:
-    preprocess_frame (src/refactor/preprocess.py:77-91: grey frames enhanced with CLAHE, gamma and the bilateral filter,
-    colour frames copied, decided per frame on the device), crop_roi (:94-113, the slice of roi = (x, y, w, h) clamped to
+    preprocess_frame (src/refactor/preprocess.py:77-91: grey frames enhanced with CLAHE, gamma and the bilateral filter --
+    or, with denoise_method="fastNlMeans", non-local means (nlmeans.preprocess_frames_nlm) -- colour frames copied, decided
+    per frame on the device), crop_roi (:94-113, the slice of roi = (x, y, w, h) clamped to
     the frame), then process_frames on the crop with target_size = (input_size, input_size) and no ROI clip.  `cfg`:
     PreprocessConfig's fields as NestedUNet.preprocess_frames takes them (clip_limit, tile_grid, gamma, denoise_method,
     denoise_strength); `enable` is enable_grayscale_enhance.  Returns (pred uint8 [B,input_size,input_size], mask_cable,
@@ -88,7 +89,11 @@ def process_frames_refactored(model, frames_bgr_u8, roi_xywh, input_size=512, *,
     x1, y1, x2, y2 = en.roi_bounds(int(x.shape[1]), int(x.shape[2]), roi_xywh)
     if x2 <= x1 or y2 <= y1:
         raise ValueError(f"roi {tuple(roi_xywh)} does not meet the {int(x.shape[1])}x{int(x.shape[2])} frame")
-    pre = model.preprocess_frames(x, enable, threshold, **cfg)
+    if cfg.get("denoise_method") == "fastNlMeans":          # NestedUNet.preprocess_frames refuses it by name (its tests pin that)
+        from . import nlmeans
+        pre = nlmeans.preprocess_frames_nlm(model, x, enable, threshold, **{k: v for k, v in cfg.items() if k != "denoise_method"})
+    else:
+        pre = model.preprocess_frames(x, enable, threshold, **cfg)
     crop = pre[:, y1:y2, x1:x2].contiguous()
     return process_frames(model, crop, (int(input_size), int(input_size)), roi=None)
 

@@ -213,8 +213,12 @@ __global__ void convert_input_kernel(const void* __restrict__ in, int fmt, int N
 // ------------------------------------------------------------------------------------------------
 // up = nn.Upsample(scale_factor=2, 'bilinear', align_corners=True) (reference unetpp.py:76,112-116).
 // src = dst*(in-1)/(out-1) in fp32, i0 = int(src), i1 = i0 + (i0 < in-1), l1 = src - i0, l0 = 1 - l1;
-// x is interpolated inside each row first.  The torch.cat([skip, up]) that follows is virtual: the
-// decoder conv reads `skip` and this kernel's output as two sources (conv3x3_mfma.h).
+// x is interpolated inside each row first.  l1 is written as ONE fused multiply-add, fmaf(s, dst, -i0): the rounded exact
+// difference (hence the clamp to [0, 1]), not the difference of the rounded src -- left as `s * dst - i0` the compiler contracted
+// it in some places and not in others (not where the product was shared with another use).  The fused loader of
+// conv3x3_mfma.h does the same; oracle/fast_emulation.py and tests/test_gpu_fast.py pin it.
+// The torch.cat([skip, up]) that follows is virtual: the decoder conv reads `skip` and this kernel's output as two
+// sources (conv3x3_mfma.h).
 typedef __attribute__((ext_vector_type(4))) _Float16 half4v;
 constexpr int UP_SEG = 256;                 // output columns per upsample workgroup
 
@@ -271,7 +275,7 @@ __global__ __launch_bounds__(1024) void upsample2x_kernel(const half_t* __restri
     const float fy = sh * (float)y;
     const int y0 = (int)fy;
     const int y1 = y0 + (y0 < h - 1 ? 1 : 0);
-    const float ly1 = fminf(fmaxf(fy - (float)y0, 0.f), 1.f), ly0 = 1.f - ly1;
+    const float ly1 = fminf(fmaxf(fmaf(sh, (float)y, -(float)y0), 0.f), 1.f), ly0 = 1.f - ly1;
 #pragma unroll
     for (int k = 0; k < 3; ++k) wy[ro][k] = (k == y0 - ybase ? ly0 : 0.f) + (k == y1 - ybase ? ly1 : 0.f);
   }
@@ -283,7 +287,7 @@ __global__ __launch_bounds__(1024) void upsample2x_kernel(const half_t* __restri
     const int xg = (int)fx;                     // global low-res column
     const int x0 = xg - xbase;                  // column inside the staged segment
     const int x1 = x0 + (xg < w - 1 ? 1 : 0);
-    const float lx1 = fminf(fmaxf(fx - (float)xg, 0.f), 1.f), lx0 = 1.f - lx1;
+    const float lx1 = fminf(fmaxf(fmaf(sw, (float)x, -(float)xg), 0.f), 1.f), lx0 = 1.f - lx1;
     half_t* dst = out + ((nb * H + 2 * r) * W + x) * (size_t)REC + piece * 8;      // output row 2r; row 2r+1 is W*REC further
     if (P == 2) {
       const int oct = piece & 1, role = piece >> 1;       // role 0 stores hi and computes channels 0-3 of the octet
@@ -529,9 +533,10 @@ __global__ void unpack_nchw_kernel(const half_t* __restrict__ x, int N, int C, i
     const float lo = (float)p[CB];
     v = plane == 0 ? v + lo : plane == 2 ? lo : v;
   }
-  if (P == 3) {          // EXACT8 record (CB = 16): lo8 at byte 32 + 16 (c / 8) + 8 ((c / 4) & 1) + c % 4, x8 four bytes behind it
-    const int cc = c % 16;
-    const unsigned char* q = (const unsigned char*)(p - cc) + 32 + 16 * (cc >> 3) + 8 * ((cc >> 2) & 1) + (cc & 3);
+  if (P == 3) {          // EXACT8 record: the hi plane's 2 CB bytes, then lo8 at byte 16 (c / 8) + 8 ((c / 4) & 1) + c % 4, x8 four bytes behind it
+    // (CB = 8, the input tensor: a 32-byte record {hi x 8}{lo8 c0-3, x8 c0-3, 0, 0} -- channels 4..7 decode the zero words)
+    const int cc = c % CB;
+    const unsigned char* q = (const unsigned char*)(p - cc) + 2 * CB + 16 * (cc >> 3) + 8 * ((cc >> 2) & 1) + (cc & 3);
     const float l8 = __builtin_amdgcn_cvt_scalef32_f32_bf8((int)q[0], 1.0f, 0), x8 = __builtin_amdgcn_cvt_scalef32_f32_bf8((int)q[4], 1.0f, 0);
     v = plane == 0 ? v + l8 * X8_LO_MUL : plane == 2 ? l8 : plane == 3 ? x8 : v;
   }

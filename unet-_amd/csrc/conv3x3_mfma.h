@@ -475,7 +475,9 @@ void conv3x3_bias_relu_kernel(ConvArgs a) {
         const float fy = up_sh * (float)max(gy, 0), fx = up_sw * (float)max(gx, 0);
         const int yy0 = min((int)fy, Hs - 1), xx0 = min((int)fx, Ws - 1);
         const int yy1 = yy0 + (yy0 < Hs - 1 ? 1 : 0), xx1 = xx0 + (xx0 < Ws - 1 ? 1 : 0);
-        const float ly1 = fminf(fmaxf(fy - (float)yy0, 0.f), 1.f), lx1 = fminf(fmaxf(fx - (float)xx0, 0.f), 1.f);
+        // the weights as one fma each (see upsample2x_kernel): the rounded exact difference s * dst - i0
+        const float ly1 = fminf(fmaxf(fmaf(up_sh, (float)max(gy, 0), -(float)yy0), 0.f), 1.f);
+        const float lx1 = fminf(fmaxf(fmaf(up_sw, (float)max(gx, 0), -(float)xx0), 0.f), 1.f);
         const int ry0 = min(max(yy0 - ybase, 0), C::LSH - 1), ry1 = min(max(yy1 - ybase, 0), C::LSH - 1);
         const int rx0 = min(max(xx0 - xbase, 0), C::LSW - 1), rx1 = min(max(xx1 - xbase, 0), C::LSW - 1);
         up_o00[r] = (ry0 * C::LSW + rx0) * C::LS_REC + kg * 16;

@@ -680,6 +680,42 @@ int unetpp_nlmeans_u8(unetpp_engine* e, const uint8_t* dev_src, int batch, int h
                       const uint8_t* dev_decisions, const uint16_t* dev_weights_u16, int n_weights, uint8_t* dev_out,
                       void* stream);
 
+/* ---- segmentation evaluation on the device: confusion matrix and mask disagreement ---------------------------------------
+ * What the reference's compute_metrics / compute_confusion_matrix (src/utils/metrics.py:9-127) and iou_per_class
+ * (tools/eval.py:25-34) are functions of, and the comparison of two masks of the same frames.  unet_amd/evaluation.py is
+ * the NumPy form and derives the metrics from the table; every result equals it exactly: integer sums, a minimum, and a
+ * maximum of float32 values, none of which depends on the order of arrival.
+ *
+ * unetpp_confusion_u8: dev_pred, dev_target uint8 [B,h,w] (any h, w >= 1 with h * w < 2^32; any byte alignment: frames
+ *   are read with 16-byte loads when the two pointers agree modulo 16, byte by byte otherwise and at each frame's head
+ *   and tail; nothing outside a frame is read).  2 <= num_classes <= 16 is an argument, not the engine's class count.
+ *   ignore_value: 0..255, or -1 for none.
+ *   dev_counts  uint32 [B,C,C]: [b,t,p] = pixels of frame b with target t and pred p, both < C, target not ignored
+ *   dev_outside uint32 [B,2]:   [b,0] = pixels whose target equals ignore_value; [b,1] = the other pixels with
+ *               target >= C or pred >= C.  Neither kind enters dev_counts; the three sum to h * w per frame.
+ *   dev_total   NULL, or uint64 [C*C + 2] (8-byte aligned): the kernel ADDS the counts and then the two outside counters
+ *               of all frames to it and never clears it, so a loop over a whole set needs no synchronisation.
+ *   dev_counts and dev_outside are cleared on `stream` inside the call.  One launch.
+ *
+ * unetpp_mask_disagreement: dev_a, dev_b uint8 [B,h,w] (h * w < 2^31).  Per frame over the pixels with a != b:
+ *   dev_n_diff uint32 [B] their number; dev_first int32 [B] the smallest linear index y * w + x, -1 for none.
+ *   dev_logits: NULL, or float32 [B,num_classes,h,w] (1 <= num_classes <= 256); then, over the differing pixels with
+ *   both values < num_classes: dev_max_margin float32 [B] = max |logits[a] - logits[b]| (0.0 for none) and dev_n_nan
+ *   uint32 [B] = those whose margin is NaN (they stay out of the maximum).  Logits are read at differing pixels only.
+ *   Without logits dev_max_margin and dev_n_nan may be NULL (num_classes is ignored); given, they are cleared.
+ *
+ * unetpp_evaluation_layout: the pixels of a frame one workgroup of either kernel owns (tests place seams with it).
+ *
+ * Errors: UNETPP_E_INVALID for NULL where not allowed, a bad shape, num_classes or ignore_value, a misaligned
+ * dev_total.  No kernel is launched when an error is returned. */
+int unetpp_evaluation_layout(int* span_pixels);
+int unetpp_confusion_u8(unetpp_engine* e, const uint8_t* dev_pred, const uint8_t* dev_target, int batch, int h, int w,
+                        int num_classes, int ignore_value, uint32_t* dev_counts, uint32_t* dev_outside,
+                        uint64_t* dev_total, void* stream);
+int unetpp_mask_disagreement(unetpp_engine* e, const uint8_t* dev_a, const uint8_t* dev_b, int batch, int h, int w,
+                             const float* dev_logits, int num_classes, uint32_t* dev_n_diff, int32_t* dev_first,
+                             float* dev_max_margin, uint32_t* dev_n_nan, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

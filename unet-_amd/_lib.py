@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunetpp_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["unetpp_abi.hip", "unetpp_postproc.hip"]      # the engine; the post-processing entry points
-HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "frame_kernels.h", "components.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "nlmeans.h", "geometry.h", "tiling.h", os.path.join("..", "..", "include", "unetpp.h")]
+HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "frame_kernels.h", "components.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "nlmeans.h", "evaluation.h", "geometry.h", "tiling.h", os.path.join("..", "..", "include", "unetpp.h")]
 
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
 PREC_EXACT, PREC_FAST, PREC_EXACT8 = 0, 1, 2
@@ -135,6 +135,9 @@ ABI = {
     "unetpp_enhance_layout": (ci, [ctypes.POINTER(ci), ctypes.POINTER(ci)]),
     "unetpp_nlmeans_layout": (ci, [ctypes.POINTER(ci), ctypes.POINTER(ci)]),
     "unetpp_nlmeans_u8": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, ci, vp, vp]),
+    "unetpp_evaluation_layout": (ci, [ctypes.POINTER(ci)]),
+    "unetpp_confusion_u8": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
+    "unetpp_mask_disagreement": (ci, [vp, vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
 }
 ABI_SYMBOLS = list(ABI)
 

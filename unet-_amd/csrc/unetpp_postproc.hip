@@ -18,6 +18,7 @@
 #include "edges.h"
 #include "edges_multi.h"
 #include "enhance.h"
+#include "evaluation.h"
 #include "frame_kernels.h"
 #include "geometry.h"
 #include "morphology.h"
@@ -623,6 +624,60 @@ int unetpp_nlmeans_u8(unetpp_engine* e, const uint8_t* dev_src, int batch, int h
   const int vec = w % 4 == 0 && (uintptr_t)dev_out % 4 == 0;
   hipLaunchKernelGGL(nlmeans_kernel, tile_grid(w, h, NLM_TILE_W, NLM_TILE_H, batch), dim3(NLM_THREADS), 0, (hipStream_t)stream, dev_src, h, w,
                      channels_in, channels_out, dev_decisions, dev_weights_u16, n_weights, vec, dev_out);
+  return launched(e);
+}
+
+// ---- segmentation evaluation: joint histogram of two masks, mask disagreement (evaluation.h) --------------------------------
+int unetpp_evaluation_layout(int* span_pixels) {
+  if (!span_pixels) return fail(nullptr, UNETPP_E_INVALID, "null argument");
+  *span_pixels = EV_SPAN;
+  return UNETPP_OK;
+}
+
+// any h, w >= 1 below `pixel_limit` pixels; batch is a grid dimension
+static int eval_shape_check(unetpp_engine* e, int batch, int h, int w, uint64_t pixel_limit) {
+  if (batch < 1 || batch > MAX_DIM || h < 1 || w < 1 || (uint64_t)h * (uint64_t)w >= pixel_limit)
+    return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d: 1 <= batch <= 65535, h, w >= 1, h * w < 2^%d", batch, h, w, pixel_limit >> 32 ? 32 : 31);
+  return UNETPP_OK;
+}
+
+// 16-byte loads need the two masks to sit at the same offset from a 16-byte boundary; frames then share their heads
+static int eval_vec(const void* p, const void* q) { return (((uintptr_t)p ^ (uintptr_t)q) & 15u) == 0; }
+
+static dim3 eval_grid(uint64_t hw, int batch) { return dim3((unsigned)((hw + 15 + EV_SPAN - 1) / EV_SPAN), (unsigned)batch); }
+
+int unetpp_confusion_u8(unetpp_engine* e, const uint8_t* dev_pred, const uint8_t* dev_target, int batch, int h, int w, int num_classes,
+                        int ignore_value, uint32_t* dev_counts, uint32_t* dev_outside, uint64_t* dev_total, void* stream) {
+  REQUIRE_ARGS(e, dev_pred && dev_target && dev_counts && dev_outside);
+  if (int rc = eval_shape_check(e, batch, h, w, 1ull << 32)) return rc;
+  if (num_classes < 2 || num_classes > EV_MAX_CLASSES) return fail(e, UNETPP_E_INVALID, "num_classes %d: 2..%d", num_classes, EV_MAX_CLASSES);
+  if (ignore_value < -1 || ignore_value > 255) return fail(e, UNETPP_E_INVALID, "ignore_value %d: 0..255, or -1 for none", ignore_value);
+  if ((uintptr_t)dev_total % 8) return fail(e, UNETPP_E_INVALID, "dev_total must be 8-byte aligned");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t hw = (uint64_t)h * (uint64_t)w;
+  HIP_TRY(e, hipMemsetAsync(dev_counts, 0, (size_t)batch * num_classes * num_classes * sizeof(uint32_t), s));
+  HIP_TRY(e, hipMemsetAsync(dev_outside, 0, (size_t)batch * 2 * sizeof(uint32_t), s));
+  hipLaunchKernelGGL(confusion_kernel, eval_grid(hw, batch), dim3(EV_THREADS), 0, s, dev_pred, dev_target, (unsigned)hw, num_classes, ignore_value,
+                     eval_vec(dev_pred, dev_target), (unsigned*)dev_counts, (unsigned*)dev_outside, (unsigned long long*)dev_total);
+  return launched(e);
+}
+
+int unetpp_mask_disagreement(unetpp_engine* e, const uint8_t* dev_a, const uint8_t* dev_b, int batch, int h, int w, const float* dev_logits,
+                             int num_classes, uint32_t* dev_n_diff, int32_t* dev_first, float* dev_max_margin, uint32_t* dev_n_nan, void* stream) {
+  REQUIRE_ARGS(e, dev_a && dev_b && dev_n_diff && dev_first && (!dev_logits || (dev_max_margin && dev_n_nan)));
+  if (int rc = eval_shape_check(e, batch, h, w, 1ull << 31)) return rc;
+  if (dev_logits && (num_classes < 1 || num_classes > 256)) return fail(e, UNETPP_E_INVALID, "num_classes %d: 1..256 with logits", num_classes);
+  if ((uintptr_t)dev_logits % 4) return fail(e, UNETPP_E_INVALID, "dev_logits must be 4-byte aligned");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t hw = (uint64_t)h * (uint64_t)w;
+  HIP_TRY(e, hipMemsetAsync(dev_n_diff, 0, (size_t)batch * sizeof(uint32_t), s));
+  HIP_TRY(e, hipMemsetAsync(dev_first, 0xff, (size_t)batch * sizeof(int32_t), s));
+  if (dev_max_margin) HIP_TRY(e, hipMemsetAsync(dev_max_margin, 0, (size_t)batch * sizeof(float), s));
+  if (dev_n_nan) HIP_TRY(e, hipMemsetAsync(dev_n_nan, 0, (size_t)batch * sizeof(uint32_t), s));
+  hipLaunchKernelGGL(mask_disagreement_kernel, eval_grid(hw, batch), dim3(EV_THREADS), 0, s, dev_a, dev_b, (unsigned)hw, dev_logits, num_classes,
+                     eval_vec(dev_a, dev_b), (unsigned*)dev_n_diff, (unsigned*)dev_first, (unsigned*)dev_max_margin, (unsigned*)dev_n_nan);
   return launched(e);
 }
 

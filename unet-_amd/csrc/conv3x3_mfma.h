@@ -186,6 +186,24 @@ __device__ __forceinline__ void touch_kernarg_lines() {
   asm volatile("" :: "s"(touched));
 }
 
+// The argument block of a kernel whose only parameter is `Args`, read IN PLACE (constant address space: s_load).  Fields
+// of the by-value parameter are all fetched at kernel entry and stay live from there to their last use; a kernel whose waves
+// split into roles then keeps the other role's fields and spills its own into vector lanes.  Through this pointer a field is
+// fetched where the code uses it.  The empty asm hides where the pointer comes from: loads behind it are not hoisted above
+// it, so a call at a loop's head (kernargs_again) makes the loop re-read what it needs once per trip out of the scalar
+// cache instead of holding it in registers across the whole trip.
+template <class Args>
+using KernArgs = const __attribute__((address_space(4))) Args*;
+template <class Args>
+__device__ __forceinline__ KernArgs<Args> kernargs_again(KernArgs<Args> p) {
+  asm volatile("" : "+s"(p));
+  return p;
+}
+template <class Args>
+__device__ __forceinline__ KernArgs<Args> kernargs() {
+  return kernargs_again<Args>((KernArgs<Args>)__builtin_amdgcn_kernarg_segment_ptr());
+}
+
 __device__ __forceinline__ void glds16(const void* sbase, unsigned voff, unsigned lds_dst) {
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
@@ -213,6 +231,30 @@ __device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t rsrc, unsigned vof
                  : "=&s"(keep)
                  : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst)
                  : "memory");
+}
+
+// A RUN of DMA pieces issued back to back (the producers of conv3x3_ws.h: up to 19 per chunk): M0 is saved once in front
+// of the run and put back once behind it instead of around every piece -- two scalar moves and a live register less per
+// piece.  Between m0_run_begin and m0_run_end only the *_run forms below and scalar address arithmetic may be issued:
+// nothing there that the compiler itself would route through M0.  The s_nop between the write of M0 and the DMA
+// instruction that reads it stays.
+__device__ __forceinline__ unsigned m0_run_begin() {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0" : "=s"(keep) :: "memory");
+  return keep;
+}
+__device__ __forceinline__ void m0_run_end(unsigned keep) {
+  asm volatile("s_mov_b32 m0, %0" :: "s"(keep) : "memory");
+}
+__device__ __forceinline__ void glds16_run(const void* sbase, unsigned voff, unsigned lds_dst) {
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
+}
+template <bool NT = false>
+__device__ __forceinline__ void blds16_run(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int soff, unsigned lds_dst) {
+  if (NT)
+    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen nt lds" :: "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
+  else
+    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" :: "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
 }
 
 // Epilogue helper shared by the conv and transposed-conv kernels.  `v` = the 16 channel values of one pixel

@@ -99,18 +99,26 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// A wave-uniform value the compiler knows nothing about (stays in scalar registers): what is computed from it is computed
+// where it is used, not ahead of the loop the value belongs to.
+template <class T>
+__device__ __forceinline__ T opaque(T v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+
 // Epilogue of ROWS image rows (acc[m] = row gy0 + m) x 32 pixels x 32 channels [cbase, cbase + 32) held in MFMA
 // accumulators (pixel on the lane; the weights are packed with rows8, so register r holds channel
 // 16 * (r >> 3) + 8 * (lane >> 5) + (r & 7): eight consecutive channels of each of the tile's two records): scale, bias, ReLU,
 // then either the fp16 hi/lo store (+ the fused 2x2 max-pool of rows (0,1), (2,3), ...) or the fused 1x1 head with
 // softmax / argmax / class rules.  Same arithmetic, statement for statement, as the epilogue of conv3x3_bias_relu_kernel.
 template <int P, int ROWS, bool POOL, bool HEAD, bool X8 = false>
-__device__ __forceinline__ void ws_epilogue(const ConvArgs& a, const float16v (&acc)[ROWS], const float2* sb_lds,
+__device__ __forceinline__ void ws_epilogue(KernArgs<ConvArgs> a, const float16v (&acc)[ROWS], const float2* sb_lds,
                                             const float* head_lds, int n, int gy0, int x0, int cbase, int lane) {
-  const int H = a.H, W = a.W;
+  const int H = a->H, W = a->W;
   const int h = lane >> 5;
   const int gx = x0 + (lane & 31);
-  const int nbo = a.Cout >> 4;
+  const int nbo = a->Cout >> 4;
   float v[ROWS][16];
   float vmax = 0.f;
 #pragma unroll
@@ -124,7 +132,7 @@ __device__ __forceinline__ void ws_epilogue(const ConvArgs& a, const float16v (&
     }
   }
   if (!HEAD && __builtin_amdgcn_ballot_w64(vmax > F16_MAX)) {      // rare: report, then clamp to what fp16 can hold
-    range_flag(a.status, vmax > F16_MAX, false);
+    range_flag(a->status, vmax > F16_MAX, false);
 #pragma unroll
     for (int r = 0; r < 16; ++r)
 #pragma unroll
@@ -136,9 +144,9 @@ __device__ __forceinline__ void ws_epilogue(const ConvArgs& a, const float16v (&
       const int gy = gy0 + m;
       const bool ok = gy < H && gx < W;
       const size_t blk = (size_t)H * W * P * 16;
-      half_t* dst = a.out + ((size_t)n * nbo + (cbase >> 4)) * blk + ((size_t)gy * W + gx) * P * 16;
+      half_t* dst = a->out + ((size_t)n * nbo + (cbase >> 4)) * blk + ((size_t)gy * W + gx) * P * 16;
 #ifdef UNETPP_WS_DBG
-      pack_store_rows8<P, X8>(v[m], dst, blk, ok, h, (a.dbg & 262144) != 0, (a.dbg & 524288) != 0);
+      pack_store_rows8<P, X8>(v[m], dst, blk, ok, h, (a->dbg & 262144) != 0, (a->dbg & 524288) != 0);
 #else
       pack_store_rows8<P, X8>(v[m], dst, blk, ok, h);
 #endif
@@ -156,14 +164,14 @@ __device__ __forceinline__ void ws_epilogue(const ConvArgs& a, const float16v (&
 #pragma unroll
       for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) {
         lg[c] = -INFINITY;
-        if (c < a.head_C) {       // uniform branch
+        if (c < a->head_C) {       // uniform branch
           float wq[16];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const float4 w4 = *(const float4*)(head_lds + c * 32 + 16 * (q >> 1) + 8 * h + 4 * (q & 1));
             wq[4 * q] = w4.x; wq[4 * q + 1] = w4.y; wq[4 * q + 2] = w4.z; wq[4 * q + 3] = w4.w;
           }
-          const float bc = head_lds[a.head_C * 32 + c];
+          const float bc = head_lds[a->head_C * 32 + c];
           float p0 = 0.f, p1 = 0.f;
 #pragma unroll
           for (int r = 0; r < 16; ++r) { p0 = fmaf(v[2 * m2][r], wq[r], p0); p1 = fmaf(v[2 * m2 + 1][r], wq[r], p1); }
@@ -184,30 +192,30 @@ __device__ __forceinline__ void ws_epilogue(const ConvArgs& a, const float16v (&
       for (int c = 1; c < HEAD_FUSED_MAX_CLASSES; ++c)
         if (lg[c] > best) { best = lg[c]; besti = c; }        // first maximal class wins
       bool is_cable = besti == 1, is_tape = besti == 2;
-      if (a.probs || a.rule) {      // uniform: softmax_np = exp(x - max) / sum, fp32
+      if (a->probs || a->rule) {      // uniform: softmax_np = exp(x - max) / sum, fp32
         float pe[HEAD_FUSED_MAX_CLASSES], sum = 0.f;
 #pragma unroll
         for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) {
-          pe[c] = (c < a.head_C) ? expf(lg[c] - best) : 0.f;
+          pe[c] = (c < a->head_C) ? expf(lg[c] - best) : 0.f;
           sum += pe[c];
         }
 #pragma unroll
         for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) {
           pe[c] = pe[c] / sum;
-          if (ok && a.probs && c < a.head_C) a.probs[((size_t)n * a.head_C + c) * hw + pix] = pe[c];
+          if (ok && a->probs && c < a->head_C) a->probs[((size_t)n * a->head_C + c) * hw + pix] = pe[c];
         }
-        if (a.rule) apply_rule(a.rule, pe[0], pe[1], pe[2], a.t_cable, a.t_tape, a.bg_margin, a.ct_margin, is_cable, is_tape);
+        if (a->rule) apply_rule(a->rule, pe[0], pe[1], pe[2], a->t_cable, a->t_tape, a->bg_margin, a->ct_margin, is_cable, is_tape);
       }
       if (ok) {
-        if (a.logits) {
+        if (a->logits) {
 #pragma unroll
           for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c)
-            if (c < a.head_C) a.logits[((size_t)n * a.head_C + c) * hw + pix] = lg[c];
+            if (c < a->head_C) a->logits[((size_t)n * a->head_C + c) * hw + pix] = lg[c];
         }
         const size_t o = (size_t)n * hw + pix;
-        if (a.mask) a.mask[o] = (uint8_t)besti;
-        if (a.cable) a.cable[o] = is_cable;
-        if (a.tape) a.tape[o] = is_tape;
+        if (a->mask) a->mask[o] = (uint8_t)besti;
+        if (a->cable) a->cable[o] = is_cable;
+        if (a->tape) a->tape[o] = is_tape;
       }
     }
   }
@@ -226,9 +234,9 @@ __device__ __forceinline__ void ws_epilogue(const ConvArgs& a, const float16v (&
       const int py = (gy0 >> 1) + m2, px = (x0 >> 1) + ((lane & 31) >> 1);
       const bool ok = ((lane & 1) == 0) && py < Hp && px < Wp;
       const size_t blk = (size_t)Hp * Wp * P * 16;
-      half_t* dst = a.pool_out + ((size_t)n * nbo + (cbase >> 4)) * blk + ((size_t)py * Wp + px) * P * 16;
+      half_t* dst = a->pool_out + ((size_t)n * nbo + (cbase >> 4)) * blk + ((size_t)py * Wp + px) * P * 16;
 #ifdef UNETPP_WS_DBG
-      pack_store_rows8<P, X8>(pv, dst, blk, ok, h, (a.dbg & 262144) != 0);
+      pack_store_rows8<P, X8>(pv, dst, blk, ok, h, (a->dbg & 262144) != 0);
 #else
       pack_store_rows8<P, X8>(pv, dst, blk, ok, h);
 #endif
@@ -248,9 +256,15 @@ __device__ __forceinline__ void ws_epilogue(const ConvArgs& a, const float16v (&
 // stay in LDS for the whole launch.
 // CAT2: the K loop runs over TWO full-resolution tensors (SimpleUNet's cat([up, enc]), simple_unet.py:112,117,122), in0's chunks
 // first; both hold whole 16-channel records (the host checks), so a lane's offsets are those of the first source.
-template <int P, bool POOL, bool HEAD, bool UPF, bool C0F = false, int NW = 1, int MWP = 4, bool X8 = false, bool CAT2 = false>
-__global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
+// SPLITK: the split-K launches (a->ksplit > 1) have a kernel of their own (conv3x3_ws_splitk_kernel); everywhere else KS is
+// the constant 1 and the partial buffer, the counters and the share arithmetic are not compiled.
+// The arguments are read in place (KernArgs, conv3x3_mfma.h): each role fetches the fields it uses, and what a role needs
+// once per tile it reads again at the tile boundary instead of holding it across the chunk loop.
+template <int P, bool POOL, bool HEAD, bool UPF, bool C0F, int NW, int MWP, bool X8, bool CAT2, bool SPLITK>
+__device__ __forceinline__ void conv3x3_ws_body() {
   using C = WsCfg<P, UPF, C0F, NW, MWP, X8>;
+  static_assert(!SPLITK || (!UPF && !C0F && !HEAD), "split-K: plain and pooling layers only (launch_ws_k)");
+  KernArgs<ConvArgs> a = kernargs<ConvArgs>();
   static_assert(!C0F || (!UPF && !HEAD && P == 2 && NW == 1), "fused first block: exact mode, no other fusion in the loader");
   static_assert(!HEAD || NW == 1, "the fused head needs all 32 channels of x0_4 in one 32-block");
   constexpr int NT = C::NT, MW = C::MW, TH = C::TH, TW = C::TW, HALO_W = C::HALO_W;
@@ -266,13 +280,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int H = a.H, W = a.W;
-  const int tiles_img = a.tiles_x * a.tiles_y;
-  // a.nct = Cout / BN channel tiles per pixel tile; a.ksplit (>= 1) = workgroups that share a tile, each with its own
+  const int H = a->H, W = a->W;
+  const int tiles_img = a->tiles_x * a->tiles_y;
+  // a->nct = Cout / BN channel tiles per pixel tile; a->ksplit (>= 1) = workgroups that share a tile, each with its own
   // range of K-chunks (small batches: see the split-K notes at the consumers' epilogue)
-  const int KS = a.ksplit;
-  const int total_tiles = a.N * tiles_img * a.nct * KS;
-  const int nch0 = (a.C0 + KC - 1) / KC;
+  const int KS = SPLITK ? a->ksplit : 1;
+  const int total_tiles = a->N * tiles_img * a->nct * KS;
+  const int nch0 = (a->C0 + KC - 1) / KC;
   const unsigned lds_base = (unsigned)(unsigned long)(lds_char_t*)smem;
 
   // per-channel (scale, bias) of the layer and the head weights, staged once per workgroup (read by the consumers)
@@ -280,12 +294,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
   // to their first DMA instead of waiting for these loads; the first chunk's barrier publishes the table -- a launch of one
   // tile per CU, i.e. a small batch, is a chain of such latencies)
   float2* sb_lds = (float2*)(smem + C::LDS_BYTES);
-  float* head_lds = (float*)(smem + C::LDS_BYTES + a.Cout * 8);
+  float* head_lds = (float*)(smem + C::LDS_BYTES + a->Cout * 8);
   if (wave < C::NCONS) {
-    for (int i = tid; i < a.Cout; i += C::NCONS * 64) sb_lds[i] = make_float2(a.scale[i], a.bias[i]);
+    for (int i = tid; i < a->Cout; i += C::NCONS * 64) sb_lds[i] = make_float2(a->scale[i], a->bias[i]);
     if (HEAD) {
-      for (int i = tid; i < a.head_C * 32; i += C::NCONS * 64) head_lds[i] = a.head_w[i];
-      for (int i = tid; i < a.head_C; i += C::NCONS * 64) head_lds[a.head_C * 32 + i] = a.head_b[i];
+      for (int i = tid; i < a->head_C * 32; i += C::NCONS * 64) head_lds[i] = a->head_w[i];
+      for (int i = tid; i < a->head_C; i += C::NCONS * 64) head_lds[a->head_C * 32 + i] = a->head_b[i];
     }
   }
 
@@ -295,58 +309,81 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
   // tile order as in conv3x3_bias_relu_kernel: an XCD (workgroups b, b+8, ...) walks a contiguous run of tiles
   const int G = (int)gridDim.x;
   const int slot = (G % 8 == 0) ? ((int)blockIdx.x % 8) * (G / 8) + (int)blockIdx.x / 8 : (int)blockIdx.x;
-  // Tile number -> (channel tile, column, row, image).  A workgroup asks for its slot, then for tiles G apart (or the
-  // same tile again): only the first call divides, later ones add G's own decomposition with carries (wave-uniform
-  // scalar work; the six divisions per tile used to cost several hundred cycles in each role).
-  int dec_ks = 0, dec_ct = 0, dec_tx = 0, dec_ty = 0, dec_n = 0, dec_t = -1;      // the tile decoded last (per-wave cursor)
-  // (G's own decomposition comes from the host: five scalar divisions are ~150 dependent instructions, and at one tile
-  // per workgroup -- a small batch -- the whole launch waits for the producers' path to their first DMA)
-  const int g_ks = a.gdec[0], g_ct = a.gdec[1], g_tx = a.gdec[2], g_ty = a.gdec[3], g_n = a.gdec[4];
+  // Tile number -> (split share, channel tile, column, row, image), kept as a per-wave cursor dec_*.  A workgroup divides once,
+  // for its slot (decode_first); every later tile is G further on and adds G's own digits with carries (decode_next:
+  // wave-uniform scalar work; the six divisions per tile used to cost several hundred cycles in each role).  G's digits come
+  // from the host (gdec): five scalar divisions are ~150 dependent instructions, and at one tile per workgroup -- a small
+  // batch -- the whole launch waits for the producers' path to their first DMA.
+  int dec_ks = 0, dec_ct = 0, dec_tx = 0, dec_ty = 0, dec_n = 0, dec_t = -1;
+  // HEAD: radix, step and bound are fetched again at every tile instead of being held (see tiles_end)
+  constexpr bool REREAD = HEAD;
+  // The tile loops' bound and step.  HEAD: the epilogue between two tiles needs every scalar register it can get, so both are
+  // worked out again from the argument block (s_loads that hit, a few multiplications per tile) instead of surviving it in
+  // vector lanes; the step is the grid size, which the host wrote down digit by digit (gdec; no split-K with a head).
+  auto tiles_end = [&]() {
+    if (!REREAD) return total_tiles;
+    KernArgs<ConvArgs> p = kernargs_again(a);
+    return p->N * p->tiles_x * p->tiles_y * p->nct;
+  };
+  auto tile_step = [&]() {
+    if (!REREAD) return G;
+    KernArgs<ConvArgs> p = kernargs_again(a);
+    return ((p->gdec[4] * p->tiles_y + p->gdec[3]) * p->tiles_x + p->gdec[2]) * p->nct + p->gdec[1];
+  };
   // u = q d + r for wave-uniform 0 <= u < 2^22, d >= 1: one reciprocal and a branch-free correction step instead of the
   // generic 32-bit division (below 2^22 the float quotient is off by at most one)
-  const bool small_radix = total_tiles < (1 << 22);
+  // (the radix test is made where a division happens -- a workgroup's first tile -- not kept as a lane mask for the whole launch)
   auto divmod = [&](const int u, const int d, int& q, int& r) {      // (q may alias the caller's u)
     int qq, rr;
-    if (small_radix) {
+    if (opaque(tiles_end()) < (1 << 22)) {
       qq = (int)((float)u * __builtin_amdgcn_rcpf((float)d));
       rr = u - qq * d;
       const int up = rr >= d ? 1 : 0, dn = rr < 0 ? 1 : 0;
       qq += up - dn; rr += (dn - up) * d;
     } else {
-      qq = u / d; rr = u - qq * d;
+      const int dd = opaque(d);      // (2^22 tiles and more: the division's reciprocal set-up stays here, out of the tile loop's live set)
+      qq = u / dd; rr = u - qq * dd;
     }
     q = qq; r = rr;
   };
+  auto decode_first = [&](int t) {
+    int u = t;
+    if (SPLITK) divmod(u, KS, u, dec_ks);
+    divmod(u, a->nct, u, dec_ct);
+    divmod(u, a->tiles_x, u, dec_tx);
+    divmod(u, a->tiles_y, dec_n, dec_ty);
+  };
+  auto decode_next = [&]() {
+    KernArgs<ConvArgs> p = REREAD ? kernargs_again(a) : a;
+    const int g_ks = SPLITK ? p->gdec[0] : 0, g_ct = p->gdec[1], g_tx = p->gdec[2], g_ty = p->gdec[3], g_n = p->gdec[4];
+    dec_ks += g_ks;
+    int carry = dec_ks >= KS ? 1 : 0;
+    dec_ks -= carry ? KS : 0;
+    dec_ct += g_ct + carry;
+    carry = dec_ct >= p->nct ? 1 : 0;
+    dec_ct -= carry ? p->nct : 0;
+    dec_tx += g_tx + carry;
+    carry = dec_tx >= p->tiles_x ? 1 : 0;
+    dec_tx -= carry ? p->tiles_x : 0;
+    dec_ty += g_ty + carry;
+    carry = dec_ty >= p->tiles_y ? 1 : 0;
+    dec_ty -= carry ? p->tiles_y : 0;
+    dec_n += g_n + carry;
+  };
+  // the fused first block's producers ask one tile ahead and for the same tile twice: dec_t = the tile the cursor stands on
   auto decode = [&](int t, int& n, int& y0, int& x0) {
     if (t != dec_t) {
-      if (dec_t >= 0 && t == dec_t + G) {
-        dec_ks += g_ks;
-        int carry = dec_ks >= KS ? 1 : 0;
-        dec_ks -= carry ? KS : 0;
-        dec_ct += g_ct + carry;
-        carry = dec_ct >= a.nct ? 1 : 0;
-        dec_ct -= carry ? a.nct : 0;
-        dec_tx += g_tx + carry;
-        carry = dec_tx >= a.tiles_x ? 1 : 0;
-        dec_tx -= carry ? a.tiles_x : 0;
-        dec_ty += g_ty + carry;
-        carry = dec_ty >= a.tiles_y ? 1 : 0;
-        dec_ty -= carry ? a.tiles_y : 0;
-        dec_n += g_n + carry;
-      } else {
-        int u = t;
-        divmod(u, KS, u, dec_ks);
-        divmod(u, a.nct, u, dec_ct);
-        divmod(u, a.tiles_x, u, dec_tx);
-        divmod(u, a.tiles_y, dec_n, dec_ty);
-      }
+      if (dec_t >= 0 && t == dec_t + tile_step()) decode_next();
+      else decode_first(t);
       dec_t = t;
     }
     n = dec_n; x0 = dec_tx * TW; y0 = dec_ty * TH;
   };
   if (slot >= total_tiles) return;                       // whole workgroup: no barrier has been executed yet
   // (a one-chunk tile has no second barrier to publish the handed-over pair; a split tile has no epilogue to share)
-  const bool handoff = C::HANDOFF && a.nchunks >= 2 && KS == 1;
+  // (asked again per tile and behind the loops, from the argument block: as one value it is a lane mask held in two scalar
+  // registers by both roles from here to the last barrier)
+  auto handoff_on = [&]() { KernArgs<ConvArgs> p = kernargs_again(a); return C::HANDOFF && p->nchunks >= 2 && (!SPLITK || p->ksplit == 1); };
 
   // ---- C0F: patch loader (producer lanes) and the once-per-launch part of the producers' work
   typedef __attribute__((ext_vector_type(4))) float float4v;
@@ -362,7 +399,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
     for (int i = 0; i < PATCH_LOADS; ++i) {
       const int e = plane_id + i * (C::NPROD * 64);
       int row, col, cs, idx;
-      if (a.raw_fmt == 0) {
+      if (a->raw_fmt == 0) {
         const int ch = e / (C::PATCH_H * C::PATCH_W), rem = e - ch * (C::PATCH_H * C::PATCH_W);
         row = rem / C::PATCH_W; col = rem - row * C::PATCH_W; cs = ch; idx = rem * 3 + ch;
       } else {
@@ -378,14 +415,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
   auto patch_fetch = [&](int n, int y0, int x0, float (&val)[PATCH_LOADS]) {
     const size_t img = (size_t)H * W * 3;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)a.raw_in + (size_t)n * img * (a.raw_fmt == 0 ? 4 : 1)), 0, (int)(img * (a.raw_fmt == 0 ? 4 : 1)), 0x00020000);
+        (void*)((const char*)a->raw_in + (size_t)n * img * (a->raw_fmt == 0 ? 4 : 1)), 0, (int)(img * (a->raw_fmt == 0 ? 4 : 1)), 0x00020000);
     bool beyond = false;
 #pragma unroll
     for (int i = 0; i < PATCH_LOADS; ++i) {
       const int gy = y0 - 2 + (pe_rc[i] >> 16), gx = x0 - 2 + ((pe_rc[i] >> 2) & 0x3fff), cs = pe_rc[i] & 3;
       const bool ok = pe_idx[i] >= 0 && gy >= 0 && gy < H && gx >= 0 && gx < W;
       float v;
-      if (a.raw_fmt == 0) {
+      if (a->raw_fmt == 0) {
         v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, ok ? ((cs * H + gy) * W + gx) * 4 : (int)0x80000000, 0, 0));
       } else {
         const unsigned char b8 = __builtin_amdgcn_raw_buffer_load_b8(rs, ok ? (gy * W + gx) * 3 + cs : (int)0x80000000, 0, 0);
@@ -399,7 +436,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
       bool nan = false;
 #pragma unroll
       for (int i = 0; i < PATCH_LOADS; ++i) { nan |= val[i] != val[i]; val[i] = __builtin_amdgcn_fmed3f(val[i], -F16_MAX, F16_MAX); }
-      range_flag(a.status, beyond, nan);
+      range_flag(a->status, beyond, nan);
     }
   };
   // LDS image [row][col][RGB], one word per sample: fp16 hi in the low half, fp16 lo (= sample - hi) in the high half --
@@ -422,7 +459,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
       const int piece = (wave - C::NCONS) + it * C::NPROD;
       if (piece < 2 * C::SLAB_PIECES) {
         const int c = piece / C::SLAB_PIECES, pc = piece - c * C::SLAB_PIECES;
-        glds16((const char*)a.wpk + (size_t)c * C::SLAB_BYTES + pc * 1024, lane * 16,
+        glds16((const char*)a->wpk + (size_t)c * C::SLAB_BYTES + pc * 1024, lane * 16,
                lds_base + c * C::BUF_BYTES + C::HALO_BYTES + pc * 1024);
       }
     }
@@ -443,9 +480,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
 #define WS_STAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); st_sum[i] += now_ - st_t; st_t = now_; \
                       if (ev_ptr && ev_ptr < ev_end) *ev_ptr++ = ((unsigned long long)(i) << 56) | __builtin_amdgcn_s_memrealtime(); }
 // event log of one wave per role (dbg bit 131072, single-layer stamps only): (phase << 56 | 100 MHz wall clock) after every phase, 60 events
-#define WS_EVLOG(role) unsigned long long* ev_ptr = (a.stamps && (a.dbg & 131072) && lane == 0 && blockIdx.x < 1024) ? a.stamps + (size_t)1024 * 32 + ((size_t)blockIdx.x * 2 + (role)) * 64 : nullptr; \
+#define WS_EVLOG(role) unsigned long long* ev_ptr = (a->stamps && (a->dbg & 131072) && lane == 0 && blockIdx.x < 1024) ? a->stamps + (size_t)1024 * 32 + ((size_t)blockIdx.x * 2 + (role)) * 64 : nullptr; \
                        unsigned long long* const ev_end = ev_ptr + 60; if (ev_ptr) *ev_ptr++ = (63ull << 56) | rt_entry;
-#define WS_STAMP_IN(i) if (a.dbg & 32768) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); WS_STAMP(i) __builtin_amdgcn_sched_barrier(0); }
+#define WS_STAMP_IN(i) if (a->dbg & 32768) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); WS_STAMP(i) __builtin_amdgcn_sched_barrier(0); }
 #define WS_EVT(i) { if (ev_ptr && ev_ptr < ev_end) *ev_ptr++ = ((unsigned long long)(i) << 56) | __builtin_amdgcn_s_memrealtime(); }
 #else
 #define WS_STAMP(i) {}
@@ -475,15 +512,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
     half8 wa_h[2], wa_l[2];
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      wa_h[c] = *(const half8*)(a.c1w + ((size_t)(c * 2 + 0) * 64 + lane) * 8);
-      wa_l[c] = *(const half8*)(a.c1w + ((size_t)(c * 2 + 1) * 64 + lane) * 8);
+      wa_h[c] = *(const half8*)(a->c1w + ((size_t)(c * 2 + 0) * 64 + lane) * 8);
+      wa_l[c] = *(const half8*)(a->c1w + ((size_t)(c * 2 + 1) * 64 + lane) * 8);
     }
     // scale / bias of conv1's channels 16 c + 4 kq + r
     float sc1[2][4], bi1[2][4];
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { sc1[c][r] = a.c1_scale[16 * c + 4 * kq + r]; bi1[c][r] = a.c1_bias[16 * c + 4 * kq + r]; }
+      for (int r = 0; r < 4; ++r) { sc1[c][r] = a->c1_scale[16 * c + 4 * kq + r]; bi1[c][r] = a->c1_bias[16 * c + 4 * kq + r]; }
     // operand slot i of a pixel at patch position (hy, hx): byte offset relative to patch[(hy)][hx][0]
     //   kq < 3: row hy + kq, floats 0..7 of the 9 (dx, ch) values;  kq == 3: float 8 of rows hy, hy+1, hy+2, then zeros
     int koff[8];
@@ -591,7 +628,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
         };
         if (y0 >= 1 && y0 + TH < H && x0 >= 1 && x0 + TW < W) groups(std::true_type());
         else groups(std::false_type());
-        if (__builtin_amdgcn_ballot_w64(vmax > F16_MAX)) range_flag(a.status, vmax > F16_MAX, false);
+        if (__builtin_amdgcn_ballot_w64(vmax > F16_MAX)) range_flag(a->status, vmax > F16_MAX, false);
         WS_STAMP(1)
         if (have_next) patch_store(tbuf ^ 1, pv);
         WS_STAMP(2)
@@ -600,10 +637,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
       }
     }
 #ifdef UNETPP_WS_DBG
-    if (a.stamps && pw == 0 && lane == 0)
+    if (a->stamps && pw == 0 && lane == 0)
 #pragma unroll
-      for (int i = 0; i < 11; ++i) a.stamps[((size_t)blockIdx.x * 2 + 1) * 16 + i] = st_sum[i];
-    if (a.stamps && pw == 0 && lane == 0) a.stamps[((size_t)blockIdx.x * 2 + 1) * 16 + 12] = __builtin_amdgcn_s_memrealtime();
+      for (int i = 0; i < 11; ++i) a->stamps[((size_t)blockIdx.x * 2 + 1) * 16 + i] = st_sum[i];
+    if (a->stamps && pw == 0 && lane == 0) a->stamps[((size_t)blockIdx.x * 2 + 1) * 16 + 12] = __builtin_amdgcn_s_memrealtime();
 #endif
     return;
   }
@@ -613,14 +650,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
     const int pw = wave - C::NCONS;
 #ifdef UNETPP_WS_DBG
     const unsigned long long rt_prod = __builtin_amdgcn_s_memrealtime();
-    { const int pr = (a.dbg >> 10) & 3; if (pr == 1) __builtin_amdgcn_s_setprio(1); else if (pr == 2) __builtin_amdgcn_s_setprio(2); else if (pr == 3) __builtin_amdgcn_s_setprio(3); }
+    { const int pr = (a->dbg >> 10) & 3; if (pr == 1) __builtin_amdgcn_s_setprio(1); else if (pr == 2) __builtin_amdgcn_s_setprio(2); else if (pr == 3) __builtin_amdgcn_s_setprio(3); }
 #endif
     constexpr unsigned OOB = 0x80000000u;                // beyond num_records: the buffer load returns zeros
     constexpr int ITERS = C::HALO_ITERS;
     // tile-invariant: halo pixel / unit of this lane in each of its DMA pieces (as in conv3x3_bias_relu_kernel)
     int my_u = lane / PPP;
 #ifdef UNETPP_WS_DBG
-    if (a.dbg & 16384) my_u = lane % C::U;               // timing experiment: a pixel's units on neighbouring lanes (results garbage)
+    if (a->dbg & 16384) my_u = lane % C::U;               // timing experiment: a pixel's units on neighbouring lanes (results garbage)
 #endif
     const int my_pl = my_u / KG, my_k8 = (my_u % KG) * 8;
     int hyx[ITERS];
@@ -628,17 +665,17 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
     for (int it = 0; it < ITERS; ++it) {
       int hp = (pw + it * C::NPROD) * PPP + lane % PPP;
 #ifdef UNETPP_WS_DBG
-      if (a.dbg & 16384) hp = (pw + it * C::NPROD) * PPP + lane / C::U;
+      if (a->dbg & 16384) hp = (pw + it * C::NPROD) * PPP + lane / C::U;
 #endif
       const int hy = hp / HALO_W, hx = hp - hy * HALO_W;
       hyx[it] = (hp < C::NHALO) ? ((hy << 8) | hx) : -1;
     }
-    const int cb0 = a.C0 < 16 ? a.C0 : 16;
+    const int cb0 = a->C0 < 16 ? a->C0 : 16;
     const unsigned plane_bytes0 = (unsigned)H * (unsigned)W * (unsigned)(P * cb0 * 2);      // < 2^31: unetpp_create's shape limit
-    const unsigned img_bytes0 = (unsigned)H * (unsigned)W * (unsigned)(P * a.C0 * 2);
+    const unsigned img_bytes0 = (unsigned)H * (unsigned)W * (unsigned)(P * a->C0 * 2);
     const int Hs = H >> 1, Ws = W >> 1;
     const unsigned plane_bytes1 = (unsigned)Hs * (unsigned)Ws * (unsigned)(P * 16 * 2);
-    const unsigned img_bytes1 = (unsigned)Hs * (unsigned)Ws * (unsigned)(P * a.C1 * 2);
+    const unsigned img_bytes1 = (unsigned)Hs * (unsigned)Ws * (unsigned)(P * a->C1 * 2);
     const float up_sh = Hs > 1 ? (float)(Hs - 1) / (float)(H - 1) : 0.f;
     const float up_sw = Ws > 1 ? (float)(Ws - 1) / (float)(W - 1) : 0.f;
 
@@ -648,7 +685,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
       const int hy = hyx[it] >> 8, hx = hyx[it] & 255;
-      const bool valid = hyx[it] >= 0 && my_k8 < a.C0;
+      const bool valid = hyx[it] >= 0 && my_k8 < a->C0;
       lane_off0[it] = valid ? (my_k8 >> 4) * (int)plane_bytes0 + ((((hy - 1) * W + (hx - 1)) * P + my_pl) * cb0 + (my_k8 & 15)) * 2 : (int)OOB;
     }
     unsigned voff0[ITERS];
@@ -666,7 +703,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
     // also replace the ds_read2_b64 the compiler forms from a fixed +32 offset (8 cycles, banked modulo 32).
     int rd_swap = (P == 2 && !X8 && (lane & 16)) ? 32 : 0;      // (X8: hi and the 8-bit planes are not interchangeable)
 #ifdef UNETPP_WS_DBG
-    if (a.dbg & 32) rd_swap = 0;
+    if (a->dbg & 32) rd_swap = 0;
 #endif
     if (UPF) {
 #pragma unroll
@@ -696,16 +733,24 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
         for (int it = 0; it < ITERS; ++it) {
           const int hy = hyx[it] >> 8, hx = hyx[it] & 255;
           const int gy = y0 + hy - 1, gx = x0 + hx - 1;
-          const bool ok = hyx[it] >= 0 && gy >= 0 && gy < H && gx >= 0 && gx < W;
+          // (one sign test for "this lane has a pixel", gy >= 0 and gx >= 0: tested on its own, the tile-invariant first
+          // of the three becomes a lane mask per piece that lives in scalar registers across the whole tile loop)
+          const bool ok = (hyx[it] | gy | gx) >= 0 && gy < H && gx < W;
           const unsigned pix = (unsigned)((gy * W + gx) * P + my_pl);
-          voff0[it] = (ok && my_k8 < a.C0) ? (unsigned)(my_k8 >> 4) * plane_bytes0 + (pix * cb0 + (my_k8 & 15)) * 2u : OOB;
+          voff0[it] = (ok && my_k8 < a->C0) ? (unsigned)(my_k8 >> 4) * plane_bytes0 + (pix * cb0 + (my_k8 & 15)) * 2u : OOB;
         }
       }
-      rsrc0 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in0 + (size_t)n * H * W * P * a.C0), 0, (int)img_bytes0, 0x00020000);
-      if (CAT2)
-        rsrc1 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in1 + (size_t)n * H * W * P * a.C1), 0, (int)((unsigned)H * (unsigned)W * (unsigned)(P * a.C1 * 2)), 0x00020000);
+      // (an image's halves = half its bytes: one 32-bit value serves the descriptor's size and, times n, its base -- the
+      // 64-bit product H W P C is not another pair of registers held across the tile loop; < 2^31 bytes: unetpp_create)
+      KernArgs<ConvArgs> at = REREAD ? kernargs_again(a) : a;
+      const unsigned img0 = REREAD ? (unsigned)H * (unsigned)W * (unsigned)(P * at->C0 * 2) : img_bytes0;
+      rsrc0 = __builtin_amdgcn_make_buffer_rsrc((void*)(at->in0 + (size_t)n * (img0 >> 1)), 0, (int)img0, 0x00020000);
+      if (CAT2) {
+        const unsigned img_bytes_cat = (unsigned)H * (unsigned)W * (unsigned)(P * a->C1 * 2);
+        rsrc1 = __builtin_amdgcn_make_buffer_rsrc((void*)(a->in1 + (size_t)n * (img_bytes_cat >> 1)), 0, (int)img_bytes_cat, 0x00020000);
+      }
       if (UPF) {
-        rsrc1 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.in1 + (size_t)n * Hs * Ws * P * a.C1), 0, (int)img_bytes1, 0x00020000);
+        rsrc1 = __builtin_amdgcn_make_buffer_rsrc((void*)(a->in1 + (size_t)n * (img_bytes1 >> 1)), 0, (int)img_bytes1, 0x00020000);
         const int ybase = (int)(up_sh * (float)max(y0 - 1, 0)), xbase = (int)(up_sw * (float)max(x0 - 1, 0));
         constexpr int PXP = 1024 / C::LS_REC, PARTS = C::LS_REC / 16;
 #pragma unroll
@@ -774,7 +819,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
 #ifdef UNETPP_WS_DBG
-          if (a.dbg & 512) { hq[r][k] = (u32x2){0x3c003c00u, 0x3c003c00u}; lq[r][k] = (u32x2){0u, 0u}; continue; }
+          if (a->dbg & 512) { hq[r][k] = (u32x2){0x3c003c00u, 0x3c003c00u}; lq[r][k] = (u32x2){0u, 0u}; continue; }
 #endif
           hq[r][k] = *(const u32x2*)(ls + off[k]);
           if (P == 2) lq[r][k] = *(const u32x2*)(ls + (off[k] ^ 32));
@@ -820,7 +865,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
         }
         WS_STAMP_IN(9)
 #ifdef UNETPP_WS_DBG
-        if (a.dbg & 64) { if (v[0][0] == 12345.f && v[3][3] == 7.f && v[1][2] == 3.f && v[2][1] == 9.f) a.status[1] = 1; continue; }
+        if (a->dbg & 64) { if (v[0][0] == 12345.f && v[3][3] == 7.f && v[1][2] == 3.f && v[2][1] == 9.f) a->status[1] = 1; continue; }
 #endif
         if (up_st[r][0] >= 0) {
 #pragma unroll
@@ -850,8 +895,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
 
     // HANDOFF: the epilogue of the accumulator pair consumer wave `pw` left in LDS for the previous tile
     const int stg_base = 2 * C::BUF_BYTES + 2 * C::LS_BYTES + 2 * C::PATCH_BYTES;
-    int hn = 0, hy0 = 0, hx0 = 0, hct = 0;
-    bool have_handoff = false;
+    int hn = -1, hty = 0, htx = 0, hct = 0;            // the cursor's digits of that tile (not y0, x0 as well); hn < 0: none yet
     auto handoff_epilogue = [&]() {
       const char* st = smem + stg_base + pw * C::STG_WAVE + lane * 16;
       float16v pair[2];
@@ -864,99 +908,113 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
           pair[i][4 * q] = v4[0]; pair[i][4 * q + 1] = v4[1]; pair[i][4 * q + 2] = v4[2]; pair[i][4 * q + 3] = v4[3];
         }
       // the pair is rows (2, 3) of the wave's four rows (MW = 4) or the second 32-channel block of its two rows (MW = 2)
-      const int gy0 = hy0 + pw * MW + (MW == 4 ? 2 : 0);
+      const int gy0 = hty * TH + pw * MW + (MW == 4 ? 2 : 0);
       const int cbase = hct * BN + (MW == 4 ? 0 : 32);
-      ws_epilogue<P, 2, POOL, HEAD, X8>(a, pair, sb_lds, head_lds, hn, gy0, hx0, cbase, lane);
+      ws_epilogue<P, 2, POOL, HEAD, X8>(kernargs_again(a), pair, sb_lds, head_lds, hn, gy0, htx * TW, cbase, lane);
     };
     int g = 0;                                           // global chunk counter: chunk g -> stage buffer g & 1
-    const bool slabs_stay = a.nchunks == 2 && a.nct == 1 && KS == 1;
-    const int chunks_per_share = KS == 1 ? a.nchunks : a.nchunks / KS;
 #ifdef UNETPP_WS_DBG
     st_t = __builtin_readcyclecounter();
 #endif
     WS_EVT(51)
-    for (int tile = slot; tile < total_tiles; tile += G) {
-      int n, y0, x0;
-      decode(tile, n, y0, x0);
+    decode_first(slot);
+    for (int tile = slot; tile < tiles_end(); tile += tile_step(), decode_next()) {
+      const int n = dec_n, y0 = dec_ty * TH, x0 = dec_tx * TW;
       WS_EVT(52)
-      const char* wsrc = (const char*)a.wpk + (size_t)dec_ct * a.nchunks * C::SLAB_BYTES;
-      const int tile_ct = dec_ct;
-      const int c_begin = dec_ks * chunks_per_share, c_end = c_begin + chunks_per_share;       // this workgroup's share of K
+      // the chunk behind which the previous tile's handed-over pair is finished, or -1 (one number, not two lane masks)
+      const int handoff_c = opaque((handoff_on() && hn >= 0) ? 1 : -1);
+      KernArgs<ConvArgs> at = REREAD ? kernargs_again(a) : a;
+      const int nchunks = at->nchunks;
+      const bool slabs_stay = nchunks == 2 && at->nct == 1 && KS == 1;
+      const int chunks_per_share = KS == 1 ? nchunks : nchunks / KS;
+      const char* wsrc = (const char*)at->wpk + (size_t)dec_ct * nchunks * C::SLAB_BYTES;
+      const int c_begin = dec_ks * chunks_per_share, c_end = c_begin + opaque(chunks_per_share);       // this workgroup's share of K (opaque: no "loop runs at all" mask kept)
       setup_tile(n, y0, x0);
       WS_STAMP(7)
       for (int c = c_begin; c < c_end; ++c, ++g) {
         const int buf = (g & 1) * C::BUF_BYTES;
+        // One destination and one source per chunk, each piece a compile-time constant further on.  opaque(): the compiler
+        // otherwise precomputes every piece's address outside the tile loop (nine 64-bit slab offsets, six LDS
+        // addresses per stage) and spills them into vector lanes, to be read back in front of each DMA instruction.
+        const unsigned dst0 = opaque(lds_base + buf + pw * 1024);
+        const unsigned m0_keep = m0_run_begin();         // one save / restore of M0 for all DMA pieces of the chunk
 #ifdef UNETPP_WS_DBG
-        if (!(a.dbg & 2))
+        if (!(a->dbg & 2))
 #endif
         if (c < nch0) {
+          const int soff = c * (int)plane_bytes0;
 #pragma unroll
           for (int it = 0; it < ITERS; ++it) {
             const int piece = pw + it * C::NPROD;
-            if (C::HALO_PIECES % C::NPROD == 0 || piece < C::HALO_PIECES)
-              blds16<true>(rsrc0, voff0[it], c * (int)plane_bytes0, lds_base + buf + piece * 1024);
+            if (it + 1 < ITERS || C::HALO_PIECES % C::NPROD == 0 || piece < C::HALO_PIECES)      // (only a wave's last piece can be missing)
+              blds16_run<true>(rsrc0, voff0[it], soff, dst0 + it * (C::NPROD * 1024));
           }
         } else if (CAT2) {                               // chunk of the second full-resolution source
+          const int soff = (c - nch0) * (int)plane_bytes0;
 #pragma unroll
           for (int it = 0; it < ITERS; ++it) {
             const int piece = pw + it * C::NPROD;
-            if (C::HALO_PIECES % C::NPROD == 0 || piece < C::HALO_PIECES)
-              blds16<true>(rsrc1, voff0[it], (c - nch0) * (int)plane_bytes0, lds_base + buf + piece * 1024);
+            if (it + 1 < ITERS || C::HALO_PIECES % C::NPROD == 0 || piece < C::HALO_PIECES)      // (only a wave's last piece can be missing)
+              blds16_run<true>(rsrc1, voff0[it], soff, dst0 + it * (C::NPROD * 1024));
           }
         }
         // A layer of two chunks and one channel tile keeps its weights: chunk c of every tile lands in stage c, so the
         // slabs this workgroup loaded for its first tile are still there (a third of the bytes and DMA pieces saved).
 #ifdef UNETPP_WS_DBG
-        if (!(a.dbg & 8))
+        if (!(a->dbg & 8))
 #endif
-        if (!(slabs_stay && g >= 2))
+        if (!(slabs_stay && g >= 2)) {
+          const char* wchunk = opaque(wsrc + (size_t)c * C::SLAB_BYTES + pw * 1024);
 #pragma unroll
-        for (int it = 0; it < C::SLAB_ITERS; ++it) {
-          const int piece = pw + it * C::NPROD;
-          if (C::SLAB_PIECES % C::NPROD == 0 || piece < C::SLAB_PIECES)
-            glds16(wsrc + (size_t)c * C::SLAB_BYTES + piece * 1024, lane * 16, lds_base + buf + C::HALO_BYTES + piece * 1024);
+          for (int it = 0; it < C::SLAB_ITERS; ++it) {
+            const int piece = pw + it * C::NPROD;
+            if (it + 1 < C::SLAB_ITERS || C::SLAB_PIECES % C::NPROD == 0 || piece < C::SLAB_PIECES)
+              glds16_run(wchunk + it * (C::NPROD * 1024), lane * 16, dst0 + C::HALO_BYTES + it * (C::NPROD * 1024));
+          }
         }
-        if (!UPF) { WS_STAMP(0) }
+        if (!UPF) { m0_run_end(m0_keep); WS_STAMP(0) }
         if (UPF) {
 #ifdef UNETPP_WS_DBG
-          if (!(a.dbg & 2))
+          if (!(a->dbg & 2))
 #endif
-          if (c + 1 < a.nchunks && c + 1 >= nch0) {      // low-res records of the NEXT chunk, one iteration ahead
+          if (c + 1 < nchunks && c + 1 >= nch0) {      // low-res records of the NEXT chunk, one iteration ahead
+            const int soffL = (c + 1 - nch0) * (int)plane_bytes1;
+            const unsigned dstL = opaque(lds_base + 2 * C::BUF_BYTES + ((c + 1) & 1) * C::LS_BYTES + pw * 1024);
 #pragma unroll
             for (int it = 0; it < LSR; ++it) {
               const int piece = pw + it * C::NPROD;
-              if (C::LS_PIECES % C::NPROD == 0 || piece < C::LS_PIECES)
-                blds16(rsrc1, voffL[it], (c + 1 - nch0) * (int)plane_bytes1,
-                       lds_base + 2 * C::BUF_BYTES + ((c + 1) & 1) * C::LS_BYTES + piece * 1024);
+              if (it + 1 < LSR || C::LS_PIECES % C::NPROD == 0 || piece < C::LS_PIECES)
+                blds16_run(rsrc1, voffL[it], soffL, dstL + it * (C::NPROD * 1024));
             }
           }
+          m0_run_end(m0_keep);
           if (c >= nch0) { WS_STAMP(3) } else { WS_STAMP(0) }
 #ifdef UNETPP_WS_DBG
-          if (!(a.dbg & 1))
+          if (!(a->dbg & 1))
 #endif
           if (c >= nch0) up_rounds(c, buf);              // this chunk's halo image from the records that landed last iteration
           if (c >= nch0) { WS_STAMP(4) } else { WS_STAMP(0) }
         }
 #ifdef UNETPP_WS_DBG
-        if (!(a.dbg & 128))
+        if (!(a->dbg & 128))
 #endif
-        if (handoff && c == 1 && have_handoff) handoff_epilogue();     // previous tile's pair: published by the barrier behind chunk 0
+        if (c == handoff_c) handoff_epilogue();     // previous tile's pair: published by the barrier behind chunk 0
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA pieces have landed
         if (UPF && c >= nch0) { WS_STAMP(5) } else { WS_STAMP(1) }
         lds_barrier();                                    // chunk g published; the consumers have left buffer (g+1) & 1
         if (UPF && c >= nch0) { WS_STAMP(6) } else { WS_STAMP(2) }
       }
-      hn = n; hy0 = y0; hx0 = x0; hct = tile_ct; have_handoff = true;
+      hn = dec_n; hty = dec_ty; htx = dec_tx; hct = dec_ct;
     }
-    if (handoff) {
+    if (handoff_on()) {
       lds_barrier();                                      // the consumers' last pair is in LDS
-      if (have_handoff) handoff_epilogue();
+      if (hn >= 0) handoff_epilogue();
     }
 #ifdef UNETPP_WS_DBG
-    if (a.stamps && pw == 0 && lane == 0)
+    if (a->stamps && pw == 0 && lane == 0)
 #pragma unroll
-      for (int i = 0; i < 11; ++i) a.stamps[((size_t)blockIdx.x * 2 + 1) * 16 + i] = st_sum[i];
-    if (a.stamps && pw == 0 && lane == 0) a.stamps[((size_t)blockIdx.x * 2 + 1) * 16 + 12] = __builtin_amdgcn_s_memrealtime();
+      for (int i = 0; i < 11; ++i) a->stamps[((size_t)blockIdx.x * 2 + 1) * 16 + i] = st_sum[i];
+    if (a->stamps && pw == 0 && lane == 0) a->stamps[((size_t)blockIdx.x * 2 + 1) * 16 + 12] = __builtin_amdgcn_s_memrealtime();
 #endif
     return;
   }
@@ -964,7 +1022,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
   // ================================================================= consumers
   const int cw = wave;
 #ifdef UNETPP_WS_DBG
-  { const int pr = (a.dbg >> 12) & 3; if (pr == 1) __builtin_amdgcn_s_setprio(1); else if (pr == 2) __builtin_amdgcn_s_setprio(2); else if (pr == 3) __builtin_amdgcn_s_setprio(3); }
+  { const int pr = (a->dbg >> 12) & 3; if (pr == 1) __builtin_amdgcn_s_setprio(1); else if (pr == 2) __builtin_amdgcn_s_setprio(2); else if (pr == 3) __builtin_amdgcn_s_setprio(3); }
 #endif
   // lane-constant LDS read offsets: pixel fragment of halo row r (0 .. MW+1 of this wave) shifted by dx
   int a_off[MW + 2][3];
@@ -1043,20 +1101,21 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
   if (cw != 0) ev_ptr = nullptr;
   if (ev_ptr) *ev_ptr++ = (62ull << 56) | rt_begin;
 #endif
-  for (int tile = slot; tile < total_tiles; tile += G) {
-    int n, y0, x0;
-    decode(tile, n, y0, x0);
+  decode_first(slot);
+  for (int tile = slot; tile < tiles_end(); tile += tile_step(), decode_next()) {
+    const int n = dec_n, y0 = dec_ty * TH, x0 = dec_tx * TW;
     const int ct = dec_ct, ks = dec_ks;
-    const int c_begin = ks * (a.nchunks / KS), c_end = c_begin + a.nchunks / KS;
+    const bool handoff = handoff_on();
+    const int c_begin = ks * (a->nchunks / KS), c_end = c_begin + a->nchunks / KS;
 #pragma unroll
     for (int m = 0; m < MW; ++m)
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
-        if (a.zinit && ks == 0) {    // accumulators start from the low-resolution half of the layer (tapmm_ws.h); uniform branch
+        if (a->zinit && ks == 0) {    // accumulators start from the low-resolution half of the layer (tapmm_ws.h); uniform branch
           typedef __attribute__((ext_vector_type(4))) float f32x4;
           const int gy = y0 + cw * MW + m, gx = x0 + (lane & 31);
           const bool in = gy < H && gx < W;
-          const float* zp = a.zinit + (((size_t)n * (a.Cout >> 5) + ((ct * BN + j * 32) >> 5)) * ((size_t)H * W) + (size_t)gy * W + gx) * 32 + 8 * (lane >> 5);
+          const float* zp = a->zinit + (((size_t)n * (a->Cout >> 5) + ((ct * BN + j * 32) >> 5)) * ((size_t)H * W) + (size_t)gy * W + gx) * 32 + 8 * (lane >> 5);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
@@ -1066,7 +1125,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
           }
         }
       }
-    const bool from_zero = a.zinit == nullptr || ks != 0;
+    const bool from_zero = a->zinit == nullptr || ks != 0;
     int4v x9[MW];                                           // EXACT8: the ninth tap's 8-bit operand of the previous chunk, see there
     if (X8) {
 #pragma unroll
@@ -1081,7 +1140,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
       // dx-major walk: the six halo rows of one column shift serve its three taps.  Fragments of the next tap
       // (and, spread over the three taps, the next column shift) are read before this tap's MFMAs.
 #ifdef UNETPP_WS_DBG
-      if (a.dbg & 16) continue;
+      if (a->dbg & 16) continue;
 #endif
       if constexpr (X8) {
         // ---- EXACT8 chunk: 9 main-term steps (fp16 hi planes, one 32-cycle MFMA per product) and 5 cross-term steps (one
@@ -1118,7 +1177,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
         };
         auto main_step = [&](const BM& b, const half8 (&hf)[R], int dy, bool first) {
 #ifdef UNETPP_WS_DBG
-          if (a.dbg & 4) return;
+          if (a->dbg & 4) return;
 #endif
           const float16v zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1129,7 +1188,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
         };
         auto cross_step = [&](const BX& b, const int8v (&x)[R], int r0) {
 #ifdef UNETPP_WS_DBG
-          if (a.dbg & (4 | 65536)) return;      // 65536: the cross terms only (how much of a chunk they are)
+          if (a->dbg & (4 | 65536)) return;      // 65536: the cross terms only (how much of a chunk they are)
 #endif
 #pragma unroll
           for (int m = 0; m < MW; ++m)
@@ -1193,7 +1252,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
           __builtin_amdgcn_sched_barrier(0);
         }
         // The ninth tap (2, 2) takes bytes 16-31 of a scaled MFMA whose bytes 0-15 belong to the ninth tap of the PREVIOUS
-        // chunk (x9, kept in registers).  a.pair9 (every layer whose workgroups take an even number of chunks): even chunks
+        // chunk (x9, kept in registers).  a->pair9 (every layer whose workgroups take an even number of chunks): even chunks
         // skip the instruction, odd chunks run it for both -- 9 cross MFMAs per two chunks instead of 10; their pair-4 weights
         // hold both taps (weight_pack_x8_kernel).  Without pair9 every chunk runs it against zero weights in bytes 0-15.
         load_bx(bx0, 4);
@@ -1203,7 +1262,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         cross_step(bx1, xa, 0);      // pair 3: taps (0, 2) + (1, 2)
         __builtin_amdgcn_sched_barrier(0);
-        if (!(a.pair9 && ((c - c_begin) & 1) == 0)) {
+        if (!(a->pair9 && ((c - c_begin) & 1) == 0)) {
           int8v xq[R];
 #pragma unroll
           for (int m = 0; m < MW; ++m) xq[m] = __builtin_shufflevector(x9[m], cur[m], 0, 1, 2, 3, 4, 5, 6, 7);
@@ -1235,7 +1294,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
           if (dx < 2) load_a_part(fan, halo, dx + 1, 2 * dy, 2 * dy + 2);
           __builtin_amdgcn_sched_barrier(0);
 #ifdef UNETPP_WS_DBG
-          if (!(a.dbg & 4))
+          if (!(a->dbg & 4))
 #endif
           {
             if (step == 0 && c == c_begin && from_zero) run_mfma_first(fa, fb);
@@ -1248,9 +1307,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
     }
     // ---- epilogue from registers, two row pairs; the producers are already filling the next tile's first chunk
 #ifdef UNETPP_WS_DBG
-    if (a.dbg & 256) { if (acc[0][0][0] == 12345.f && acc[MW - 1][NW - 1][5] == 7.f) a.status[1] = 1; continue; }
+    if (a->dbg & 256) { if (acc[0][0][0] == 12345.f && acc[MW - 1][NW - 1][5] == 7.f) a->status[1] = 1; continue; }
 #endif
-    // ---- split-K (a.ksplit > 1; small batches, where a layer has fewer tiles than the chip has CUs): this wave's raw
+    // ---- split-K (a->ksplit > 1; small batches, where a layer has fewer tiles than the chip has CUs): this wave's raw
     // accumulators go to its slot of the partial buffer; a counter per (tile, wave) tells the wave whose partial arrives
     // LAST, and that wave adds all KS partials in the fixed order 0 .. KS-1 (its own included, read back like the others:
     // the same bits whoever is last) and runs the epilogue.  No wave ever waits for another workgroup.
@@ -1263,7 +1322,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
       const int tile_id = tile / KS;                                     // (n, ty, tx, ct): the same for the KS workgroups of a tile
       const int ntile = total_tiles / KS;
       constexpr int WAVE_BYTES = MW * NW * 16 * 64 * 4;
-      const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc((void*)a.kpart, 0, KS * ntile * C::NCONS * WAVE_BYTES, 0x00020000);
+      const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc((void*)a->kpart, 0, KS * ntile * C::NCONS * WAVE_BYTES, 0x00020000);
       const int mine = ((ks * ntile + tile_id) * C::NCONS + cw) * WAVE_BYTES + lane * 16;
 #pragma unroll
       for (int m = 0; m < MW; ++m)
@@ -1277,11 +1336,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
                                                    prs, mine + ((m * NW + j) * 4 + q) * 1024, 0, 16 /* sc1 */);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       unsigned old = 0;
-      if (lane == 0) old = __hip_atomic_fetch_add(a.kcnt + tile_id * C::NCONS + cw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (lane == 0) old = __hip_atomic_fetch_add(a->kcnt + tile_id * C::NCONS + cw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       old = __builtin_amdgcn_readfirstlane(old);
       if (old != (unsigned)(KS - 1)) { WS_STAMP(2) continue; }         // another workgroup's wave finishes this part of the tile
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");           // (compiler only: the loads stay behind the add)
-      if (lane == 0) __hip_atomic_store(a.kcnt + tile_id * C::NCONS + cw, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+      if (lane == 0) __hip_atomic_store(a->kcnt + tile_id * C::NCONS + cw, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
       // Units of half a partial (8 of its 16 KB-pieces, 32 registers), two units in flight; every accumulator element still
       // receives its partials in the order 0, 1, 2, ...
       constexpr int HALF = MW * NW * 2;
@@ -1329,23 +1388,32 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs a) {
             }
         } else {
           const float16v pair[2] = {acc[2 * m2][j], acc[2 * m2 + 1][j]};
-          ws_epilogue<P, 2, POOL, HEAD, X8>(a, pair, sb_lds, head_lds, n, y0 + cw * MW + 2 * m2, x0, ct * BN + j * 32, lane);
+          ws_epilogue<P, 2, POOL, HEAD, X8>(kernargs_again(a), pair, sb_lds, head_lds, n, y0 + cw * MW + 2 * m2, x0, ct * BN + j * 32, lane);
         }
       }
     WS_STAMP(2)
   }
-  if (handoff) lds_barrier();        // the last handed-over pair is in LDS
+  if (handoff_on()) lds_barrier();        // the last handed-over pair is in LDS
 #ifdef UNETPP_WS_DBG
-  if (a.stamps && cw == 0 && lane == 0)
+  if (a->stamps && cw == 0 && lane == 0)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) a.stamps[((size_t)blockIdx.x * 2) * 16 + i] = st_sum[i];
-  if (a.stamps && cw == 0 && lane == 0) {
-    a.stamps[((size_t)blockIdx.x * 2) * 16 + 4] = rt_begin;
-    a.stamps[((size_t)blockIdx.x * 2) * 16 + 6] = rt_entry;
-    a.stamps[((size_t)blockIdx.x * 2) * 16 + 5] = __builtin_amdgcn_s_memrealtime();
+    for (int i = 0; i < 4; ++i) a->stamps[((size_t)blockIdx.x * 2) * 16 + i] = st_sum[i];
+  if (a->stamps && cw == 0 && lane == 0) {
+    a->stamps[((size_t)blockIdx.x * 2) * 16 + 4] = rt_begin;
+    a->stamps[((size_t)blockIdx.x * 2) * 16 + 6] = rt_entry;
+    a->stamps[((size_t)blockIdx.x * 2) * 16 + 5] = __builtin_amdgcn_s_memrealtime();
   }
 #endif
 }
 #undef WS_STAMP
+
+template <int P, bool POOL, bool HEAD, bool UPF, bool C0F = false, int NW = 1, int MWP = 4, bool X8 = false, bool CAT2 = false>
+__global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs) {
+  conv3x3_ws_body<P, POOL, HEAD, UPF, C0F, NW, MWP, X8, CAT2, false>();
+}
+template <int P, bool POOL, int NW = 1, int MWP = 4, bool X8 = false, bool CAT2 = false>
+__global__ __launch_bounds__(512, 2) void conv3x3_ws_splitk_kernel(ConvArgs) {
+  conv3x3_ws_body<P, POOL, false, false, false, NW, MWP, X8, CAT2, true>();
+}
 
 }  // namespace unetpp

@@ -260,7 +260,12 @@ hipError_t launch_ws_k(const LaunchCtx& cx, ConvArgs a, hipStream_t s) {
     a.gdec[3] = t % a.tiles_y;
     a.gdec[4] = t / a.tiles_y;
   }
-  auto k = conv3x3_ws_kernel<P, POOL, HEAD, UPF, C0F, NW, MW, X8, CAT2>;
+  // split launches have a kernel of their own: everywhere else the share arithmetic, the partials and the counters are not
+  // compiled (conv3x3_ws.h).  The plan above decides, nothing else: ks > 1 exactly when it did before.
+  void (*k)(ConvArgs) = conv3x3_ws_kernel<P, POOL, HEAD, UPF, C0F, NW, MW, X8, CAT2>;
+  if constexpr (!UPF && !C0F && !HEAD) {
+    if (ks > 1) k = conv3x3_ws_splitk_kernel<P, POOL, NW, MW, X8, CAT2>;
+  }
   hipError_t st = allow_full_lds((const void*)k, cx.device);
   if (st != hipSuccess) return st;
   hipLaunchKernelGGL(k, grid, dim3(C::NT), lds, s, a);

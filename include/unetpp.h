@@ -543,6 +543,53 @@ int unetpp_width_profile(unetpp_engine* e, const float* dev_widths, int batch, i
 int unetpp_components_summary(unetpp_engine* e, const int32_t* dev_num, const int32_t* dev_stats, int batch, int capacity,
                               int64_t min_area, int64_t* dev_out, void* stream);
 
+/* ---- the robust loop's mask rules on the device: distance transform + ring, best cable, ROI limit, row median ----------
+ * What infer_video_robust.py does with its two masks after exclusive_threshold (:102-216, :325-387).  unet_amd/robust.py
+ * is the NumPy form.  Every launching entry is asynchronous on `stream` and allocates nothing.  Every bad argument except
+ * a NULL engine is answered with UNETPP_E_UNSUPPORTED.
+ *
+ * unetpp_distance_transform_u8: cv2.distanceTransform(img, DIST_L2 | DIST_L1 | DIST_C, 3) (OpenCV's published
+ * distanceTransform_3x3), bit for bit.  A pixel of img is non-zero where dev_src is foreground (== match_class, or != 0
+ * for match_class < 0), or with invert != 0 where it is NOT -- so `(mask_cable == 0)` needs no launch of its own.
+ * Arithmetic: t = the smallest chamfer path length to a zero pixel in 16.16 fixed point with the weights (HV, DIAG) =
+ * (62587, 89738) for UNETPP_DIST_L2, (65536, 131072) for _L1, (65536, 65536) for _C; t = min(t, INT_MAX >> 2);
+ * distance = (float)t * (1.f / 65536).  A frame without a zero pixel is 8192.0 everywhere.  Any 1 <= h, w <= 65535 with
+ * h * w <= 2^30, any alignment of the masks.
+ *   dev_dist   float32 [B,h,w]  the distance map; may be NULL
+ *   dev_ring   uint8   [B,h,w]  out_value where lo <= distance <= hi (float32 comparisons) and the pixel of img is
+ *                               non-zero and dev_mask1 is foreground (match1 as above; dev_mask1 NULL: no such
+ *                               condition), 0 elsewhere; may be NULL, but not together with dev_dist.  With dev_dist
+ *                               NULL the search is cut off just beyond hi, so its cost follows the band's width.
+ *   dev_workspace  unetpp_distance_workspace_bytes(batch, h, w) bytes (0 for a shape outside the limits), 16-byte aligned
+ *
+ * unetpp_components_best_cable: keep_best_cable_cc (:102-160) on the labels, num and stats of unetpp_components.  In
+ * label order a component is rejected when area < min_area, then h < min_h, then w > max_w, then
+ * aspect = h / (w + 1e-6) < min_aspect; score = (h / H) * 3.0 + min(aspect, 12.0) * 0.5 + (area / (H * W)) * 0.5 in
+ * float64 without contraction; the first component with the strictly greatest score is written as out_value into dev_out
+ * uint8 [B,h,w], everything else 0 (all 0 when none qualifies or num > capacity).  min_h / max_w are the reference's
+ * int(min_h_ratio * H) / int(max_w_ratio * W), formed by the caller.  dev_workspace: the one of unetpp_components.
+ *
+ * unetpp_roi_limit_u8: apply_roi_limit (:201-216).  The bounding box of the non-zero pixels of dev_cable per frame, padded
+ * by pad >= 0 and clipped to the frame; dev_out = dev_mask inside it and 0 outside, all 0 when the cable is empty.
+ * dev_out may be dev_mask itself.  dev_workspace: unetpp_roi_limit_workspace_bytes(batch) bytes, 4-byte aligned.
+ *
+ * unetpp_row_width_median: calc_width of _measure_diameters (:372-387) from dev_widths float32 [B,2,h] of
+ * unetpp_row_widths: dev_median float64 [B,2] = np.median of the widths above 1 (a row has more than one foreground pixel
+ * exactly when last - first + 1 > 1): the middle value, the mean of the two middle ones for an even count, 0 for none. */
+enum { UNETPP_DIST_L1 = 1, UNETPP_DIST_L2 = 2, UNETPP_DIST_C = 3 };   /* cv2.DIST_L1, DIST_L2, DIST_C */
+
+size_t unetpp_distance_workspace_bytes(int batch, int h, int w);
+int unetpp_distance_transform_u8(unetpp_engine* e, const uint8_t* dev_src, int match_class, int invert, int batch, int h, int w,
+                                 int metric, float* dev_dist, const uint8_t* dev_mask1, int match1, float lo, float hi,
+                                 uint8_t out_value, uint8_t* dev_ring, void* dev_workspace, void* stream);
+int unetpp_components_best_cable(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num, const int32_t* dev_stats,
+                                 int batch, int h, int w, int capacity, double min_area, int min_h, int max_w, double min_aspect,
+                                 uint8_t out_value, uint8_t* dev_out, void* dev_workspace, void* stream);
+size_t unetpp_roi_limit_workspace_bytes(int batch);
+int unetpp_roi_limit_u8(unetpp_engine* e, const uint8_t* dev_mask, const uint8_t* dev_cable, int batch, int h, int w, int pad,
+                        uint8_t* dev_out, void* dev_workspace, void* stream);
+int unetpp_row_width_median(unetpp_engine* e, const float* dev_widths, int batch, int h, double* dev_median, void* stream);
+
 /* ---- sliding-window inference on the device: gather tiles, gate, blend -------------------------------------------------
  * SlidingWindowInference.predict (tools/inference_binary_patch.py:19-115) and OptimizedSlidingWindowInference.predict
  * (tools/inference_binary_optimized.py:21-113) around the network: cut frames into overlapping patch_size squares,

@@ -1,6 +1,6 @@
 // unetpp_postproc.hip — the post-processing entry points of the C ABI (include/unetpp.h): mask statistics, connected
-// components and their filters, the grey-level burr detectors, measurements, grey-frame enhancement and denoising, morphology, the two
-// resizes and the tiling of sliding-window inference.  Each entry checks its arguments and queues kernels on the caller's
+// components and their filters, the grey-level burr detectors, measurements, the distance transform and the robust loop's mask rules,
+// grey-frame enhancement and denoising, morphology, the two resizes and the tiling of sliding-window inference.  Each entry checks its arguments and queues kernels on the caller's
 // stream.  Of an engine this file sees unetpp_engine_common (abi_common.h) and nothing else: no tensor, layer, arena or stream.
 #include <hip/hip_runtime.h>
 
@@ -15,6 +15,7 @@
 
 #include "abi_common.h"
 #include "components.h"
+#include "distance.h"
 #include "edges.h"
 #include "edges_multi.h"
 #include "enhance.h"
@@ -421,6 +422,122 @@ int unetpp_components_summary(unetpp_engine* e, const int32_t* dev_num, const in
   ENTER_DEVICE(e);
   hipLaunchKernelGGL(components_summary_kernel, dim3((unsigned)batch), dim3(GEO_THREADS), 0, (hipStream_t)stream, (const int*)dev_num,
                      (const int*)dev_stats, capacity, (long long)min_area, (long long*)dev_out);
+  return launched(e);
+}
+
+// ---- the robust loop's mask rules: distance transform + ring, best cable, ROI limit, row median (distance.h) ---------------
+// These entries answer every bad argument but a NULL engine with UNETPP_E_UNSUPPORTED.
+#define REQUIRE_ROBUST(e, all_given)         \
+  if (!(e)) return UNETPP_E_INVALID;         \
+  if (!(all_given)) return fail(e, UNETPP_E_UNSUPPORTED, "null argument")
+
+struct DtWorkspace { size_t bits = 0, g = 0, flag = 0, total = 0; int nbands = 0; };
+static bool dt_layout(int batch, int h, int w, DtWorkspace* ws) {
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return false;
+  ws->nbands = (h + DT_BAND - 1) / DT_BAND;
+  Carve c;
+  ws->bits = c.take((size_t)batch * ws->nbands * w * sizeof(unsigned));
+  ws->g = c.take((size_t)batch * h * w * sizeof(uint16_t));
+  ws->flag = c.take((size_t)batch * sizeof(int));
+  ws->total = c.end;
+  return true;
+}
+
+size_t unetpp_distance_workspace_bytes(int batch, int h, int w) {
+  DtWorkspace ws;
+  return dt_layout(batch, h, w, &ws) ? ws.total : 0;
+}
+
+int unetpp_distance_transform_u8(unetpp_engine* e, const uint8_t* dev_src, int match_class, int invert, int batch, int h, int w, int metric,
+                                 float* dev_dist, const uint8_t* dev_mask1, int match1, float lo, float hi, uint8_t out_value,
+                                 uint8_t* dev_ring, void* dev_workspace, void* stream) {
+  REQUIRE_ROBUST(e, dev_src && dev_workspace && (dev_dist || dev_ring));
+  DtWorkspace ws;
+  if (!dt_layout(batch, h, w, &ws)) return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  unsigned hv, diag;                                         // cvRound(0.955f * 65536), cvRound(1.3693f * 65536); 1, 2; 1, 1
+  switch (metric) {
+    case UNETPP_DIST_L2: hv = 62587; diag = 89738; break;
+    case UNETPP_DIST_L1: hv = 65536; diag = 131072; break;
+    case UNETPP_DIST_C: hv = 65536; diag = 65536; break;
+    default: return fail(e, UNETPP_E_UNSUPPORTED, "unknown metric %d", metric);
+  }
+  if (match_class > 255 || match1 > 255) return fail(e, UNETPP_E_UNSUPPORTED, "match class %d / %d out of range", match_class, match1);
+  if (dev_ring && out_value == 0) return fail(e, UNETPP_E_UNSUPPORTED, "out_value must not be 0");
+  if ((uintptr_t)dev_workspace % 16) return fail(e, UNETPP_E_UNSUPPORTED, "dev_workspace must be 16-byte aligned");
+  if ((uintptr_t)dev_dist % 4) return fail(e, UNETPP_E_UNSUPPORTED, "dev_dist must be 4-byte aligned");
+  // The ring alone needs no distance above hi: the search starts from a bound two pixels beyond it (the conversion to
+  // float32 moves a value by less than 2^-23 of itself).
+  unsigned start = DT_CAP;
+  if (!dev_dist && hi < 8000.0f) start = (unsigned)((double)(hi > 0.0f ? hi : 0.0f) * 65536.0) + 2u * 65536u;
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  char* wsp = (char*)dev_workspace;
+  unsigned* bits = (unsigned*)(wsp + ws.bits);
+  uint16_t* g = (uint16_t*)(wsp + ws.g);
+  int* flag = (int*)(wsp + ws.flag);
+  const size_t lds = (size_t)w * sizeof(uint16_t);
+  if (lds > 32 * 1024) HIP_TRY(e, allow_full_lds((const void*)dt_row_kernel, unetpp_common(e)->cfg.device, 128 * 1024));
+  HIP_TRY(e, hipMemsetAsync(flag, 0, (size_t)batch * sizeof(int), s));
+  const dim3 cols((unsigned)((w + DT_THREADS - 1) / DT_THREADS), (unsigned)ws.nbands, (unsigned)batch);
+  hipLaunchKernelGGL(dt_bits_kernel, cols, dim3(DT_THREADS), 0, s, dev_src, h, w, match_class, invert != 0, bits, flag);
+  hipLaunchKernelGGL(dt_column_kernel, cols, dim3(DT_THREADS), 0, s, (const unsigned*)bits, h, w, g);
+  const DtRing ring{dev_mask1, match1, lo, hi, (unsigned)out_value};
+  hipLaunchKernelGGL(dt_row_kernel, dim3((unsigned)h, (unsigned)batch), dim3(DT_THREADS), lds, s, (const uint16_t*)g, (const int*)flag, h, w, hv,
+                     diag, start, dev_dist, ring, dev_ring);
+  return launched(e);
+}
+
+int unetpp_components_best_cable(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num, const int32_t* dev_stats, int batch, int h,
+                                 int w, int capacity, double min_area, int min_h, int max_w, double min_aspect, uint8_t out_value,
+                                 uint8_t* dev_out, void* dev_workspace, void* stream) {
+  REQUIRE_ROBUST(e, dev_labels && dev_num && dev_stats && dev_out && dev_workspace);
+  CcWorkspace ws;
+  if (capacity < 2 || !cc_layout(batch, h, w, capacity, &ws))
+    return fail(e, UNETPP_E_UNSUPPORTED, "bad shape %dx%dx%d or capacity %d", batch, h, w, capacity);
+  if (std::isnan(min_area) || std::isnan(min_aspect)) return fail(e, UNETPP_E_UNSUPPORTED, "best cable: NaN parameter");
+  if (out_value == 0) return fail(e, UNETPP_E_UNSUPPORTED, "out_value must not be 0");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  uint8_t* keep = (uint8_t*)dev_workspace + ws.keep;
+  const BestCableRule r{min_area, min_aspect, min_h, max_w, h, w};
+  hipLaunchKernelGGL(best_cable_select_kernel, dim3((unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_num, (const int*)dev_stats, capacity, r,
+                     keep);
+  hipLaunchKernelGGL(cc_apply_kernel, dim3((unsigned)ws.nchunk, (unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_labels,
+                     (const uint8_t*)keep, hw, capacity, vec16(hw, dev_labels, dev_out), (unsigned)out_value, dev_out);
+  return launched(e);
+}
+
+size_t unetpp_roi_limit_workspace_bytes(int batch) {
+  return batch >= 1 && batch <= MAX_DIM ? align_up((size_t)batch * 4 * sizeof(int), 256) : 0;
+}
+
+int unetpp_roi_limit_u8(unetpp_engine* e, const uint8_t* dev_mask, const uint8_t* dev_cable, int batch, int h, int w, int pad,
+                        uint8_t* dev_out, void* dev_workspace, void* stream) {
+  REQUIRE_ROBUST(e, dev_mask && dev_cable && dev_out && dev_workspace);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  if (pad < 0) return fail(e, UNETPP_E_UNSUPPORTED, "pad %d: must not be negative", pad);
+  if ((uintptr_t)dev_workspace % 4) return fail(e, UNETPP_E_UNSUPPORTED, "dev_workspace must be 4-byte aligned");
+  const size_t n = (size_t)batch * h * w;
+  if (dev_out != dev_mask && overlaps(dev_mask, n, dev_out, n)) return fail(e, UNETPP_E_UNSUPPORTED, "dev_out overlaps dev_mask: in place means the same pointer");
+  if (overlaps(dev_cable, n, dev_out, n)) return fail(e, UNETPP_E_UNSUPPORTED, "dev_out aliases dev_cable");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  int* box = (int*)dev_workspace;
+  HIP_TRY(e, hipMemsetAsync(box, 0xff, (size_t)batch * 4 * sizeof(int), s));
+  hipLaunchKernelGGL(roi_box_kernel, dim3((unsigned)((h + 3) / 4), (unsigned)batch), dim3(DT_THREADS), 0, s, dev_cable, h, w, box);
+  const int vec = w % 4 == 0 && ((uintptr_t)dev_mask | (uintptr_t)dev_out) % 4 == 0;
+  hipLaunchKernelGGL(roi_apply_kernel, dim3((unsigned)((w + 4 * DT_THREADS - 1) / (4 * DT_THREADS)), (unsigned)h, (unsigned)batch), dim3(DT_THREADS), 0,
+                     s, dev_mask, (const int*)box, h, w, std::min(pad, MAX_DIM), vec, dev_out);
+  return launched(e);
+}
+
+int unetpp_row_width_median(unetpp_engine* e, const float* dev_widths, int batch, int h, double* dev_median, void* stream) {
+  REQUIRE_ROBUST(e, dev_widths && dev_median);
+  if (batch < 1 || batch > MAX_DIM || h < 1 || h > MAX_DIM) return fail(e, UNETPP_E_UNSUPPORTED, "bad shape %dx%d", batch, h);
+  if ((uintptr_t)dev_median % 8) return fail(e, UNETPP_E_UNSUPPORTED, "dev_median must be 8-byte aligned");
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(row_median_kernel, dim3(2u, (unsigned)batch), dim3(DT_THREADS), 0, (hipStream_t)stream, dev_widths, h, dev_median);
   return launched(e);
 }
 

@@ -136,3 +136,25 @@ def measure_frames(model, pred, mm_per_px=0.05, defect_classes=(3, 4, 5, 6), max
         a["defect_areas"] = {c: int(row[base + j]) for j, c in enumerate(defect_classes)}
         out.append({"diameter": d, "defect_analysis": a, "delta_d_mm": d["delta_d_mm"], "wrap_diameter_mm": d["dt_mm"]})
     return out
+
+
+def process_frames_robust(model, frames_bgr_u8, new_size=512, *, t_cable=0.50, t_tape=0.42, bg_margin=0.15, ct_margin=0.10, device=None, **post):
+    """infer_frame of infer_video_robust.py (:284-370) for B raw frames of one size at once, every step on the device:
+    letterbox to new_size, the model and exclusive_threshold with the call site's thresholds (segment_thresholded,
+    rule="exclusive"), unletterbox, steps 7-9 (robust.postprocess_robust, which takes `post`: close_ksize, min_area,
+    min_h_ratio, min_aspect, max_w_ratio, band_out, band_in, tape_min_area, pad, max_components, check) and steps 10-11.
+    Returns (mask_cable, mask_tape uint8 0/1 [B,frame_h,frame_w] on the device, metrics: a list of B dicts of
+    robust.MEASURE_FIELDS); the metrics are the one read-back.  create_overlay / putText and EventGate stay on the host."""
+    import torch
+    from . import robust
+    x = frames_bgr_u8
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not x.is_cuda:
+        x = x.to(device if device is not None else f"cuda:{model._device_index or 0}", non_blocking=True)
+    canvas, plan = robust.letterbox(model, x, new_size)
+    cable_s, tape_s = model.segment_thresholded(canvas, "exclusive", t_cable, t_tape, bg_margin, ct_margin)
+    cable = robust.unletterbox_masks(model, cable_s, plan)
+    tape = robust.unletterbox_masks(model, tape_s, plan)
+    cable, tape = robust.postprocess_robust(model, cable, tape, **post)
+    return cable, tape, robust.measure_robust(model, cable, tape)

@@ -211,9 +211,9 @@ def analyze_defects_np(pred2d, cable_cls=1, tape_cls=2, defect_classes=(3, 4, 5,
             "defect_areas": areas, "total_defect_area": int(sum(areas))}
 
 
-def make_wrap_scene(H, W, seed, noise=0.02, tape_start=None, cable_end=None, tape_end=None, cable=True, holes=14, classes7=False):
+def make_wrap_scene(H, W, seed, noise=0.02, tape_start=None, cable_end=None, tape_end=None, cable=True, holes=14, classes7=False, sway=0.03):
     """A wrapping frame as compute_diameter_metrics wants it, uint8 [H,W] of classes 0..2 (0..6 with classes7):
-      cable   class 1, rows [0, cable_end), half width about 0.08 W varying slowly, centre swaying slowly
+      cable   class 1, rows [0, cable_end), half width about 0.08 W varying slowly, centre swaying slowly by `sway` W
       tape    class 2, a sleeve 1.8 times as wide over rows [tape_start, tape_end): two flanks beside the cable where
               the cable runs, the full width below its end, so that the sleeve is one component and the cable another
       distractors  a class-2 blob in rows above the sleeve and a class-1 blob in rows below the cable's end (each with
@@ -225,7 +225,7 @@ def make_wrap_scene(H, W, seed, noise=0.02, tape_start=None, cable_end=None, tap
     the cable and its distractor (the speckle stays)."""
     r = np.random.default_rng(seed)
     y = np.arange(H)[:, None]; x = np.arange(W)[None, :]
-    cx = W / 2 + (W * 0.03) * np.sin(y / H * 6.28 * r.uniform(0.5, 2)) + r.uniform(-W * 0.05, W * 0.05)
+    cx = W / 2 + (W * sway) * np.sin(y / H * 6.28 * r.uniform(0.5, 2)) + r.uniform(-W * 0.05, W * 0.05)
     t0 = int(H * r.uniform(0.30, 0.45))
     tape_start = t0 if tape_start is None else int(tape_start)
     cable_end = H - H // 8 if cable_end is None else int(cable_end)

@@ -763,6 +763,60 @@ int unetpp_mask_disagreement(unetpp_engine* e, const uint8_t* dev_a, const uint8
                              const float* dev_logits, int num_classes, uint32_t* dev_n_diff, int32_t* dev_first,
                              float* dev_max_margin, uint32_t* dev_n_nan, void* stream);
 
+/* ---- rules on a probability map: threshold levels, the one-pass threshold scan, mean probability per component -------------
+ * What tools/inference_binary_optimized.py does with the softmax map of its sliding-window predict: apply_hysteresis
+ * (:116-136), apply_morphological_and_filtering (:139-176) and scan_thresholds (:179-270).  unet_amd/probmap.py is the
+ * NumPy form and holds the compositions; every result equals it exactly: float32 comparisons and integer sums.
+ *
+ * A probability plane is (dev_prob, pixel_stride, channel): channel `channel` of an array float32
+ * [B,h,w,pixel_stride] that starts at dev_prob (4-byte aligned), so pixel i of frame b is
+ * dev_prob[(b*h*w + i)*pixel_stride + channel]; 1 <= pixel_stride <= 256.  Class 1 of the [B,h,w,C] output of
+ * unetpp_tile_blend_f32 is read in place with pixel_stride = C, channel = 1; a dense [B,h,w] plane has pixel_stride 1.
+ * With pixel_stride 1 or 2 the plane is read with 16-byte loads wherever 16 pixels start on a 16-byte boundary, one float
+ * at a time elsewhere; nothing outside the array is read.  All entries queue their work on `stream` and allocate nothing.
+ *
+ * unetpp_prob_levels_f32: dev_codes uint8 [B,h,w] = 0 for p < t_low, 1 for t_low <= p < t_high, 2 for p >= t_high
+ *   (t_low <= t_high; NaN gives 0); h * w < 2^32.  The codes feed unetpp_morphology with mask0 = codes, match0 = 2 (the
+ *   seeds) and mask1 = codes, match1 = -1 (the low region).
+ *
+ * unetpp_prob_threshold_hist_f32: thresholds is a HOST array of n_thresholds float32 values, strictly ascending,
+ *   1 <= n_thresholds = T <= 256.  Per pixel k = the number of thresholds <= p, 0..T (NaN: 0).  dev_target uint8 [B,h,w];
+ *   g = 1 where the target equals target_class (0..255; -1: is non-zero), else 0.
+ *   dev_counts  uint32 [B,2,T+1]: [b,g,k] = pixels of frame b with that g and k whose target is not ignore_value
+ *   dev_outside uint32 [B]:       pixels whose target equals ignore_value (0..255, or -1 for none)
+ *   dev_total   NULL, or uint64 [2*(T+1) + 1] (8-byte aligned): the kernel ADDS the counts and then the outside counter
+ *               of all frames to it and never clears it.
+ *   dev_counts and dev_outside are cleared on `stream` inside the call.  One launch.  The confusion table of threshold j
+ *   (pred = p >= thresholds[j]) is a suffix sum: pred 1 is k > j.
+ *
+ * unetpp_components_prob_sum_f32: dev_labels int32 [B,h,w] of unetpp_components (h * w <= 2^30).  dev_sums uint64
+ *   [B,capacity+1] (8-byte aligned, cleared inside the call): [b,l] = the sum over the pixels with label l,
+ *   1 <= l <= capacity, of q(p) = floor(clamp(p, 0, 1) * 2^32), formed from the float's bits (q(1) = 2^32, q(NaN) = 0);
+ *   row 0 stays 0.  Integer adds only: the same bits whatever order they land in.
+ *
+ * unetpp_components_filter_mean: dev_out uint8 [B,h,w] = out_value where the pixel's component l has
+ *   stats AREA >= min_area and dev_prob_sums[b,l] >= thr_q * AREA (the product formed in 128 bits), i.e. a mean probability
+ *   >= thr_q / 2^32.  dev_num, dev_stats [B,capacity,5], capacity, dev_workspace (that of unetpp_components, same
+ *   arguments) and the overflow rule are those of unetpp_components_filter: a frame with num > capacity gives all zero.
+ *
+ * unetpp_probmap_layout: the pixels of a frame one workgroup of the first three kernels owns.
+ *
+ * Errors: UNETPP_E_INVALID for NULL where not allowed, a bad shape, plane, threshold list, class or capacity, a
+ * misaligned pointer.  No kernel is launched when an error is returned. */
+int unetpp_probmap_layout(int* span_pixels);
+int unetpp_prob_levels_f32(unetpp_engine* e, const float* dev_prob, int pixel_stride, int channel, int batch, int h, int w,
+                           float t_low, float t_high, uint8_t* dev_codes, void* stream);
+int unetpp_prob_threshold_hist_f32(unetpp_engine* e, const float* dev_prob, int pixel_stride, int channel,
+                                   const uint8_t* dev_target, int batch, int h, int w, const float* thresholds,
+                                   int n_thresholds, int target_class, int ignore_value, uint32_t* dev_counts,
+                                   uint32_t* dev_outside, uint64_t* dev_total, void* stream);
+int unetpp_components_prob_sum_f32(unetpp_engine* e, const int32_t* dev_labels, const float* dev_prob, int pixel_stride,
+                                   int channel, int batch, int h, int w, int capacity, uint64_t* dev_sums, void* stream);
+int unetpp_components_filter_mean(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num,
+                                  const int32_t* dev_stats, const uint64_t* dev_prob_sums, int batch, int h, int w,
+                                  int capacity, int64_t min_area, uint64_t thr_q, uint8_t out_value, uint8_t* dev_out,
+                                  void* dev_workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunetpp_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["unetpp_abi.hip", "unetpp_postproc.hip"]      # the engine; the post-processing entry points
-HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "frame_kernels.h", "components.h", "distance.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "nlmeans.h", "evaluation.h", "geometry.h", "tiling.h", os.path.join("..", "..", "include", "unetpp.h")]
+HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "frame_kernels.h", "components.h", "distance.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "nlmeans.h", "evaluation.h", "probmap.h", "geometry.h", "tiling.h", os.path.join("..", "..", "include", "unetpp.h")]
 
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
 PREC_EXACT, PREC_FAST, PREC_EXACT8 = 0, 1, 2
@@ -139,6 +139,11 @@ ABI = {
     "unetpp_evaluation_layout": (ci, [ctypes.POINTER(ci)]),
     "unetpp_confusion_u8": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
     "unetpp_mask_disagreement": (ci, [vp, vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp]),
+    "unetpp_probmap_layout": (ci, [ctypes.POINTER(ci)]),
+    "unetpp_prob_levels_f32": (ci, [vp, vp, ci, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, vp]),
+    "unetpp_prob_threshold_hist_f32": (ci, [vp, vp, ci, ci, vp, ci, ci, ci, f32p, ci, ci, ci, vp, vp, vp, vp]),
+    "unetpp_components_prob_sum_f32": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
+    "unetpp_components_filter_mean": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint8, vp, vp, vp]),
     "unetpp_distance_workspace_bytes": (cs, [ci, ci, ci]),
     "unetpp_distance_transform_u8": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, ctypes.c_float, ctypes.c_float, ctypes.c_uint8, vp, vp, vp]),
     "unetpp_components_best_cable": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, cd, ci, ci, cd, ctypes.c_uint8, vp, vp, vp]),

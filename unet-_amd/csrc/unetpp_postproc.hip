@@ -1,6 +1,6 @@
 // unetpp_postproc.hip — the post-processing entry points of the C ABI (include/unetpp.h): mask statistics, connected
 // components and their filters, the grey-level burr detectors, measurements, the distance transform and the robust loop's mask rules,
-// grey-frame enhancement and denoising, morphology, the two resizes and the tiling of sliding-window inference.  Each entry checks its arguments and queues kernels on the caller's
+// grey-frame enhancement and denoising, evaluation, the probability-map rules, morphology, the two resizes and the tiling of sliding-window inference.  Each entry checks its arguments and queues kernels on the caller's
 // stream.  Of an engine this file sees unetpp_engine_common (abi_common.h) and nothing else: no tensor, layer, arena or stream.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +24,7 @@
 #include "geometry.h"
 #include "morphology.h"
 #include "nlmeans.h"
+#include "probmap.h"
 #include "tiling.h"
 
 using namespace unetpp;
@@ -795,6 +796,97 @@ int unetpp_mask_disagreement(unetpp_engine* e, const uint8_t* dev_a, const uint8
   if (dev_n_nan) HIP_TRY(e, hipMemsetAsync(dev_n_nan, 0, (size_t)batch * sizeof(uint32_t), s));
   hipLaunchKernelGGL(mask_disagreement_kernel, eval_grid(hw, batch), dim3(EV_THREADS), 0, s, dev_a, dev_b, (unsigned)hw, dev_logits, num_classes,
                      eval_vec(dev_a, dev_b), (unsigned*)dev_n_diff, (unsigned*)dev_first, (unsigned*)dev_max_margin, (unsigned*)dev_n_nan);
+  return launched(e);
+}
+
+// ---- rules on a float32 probability plane: levels, the one-pass threshold scan, mean probability per component (probmap.h) ----
+int unetpp_probmap_layout(int* span_pixels) {
+  if (!span_pixels) return fail(nullptr, UNETPP_E_INVALID, "null argument");
+  *span_pixels = PM_SPAN;
+  return UNETPP_OK;
+}
+
+// channel `channel` of float32 [B,h,w,pixel_stride]; the array holds fewer than 2^40 floats, far above any device's memory
+static int plane_check(unetpp_engine* e, const float* dev_prob, int pixel_stride, int channel) {
+  if ((uintptr_t)dev_prob % 4) return fail(e, UNETPP_E_INVALID, "dev_prob must be 4-byte aligned");
+  if (pixel_stride < 1 || pixel_stride > 256 || channel < 0 || channel >= pixel_stride)
+    return fail(e, UNETPP_E_INVALID, "pixel_stride %d, channel %d: 1 <= pixel_stride <= 256, 0 <= channel < pixel_stride", pixel_stride, channel);
+  return UNETPP_OK;
+}
+
+static dim3 plane_grid(uint64_t hw, int batch) { return dim3((unsigned)((hw + PM_SPAN - 1) / PM_SPAN), (unsigned)batch); }
+
+int unetpp_prob_levels_f32(unetpp_engine* e, const float* dev_prob, int pixel_stride, int channel, int batch, int h, int w, float t_low,
+                           float t_high, uint8_t* dev_codes, void* stream) {
+  REQUIRE_ARGS(e, dev_prob && dev_codes);
+  if (int rc = eval_shape_check(e, batch, h, w, 1ull << 32)) return rc;
+  if (int rc = plane_check(e, dev_prob, pixel_stride, channel)) return rc;
+  if (!(t_low <= t_high)) return fail(e, UNETPP_E_INVALID, "thresholds %g, %g: need t_low <= t_high, neither NaN", (double)t_low, (double)t_high);
+  ENTER_DEVICE(e);
+  const uint64_t hw = (uint64_t)h * (uint64_t)w;
+  hipLaunchKernelGGL(prob_levels_kernel, plane_grid(hw, batch), dim3(PM_THREADS), 0, (hipStream_t)stream, dev_prob, pixel_stride, channel,
+                     (unsigned)hw, t_low, t_high, dev_codes);
+  return launched(e);
+}
+
+int unetpp_prob_threshold_hist_f32(unetpp_engine* e, const float* dev_prob, int pixel_stride, int channel, const uint8_t* dev_target, int batch,
+                                   int h, int w, const float* thresholds, int n_thresholds, int target_class, int ignore_value,
+                                   uint32_t* dev_counts, uint32_t* dev_outside, uint64_t* dev_total, void* stream) {
+  REQUIRE_ARGS(e, dev_prob && dev_target && thresholds && dev_counts && dev_outside);
+  if (int rc = eval_shape_check(e, batch, h, w, 1ull << 32)) return rc;
+  if (int rc = plane_check(e, dev_prob, pixel_stride, channel)) return rc;
+  if (n_thresholds < 1 || n_thresholds > PM_MAX_THRESHOLDS) return fail(e, UNETPP_E_INVALID, "n_thresholds %d: 1..%d", n_thresholds, PM_MAX_THRESHOLDS);
+  PmThresholds th{};
+  for (int j = 0; j < n_thresholds; ++j) {
+    if (std::isnan(thresholds[j]) || (j && !(thresholds[j - 1] < thresholds[j])))
+      return fail(e, UNETPP_E_INVALID, "thresholds must be strictly ascending numbers (entry %d)", j);
+    th.t[j] = thresholds[j];
+  }
+  if (target_class < -1 || target_class > 255) return fail(e, UNETPP_E_INVALID, "target_class %d: 0..255, or -1 for non-zero", target_class);
+  if (ignore_value < -1 || ignore_value > 255) return fail(e, UNETPP_E_INVALID, "ignore_value %d: 0..255, or -1 for none", ignore_value);
+  if ((uintptr_t)dev_total % 8) return fail(e, UNETPP_E_INVALID, "dev_total must be 8-byte aligned");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t hw = (uint64_t)h * (uint64_t)w;
+  HIP_TRY(e, hipMemsetAsync(dev_counts, 0, (size_t)batch * 2 * (n_thresholds + 1) * sizeof(uint32_t), s));
+  HIP_TRY(e, hipMemsetAsync(dev_outside, 0, (size_t)batch * sizeof(uint32_t), s));
+  hipLaunchKernelGGL(prob_threshold_hist_kernel, plane_grid(hw, batch), dim3(PM_THREADS), 0, s, dev_prob, pixel_stride, channel, dev_target,
+                     (unsigned)hw, th, n_thresholds, target_class, ignore_value, (unsigned*)dev_counts, (unsigned*)dev_outside,
+                     (unsigned long long*)dev_total);
+  return launched(e);
+}
+
+int unetpp_components_prob_sum_f32(unetpp_engine* e, const int32_t* dev_labels, const float* dev_prob, int pixel_stride, int channel, int batch,
+                                   int h, int w, int capacity, uint64_t* dev_sums, void* stream) {
+  REQUIRE_ARGS(e, dev_labels && dev_prob && dev_sums);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if (capacity < 2) return fail(e, UNETPP_E_INVALID, "capacity %d: at least 2 rows (background + one component)", capacity);
+  if (int rc = plane_check(e, dev_prob, pixel_stride, channel)) return rc;
+  if ((uintptr_t)dev_labels % 4 || (uintptr_t)dev_sums % 8) return fail(e, UNETPP_E_INVALID, "dev_labels must be 4-byte, dev_sums 8-byte aligned");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  HIP_TRY(e, hipMemsetAsync(dev_sums, 0, (size_t)batch * ((size_t)capacity + 1) * sizeof(uint64_t), s));
+  hipLaunchKernelGGL(components_prob_sum_kernel, plane_grid((uint64_t)hw, batch), dim3(PM_THREADS), 0, s, (const int*)dev_labels, dev_prob,
+                     pixel_stride, channel, hw, capacity, (unsigned long long*)dev_sums);
+  return launched(e);
+}
+
+int unetpp_components_filter_mean(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num, const int32_t* dev_stats,
+                                  const uint64_t* dev_prob_sums, int batch, int h, int w, int capacity, int64_t min_area, uint64_t thr_q,
+                                  uint8_t out_value, uint8_t* dev_out, void* dev_workspace, void* stream) {
+  REQUIRE_ARGS(e, dev_labels && dev_num && dev_stats && dev_prob_sums && dev_out && dev_workspace);
+  if (capacity < 2) return fail(e, UNETPP_E_INVALID, "capacity %d: at least 2 rows (background + one component)", capacity);
+  CcWorkspace ws;
+  if (!cc_layout(batch, h, w, capacity, &ws)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  uint8_t* keep = (uint8_t*)dev_workspace + ws.keep;
+  hipLaunchKernelGGL(cc_select_mean_kernel, dim3((unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_num, (const int*)dev_stats,
+                     (const unsigned long long*)dev_prob_sums, capacity, (long long)min_area, (unsigned long long)thr_q, keep);
+  hipLaunchKernelGGL(cc_apply_kernel, dim3((unsigned)ws.nchunk, (unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_labels,
+                     (const uint8_t*)keep, hw, capacity, vec16(hw, dev_labels, dev_out), (unsigned)out_value, dev_out);
   return launched(e);
 }
 

@@ -158,3 +158,24 @@ def process_frames_robust(model, frames_bgr_u8, new_size=512, *, t_cable=0.50, t
     tape = robust.unletterbox_masks(model, tape_s, plan)
     cable, tape = robust.postprocess_robust(model, cable, tape, **post)
     return cable, tape, robust.measure_robust(model, cable, tape)
+
+
+def process_frames_optimized(model, frames_bgr_u8, *, patch_size=384, stride=192, target_size=256, gate_thr=0.70, gate_class=1,
+                             channel_order="bgr", device=None, **post):
+    """The frame loop of tools/inference_binary_optimized.py's main() (:381-408) for B raw frames of one size, the map
+    never leaving the device: predict_tiled(blend="probs", gate_thr) (OptimizedSlidingWindowInference.predict with the
+    window gate), then probmap.postprocess_probmap on class `gate_class` of its output, read in place (apply_hysteresis,
+    apply_morphological_and_filtering; `post` takes its thr_high, thr_low, ksize, iterations, min_area, mean_prob_thr,
+    kernel_size, max_components, out_value, check).  Frames are BGR as cv2.imread returns them (channel_order="rgb" for
+    frames already converted).  Returns (pred_final uint8 [B,H,W], output float32 [B,H,W,C]) on the device."""
+    import torch
+    from . import probmap
+    x = frames_bgr_u8
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not x.is_cuda:
+        x = x.to(device if device is not None else f"cuda:{model._device_index or 0}", non_blocking=True)
+    _, output = model.predict_tiled(x, patch_size, stride, target_size, blend="probs", gate_thr=gate_thr, gate_class=gate_class,
+                                    channel_order=channel_order)
+    _, pred_final = probmap.postprocess_probmap(model, output, channel=int(gate_class), **post)
+    return pred_final, output

@@ -260,9 +260,41 @@ __device__ __forceinline__ void ws_epilogue(KernArgs<ConvArgs> a, const float16v
 // the constant 1 and the partial buffer, the counters and the share arithmetic are not compiled.
 // The arguments are read in place (KernArgs, conv3x3_mfma.h): each role fetches the fields it uses, and what a role needs
 // once per tile it reads again at the tile boundary instead of holding it across the chunk loop.
-template <int P, bool POOL, bool HEAD, bool UPF, bool C0F, int NW, int MWP, bool X8, bool CAT2, bool SPLITK>
+// UR (conv3x3_ws_uprows_kernel, `exact`, Cout = 32, fused upsample): the up chunks are multiplied on LOW-RESOLUTION ROWS and
+// interpolated in y afterwards, in the accumulators.  The upsample is separable,
+//   U[y'] = (1 - f(y')) T[r(y')] + f(y') T[r(y') + 1],     T[r] = the x-interpolation of low row r at full-resolution columns,
+// so with Y_dy[r][x] = sum_dx W[dy, dx] T[r][x + dx] (a 1x3 product on a low row, 32 pixels on the lanes)
+//   S[y] = sum_dy [0 <= y + dy < H] ((1 - f(y + dy)) Y_dy[r(y + dy)] + f(y + dy) Y_dy[r(y + dy) + 1]).
+// The row weights are wave-uniform: the fold is a scalar-weighted FMA on accumulator registers.  With k0 = y0 / 2 the rows
+// y0 + 2 m + 1 and y0 + 2 m + 2 read low rows k0 + m and k0 + m + 1 (tests/test_uprows_host.py), so a tile needs Y_dy[r] for 28
+// (dy, r) pairs instead of 48 (row, dy) products:
+//   * chunk order: the up chunks first (Z is not live while the Y accumulators are), then the skip chunks;
+//   * producers, up chunk: x-interpolation only, into the image T = low rows k0 - 1 .. k0 + 8 x columns x0 - 1 .. x0 + 32 (zeros
+//     outside the image) in the halo image's record layout; the low-res records of a tile's first up chunk arrive during the
+//     previous tile's last chunk;
+//   * consumer wave w: Y_dy[k0 + 2 w], Y_dy[k0 + 2 w + 1] for the three dy; wave 0 also (k0 - 1; dy -1, 0), wave 3 also
+//     (k0 + 8; dy 0, +1): 8, 6, 6, 8 accumulators, 72 MFMAs per up chunk in the busiest wave instead of 108;
+//   * fold, behind the last up chunk: wave w needs (k0 + 2 w - 1; dy -1, 0) from wave w - 1 and (k0 + 2 w + 2; dy 0, +1) from
+//     wave w + 1.  They pass through the stage buffer the last up chunk has released (48 KB); the producers hold that buffer's
+//     refill back behind two extra barriers.  The edge rows of waves 0 and 3 go through LDS as well (16 KB behind the scale /
+//     bias table), so that six, not eight, Y accumulators are live beside the four Z rows: 249 registers, no spill.  Each Z row
+//     sums its terms in the fixed order dy = -1, 0, +1, lower row first: bitwise reproducible and batch-row invariant.
+// ur_row / ur_slot: the ownership table, restated in tests/test_uprows_host.py.
+__host__ __device__ constexpr int ur_row(int m, int dy) { return (m + dy + 1) / 2 - 1; }      // low row of image row 4 w + m + dy, relative to k0 + 2 w: -1 .. 2
+// exchange slots (one accumulator, 4 KB each) of the boundary between waves b and b + 1: 0, 1 = (k0 + 2 b + 1; dy -1, 0) going up
+// to wave b + 1, 2, 3 = (k0 + 2 b + 2; dy 0, +1) going down to wave b
+__host__ __device__ constexpr int ur_slot(int boundary, int i) { return boundary * 4 + i; }
+constexpr int UR_EDGE_BYTES = 4 * 4096;      // LDS behind the scale / bias table: (k0 - 1; dy -1, 0) of wave 0, (k0 + 8; dy 0, +1) of wave 3
+
+// fraction of the bilinear x2 upsample (align_corners=True) at destination index `dst` whose lower source index is `i0`
+__device__ __forceinline__ float up_frac(float scale, int dst, int i0) {
+  return fminf(fmaxf(scale * (float)max(dst, 0) - (float)i0, 0.f), 1.f);
+}
+
+template <int P, bool POOL, bool HEAD, bool UPF, bool C0F, int NW, int MWP, bool X8, bool CAT2, bool SPLITK, bool UR = false>
 __device__ __forceinline__ void conv3x3_ws_body() {
   using C = WsCfg<P, UPF, C0F, NW, MWP, X8>;
+  static_assert(!UR || (UPF && P == 2 && !X8 && NW == 1 && MWP == 4 && !SPLITK), "low-row up chunks: exact, Cout = 32, fused upsample");
   static_assert(!SPLITK || (!UPF && !C0F && !HEAD), "split-K: plain and pooling layers only (launch_ws_k)");
   KernArgs<ConvArgs> a = kernargs<ConvArgs>();
   static_assert(!C0F || (!UPF && !HEAD && P == 2 && NW == 1), "fused first block: exact mode, no other fusion in the loader");
@@ -690,7 +722,9 @@ __device__ __forceinline__ void conv3x3_ws_body() {
     }
     unsigned voff0[ITERS];
     __amdgpu_buffer_rsrc_t rsrc0, rsrc1;
-    constexpr int LSR = UPF ? C::LS_ITERS : 1, UPR = UPF ? C::UP_ROUNDS : 1;
+    // UR: interpolation items = low rows of T x column blocks x channel quads
+    constexpr int UR_ITEMS = C::LSH * C::BLK_X * 4, UR_ROUNDS = (UR_ITEMS + C::NPROD * 64 - 1) / (C::NPROD * 64);
+    constexpr int LSR = UPF ? C::LS_ITERS : 1, UPR = UR ? UR_ROUNDS : UPF ? C::UP_ROUNDS : 1;
     unsigned voffL[LSR];
     // interpolation item r of this lane: block (by, bx) x channel quad q
     int up_o00[UPR], up_o01[UPR], up_o10[UPR];          // staging offsets of the corners (ra,ca), (ra,cb), (rb,ca)
@@ -705,7 +739,21 @@ __device__ __forceinline__ void conv3x3_ws_body() {
 #ifdef UNETPP_WS_DBG
     if (a->dbg & 32) rd_swap = 0;
 #endif
-    if (UPF) {
+    if (UR) {
+      // item = (row of T, column block, channel quad): the block's two pixels of that row, [0], [1] (q >= 2: in the opposite order)
+#pragma unroll
+      for (int r = 0; r < UPR; ++r) {
+        const int i = pw * 64 + lane + r * (C::NPROD * 64);
+        const int q = i & 3, blk = i >> 2;
+        const int tr = blk / C::BLK_X, bx = blk - tr * C::BLK_X;
+#pragma unroll
+        for (int px = 0; px < 2; ++px) {
+          const int hp = tr * HALO_W + 2 * bx + (px ^ ((q >> 1) & 1));
+          up_st[r][px] = (hp / PPP) * 1024 + ((q >> 1) * PPP + hp % PPP) * 16 + (q & 1) * 8;
+        }
+        if (i >= UR_ITEMS) up_st[r][0] = -1;
+      }
+    } else if (UPF) {
 #pragma unroll
       for (int r = 0; r < UPR; ++r) {
         const int i = pw * 64 + lane + r * (C::NPROD * 64);
@@ -722,6 +770,31 @@ __device__ __forceinline__ void conv3x3_ws_body() {
         if (i >= C::UP_ITEMS) up_st[r][0] = -1;
       }
     }
+
+    // UR: byte offsets of this lane's parts of the low-res records of the tile at (y0, x0): rows k0 - 1 .. k0 + 8 (a row outside the
+    // image reads zeros: T's zero rows), 18 columns from the first one the tile's halo touches
+    auto ur_ls_offsets = [&](int y0, int x0, unsigned (&vo)[LSR]) {
+      const int yfirst = (y0 >> 1) - 1, xbase = (int)(up_sw * (float)max(x0 - 1, 0));
+      constexpr int PXP = 1024 / C::LS_REC, PARTS = C::LS_REC / 16;
+#pragma unroll
+      for (int it = 0; it < LSR; ++it) {
+        const int lp = (pw + it * C::NPROD) * PXP + lane / PARTS;
+        const int ly = lp / C::LSW, lx = lp - ly * C::LSW;
+        const int yy = yfirst + ly, xx = min(xbase + lx, Ws - 1);
+        vo[it] = (lp < C::LS_PX && yy >= 0 && yy < Hs) ? (unsigned)((yy * Ws + xx) * C::LS_REC + (lane % PARTS) * 16) : OOB;
+      }
+    };
+    // the low-res records of up chunk j (channel block j of in1) into staging buffer j & 1; inside an M0 run
+    auto ur_ls_dma = [&](__amdgpu_buffer_rsrc_t rs, const unsigned (&vo)[LSR], int j) {
+      const int soffL = j * (int)plane_bytes1;
+      const unsigned dstL = opaque(lds_base + 2 * C::BUF_BYTES + (j & 1) * C::LS_BYTES + pw * 1024);
+#pragma unroll
+      for (int it = 0; it < LSR; ++it) {
+        const int piece = pw + it * C::NPROD;
+        if (it + 1 < LSR || C::LS_PIECES % C::NPROD == 0 || piece < C::LS_PIECES)
+          blds16_run(rs, vo[it], soffL, dstL + it * (C::NPROD * 1024));
+      }
+    };
 
     auto setup_tile = [&](int n, int y0, int x0) {
       if (y0 >= 1 && y0 + TH < H && x0 >= 1 && x0 + TW < W) {          // halo rows y0-1 .. y0+TH, columns x0-1 .. x0+TW
@@ -749,7 +822,33 @@ __device__ __forceinline__ void conv3x3_ws_body() {
         const unsigned img_bytes_cat = (unsigned)H * (unsigned)W * (unsigned)(P * a->C1 * 2);
         rsrc1 = __builtin_amdgcn_make_buffer_rsrc((void*)(a->in1 + (size_t)n * (img_bytes_cat >> 1)), 0, (int)img_bytes_cat, 0x00020000);
       }
-      if (UPF) {
+      if (UR) {
+        rsrc1 = __builtin_amdgcn_make_buffer_rsrc((void*)(a->in1 + (size_t)n * (img_bytes1 >> 1)), 0, (int)img_bytes1, 0x00020000);
+        ur_ls_offsets(y0, x0, voffL);
+        const int xbase = (int)(up_sw * (float)max(x0 - 1, 0));
+#pragma unroll
+        for (int r = 0; r < UPR; ++r) {
+          const int i = pw * 64 + lane + r * (C::NPROD * 64);
+          const int q = i & 3, blk = i >> 2;
+          const int tr = min(blk / C::BLK_X, C::LSH - 1), bx = blk % C::BLK_X;
+          // the block's two image columns, as in the 2x2 scheme below: an odd one and the even one after it share their corner pair
+          const int gxA = x0 + 2 * bx - 1;
+          const int gxR = (gxA + 1 < W) ? gxA + 1 : gxA;
+          const int xx0 = min((int)(up_sw * (float)max(gxR, 0)), Ws - 1);
+          const int xx1 = xx0 + (xx0 < Ws - 1 ? 1 : 0);
+          const int rx0 = min(max(xx0 - xbase, 0), C::LSW - 1), rx1 = min(max(xx1 - xbase, 0), C::LSW - 1);
+          up_o00[r] = (tr * C::LSW + rx0) * C::LS_REC + q * 8 + rd_swap;
+          up_o01[r] = (tr * C::LSW + rx1) * C::LS_REC + q * 8 + rd_swap;
+          const int xs = (q >> 1) & 1;
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            const int gx = gxA + (k ^ xs);
+            const bool inx = gx >= 0 && gx < W;
+            const float lx1 = up_frac(up_sw, gx, xx0);
+            up_wx[r][2 * k] = inx ? 1.f - lx1 : 0.f; up_wx[r][2 * k + 1] = inx ? lx1 : 0.f;
+          }
+        }
+      } else if (UPF) {
         rsrc1 = __builtin_amdgcn_make_buffer_rsrc((void*)(a->in1 + (size_t)n * (img_bytes1 >> 1)), 0, (int)img_bytes1, 0x00020000);
         const int ybase = (int)(up_sh * (float)max(y0 - 1, 0)), xbase = (int)(up_sw * (float)max(x0 - 1, 0));
         constexpr int PXP = 1024 / C::LS_REC, PARTS = C::LS_REC / 16;
@@ -785,8 +884,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
           for (int k = 0; k < 2; ++k) {
             const int gy = gyA + k, gx = gxA + (k ^ xs);
             const bool iny = gy >= 0 && gy < H, inx = gx >= 0 && gx < W;
-            const float ly1 = fminf(fmaxf(up_sh * (float)max(gy, 0) - (float)yy0, 0.f), 1.f);
-            const float lx1 = fminf(fmaxf(up_sw * (float)max(gx, 0) - (float)xx0, 0.f), 1.f);
+            const float ly1 = up_frac(up_sh, gy, yy0), lx1 = up_frac(up_sw, gx, xx0);
             up_wy[r][2 * k] = iny ? 1.f - ly1 : 0.f; up_wy[r][2 * k + 1] = iny ? ly1 : 0.f;   // zero padding: all weights 0
             up_wx[r][2 * k] = inx ? 1.f - lx1 : 0.f; up_wx[r][2 * k + 1] = inx ? lx1 : 0.f;
           }
@@ -893,6 +991,52 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       }
     };
 
+    // UR: the same for the image T of up chunk j -- x-interpolation only, two corners and two pixels per item
+    auto up_rows_rounds = [&](int j, int halo_off) {
+      typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+      const char* ls = smem + 2 * C::BUF_BYTES + (j & 1) * C::LS_BYTES;
+      u32x2 hq[UPR][2], lq[UPR][2];                      // corners (r, ca), (r, cb): 4 channels each
+#pragma unroll
+      for (int r = 0; r < UPR; ++r) {
+        const int off[2] = {up_o00[r], up_o01[r]};
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          hq[r][k] = *(const u32x2*)(ls + off[k]);
+          lq[r][k] = *(const u32x2*)(ls + (off[k] ^ 32));
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);                 // every read first, as above
+      WS_STAMP_IN(8)
+#pragma unroll
+      for (int r = 0; r < UPR; ++r) {
+        float v[2][4];                                   // [pixel kx][channel]
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float cc[2];
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            if (e & 1) asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(cc[k]) : "v"(hq[r][k][e >> 1]), "v"(lq[r][k][e >> 1]));
+            else asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,1]" : "=v"(cc[k]) : "v"(hq[r][k][e >> 1]), "v"(lq[r][k][e >> 1]));
+          }
+#pragma unroll
+          for (int kx = 0; kx < 2; ++kx) v[kx][e] = fmaf(up_wx[r][2 * kx + 1], cc[1], up_wx[r][2 * kx] * cc[0]);
+        }
+        WS_STAMP_IN(9)
+        if (up_st[r][0] >= 0) {
+#pragma unroll
+          for (int kx = 0; kx < 2; ++kx) {
+            unsigned h0, h1, l0, l1;
+            split_pack2(v[kx][0], v[kx][1], h0, l0);
+            split_pack2(v[kx][2], v[kx][3], h1, l1);
+            char* dst = smem + halo_off + up_st[r][kx];
+            *(u32x2*)dst = (u32x2){h0, h1};
+            *(u32x2*)(dst + KG * PPP * 16) = (u32x2){l0, l1};
+          }
+        }
+        WS_STAMP_IN(10)
+      }
+    };
+
     // HANDOFF: the epilogue of the accumulator pair consumer wave `pw` left in LDS for the previous tile
     const int stg_base = 2 * C::BUF_BYTES + 2 * C::LS_BYTES + 2 * C::PATCH_BYTES;
     int hn = -1, hty = 0, htx = 0, hct = 0;            // the cursor's digits of that tile (not y0, x0 as well); hn < 0: none yet
@@ -918,6 +1062,21 @@ __device__ __forceinline__ void conv3x3_ws_body() {
 #endif
     WS_EVT(51)
     decode_first(slot);
+    // UR: the low-res records of a tile's first up chunk, for the tile the cursor stands on (an M0 run of its own)
+    auto ur_first_records = [&]() {
+      unsigned vn[LSR];
+      ur_ls_offsets(dec_ty * TH, dec_tx * TW, vn);
+      const int n1 = __builtin_amdgcn_readfirstlane(dec_n);      // (wave-uniform; a first tile's digits come out of the vector ALU)
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(a->in1 + (size_t)n1 * (img_bytes1 >> 1)), 0, (int)img_bytes1, 0x00020000);
+      const unsigned keep = m0_run_begin();
+      ur_ls_dma(rs, vn, 0);
+      m0_run_end(keep);
+    };
+    if constexpr (UR) {      // the first tile's: nothing to hide them behind; the consumers meet this barrier too
+      ur_first_records();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      lds_barrier();
+    }
     for (int tile = slot; tile < tiles_end(); tile += tile_step(), decode_next()) {
       const int n = dec_n, y0 = dec_ty * TH, x0 = dec_tx * TW;
       WS_EVT(52)
@@ -925,13 +1084,18 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       const int handoff_c = opaque((handoff_on() && hn >= 0) ? 1 : -1);
       KernArgs<ConvArgs> at = REREAD ? kernargs_again(a) : a;
       const int nchunks = at->nchunks;
-      const bool slabs_stay = nchunks == 2 && at->nct == 1 && KS == 1;
+      const bool slabs_stay = !UR && nchunks == 2 && at->nct == 1 && KS == 1;      // (UR: three chunks at least)
       const int chunks_per_share = KS == 1 ? nchunks : nchunks / KS;
       const char* wsrc = (const char*)at->wpk + (size_t)dec_ct * nchunks * C::SLAB_BYTES;
       const int c_begin = dec_ks * chunks_per_share, c_end = c_begin + opaque(chunks_per_share);       // this workgroup's share of K (opaque: no "loop runs at all" mask kept)
       setup_tile(n, y0, x0);
       WS_STAMP(7)
-      for (int c = c_begin; c < c_end; ++c, ++g) {
+      const int nup = nchunks - nch0;                  // UR: the up chunks run first, then the skip chunks
+      for (int cj = c_begin; cj < c_end; ++cj, ++g) {
+        const int c = UR ? (cj < nup ? cj + nch0 : cj - nup) : cj;
+        // UR: this iteration refills the stage buffer of the last up chunk, which the consumers use for their exchange of Y
+        // accumulators (behind the barrier that published the first skip chunk): wait until they have written and read it
+        if (UR && cj == nup + 1) { lds_barrier(); lds_barrier(); }
         const int buf = (g & 1) * C::BUF_BYTES;
         // One destination and one source per chunk, each piece a compile-time constant further on.  opaque(): the compiler
         // otherwise precomputes every piece's address outside the tile loop (nine 64-bit slab offsets, six LDS
@@ -973,7 +1137,19 @@ __device__ __forceinline__ void conv3x3_ws_body() {
           }
         }
         if (!UPF) { m0_run_end(m0_keep); WS_STAMP(0) }
-        if (UPF) {
+        if constexpr (UR) {
+          if (cj + 1 < nup) ur_ls_dma(rsrc1, voffL, cj + 1);      // low-res records of the NEXT up chunk
+          m0_run_end(m0_keep);
+          if (cj == nchunks - 1 && tile + tile_step() < tiles_end()) {      // ... and of the next tile's first: a look ahead with the cursor
+            const int k_ks = dec_ks, k_ct = dec_ct, k_tx = dec_tx, k_ty = dec_ty, k_n = dec_n;
+            decode_next();
+            ur_first_records();
+            dec_ks = k_ks; dec_ct = k_ct; dec_tx = k_tx; dec_ty = k_ty; dec_n = k_n;
+          }
+          if (c >= nch0) { WS_STAMP(3) } else { WS_STAMP(0) }
+          if (cj < nup) up_rows_rounds(cj, buf);
+          if (c >= nch0) { WS_STAMP(4) } else { WS_STAMP(0) }
+        } else if (UPF) {
 #ifdef UNETPP_WS_DBG
           if (!(a->dbg & 2))
 #endif
@@ -1092,9 +1268,32 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       }
   };
 
+  // UR: fragment offsets into the image T (rows k0 - 1 .. k0 + 8, the halo image's layout): this wave's two rows k0 + 2 w,
+  // k0 + 2 w + 1 and, waves 0 and 3, the tile's first / last row of T
+  constexpr int TR = UR ? 3 : 1;
+  int t_off[TR][3];
+  if (UR) {
+#pragma unroll
+    for (int r = 0; r < TR; ++r)
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) {
+        const int tr = r < 2 ? 2 * cw + 1 + r : (cw == 0 ? 0 : C::LSH - 1);
+        const int hp = tr * HALO_W + (lane & 31) + dx;
+        t_off[r][dx] = (hp / PPP) * 1024 + ((lane >> 5) * PPP + hp % PPP) * 16;
+      }
+  }
+  struct TFrag { half8 h[TR], l[TR]; };
+  // one split product (lo wh, hi wl, hi wh, as run_mfma) of T row r into a Y accumulator
+  auto ur_mfma = [&](float16v& y, const BFrag& fb, const TFrag& ft, int r, bool first) {
+    const float16v zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    y = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb.h[0], ft.l[r], first ? zero : y, 0, 0, 0);
+    y = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb.l[0], ft.h[r], y, 0, 0, 0);
+    y = __builtin_amdgcn_mfma_f32_32x32x16_f16(fb.h[0], ft.h[r], y, 0, 0, 0);
+  };
+
   int g = 0;
 #ifdef UNETPP_WS_DBG
-  unsigned long long st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // [0] barrier, [1] chunk, [2] epilogue, [3] accumulator init
+  unsigned long long st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // [0] barrier, [1] chunk, [2] epilogue, [3] accumulator init (UR: and the fold)
   unsigned long long st_t = __builtin_readcyclecounter();
   const unsigned long long rt_begin = __builtin_amdgcn_s_memrealtime();     // 100 MHz, one clock for the whole chip
   WS_EVLOG(0)
@@ -1102,6 +1301,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
   if (ev_ptr) *ev_ptr++ = (62ull << 56) | rt_begin;
 #endif
   decode_first(slot);
+  if constexpr (UR) lds_barrier();                          // the producers' barrier behind the first tile's low-res records
   for (int tile = slot; tile < tiles_end(); tile += tile_step(), decode_next()) {
     const int n = dec_n, y0 = dec_ty * TH, x0 = dec_tx * TW;
     const int ct = dec_ct, ks = dec_ks;
@@ -1111,7 +1311,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
     for (int m = 0; m < MW; ++m)
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
-        if (a->zinit && ks == 0) {    // accumulators start from the low-resolution half of the layer (tapmm_ws.h); uniform branch
+        if (!UR && a->zinit && ks == 0) {    // accumulators start from the low-resolution half of the layer (tapmm_ws.h); uniform branch
           typedef __attribute__((ext_vector_type(4))) float f32x4;
           const int gy = y0 + cw * MW + m, gx = x0 + (lane & 31);
           const bool in = gy < H && gx < W;
@@ -1125,15 +1325,151 @@ __device__ __forceinline__ void conv3x3_ws_body() {
           }
         }
       }
-    const bool from_zero = a->zinit == nullptr || ks != 0;
-    int4v x9[MW];                                           // EXACT8: the ninth tap's 8-bit operand of the previous chunk, see there
+    const bool from_zero = !UR && (a->zinit == nullptr || ks != 0);      // (UR: the fold writes every accumulator)
+    int4v x9[MW];                                          // EXACT8: the ninth tap's 8-bit operand of the previous chunk, see there
     if (X8) {
 #pragma unroll
       for (int m = 0; m < MW; ++m) x9[m] = (int4v){0, 0, 0, 0};     // (finite bytes: a tile's first chunk meets zero weights there)
     }
     WS_STAMP(3)
-    for (int c = c_begin; c < c_end; ++c, ++g) {
-      lds_barrier();                                      // chunk g is in stage buffer g & 1
+    // UR: the tile's up chunks (a loop of their own: the Y accumulators live here, Z only behind the fold), then the fold; the
+    // loop below is left with the skip chunks
+    const int ur_nup = UR ? a->nchunks - nch0 : 0;
+    if constexpr (UR) {
+      float16v yo[2][3], ye[2];                           // Y_dy of the wave's two rows [row][dy + 1]; of its edge row (wave 0: dy -1, 0; wave 3: dy 0, +1)
+      // (the tile's first up chunk is a copy of the code that starts every accumulator from the MFMA's zero operand: no test per step)
+      auto up_chunk = [&](auto first_tag) {
+        constexpr bool FIRST = decltype(first_tag)::value;
+        lds_barrier();                                    // chunk g is in stage buffer g & 1
+        WS_STAMP(0)
+        const char* halo = smem + (g & 1) * C::BUF_BYTES;
+        const char* slab = halo + C::HALO_BYTES;
+#ifdef UNETPP_WS_DBG
+        if (a->dbg & 16) return;
+#endif
+        // ---- up chunk: 1x3 products on the wave's rows of T into the Y accumulators.  dx-major as below; a step is one tap:
+        // one weight fragment against the two (three) row fragments of its column shift, the next step's fragments read first.
+        TFrag ft0, ft1;
+        BFrag fb0, fb1;
+        auto load_t = [&](TFrag& f, int dx, int r0, int r1) {
+#pragma unroll
+          for (int r = 0; r < TR; ++r)
+            if (r >= r0 && r < r1 && (r < 2 || cw == 0 || cw == C::NCONS - 1)) {
+              const char* p = halo + t_off[r][dx];
+              f.h[r] = *(const half8*)p;
+              f.l[r] = *(const half8*)(p + KG * PPP * 16);
+            }
+        };
+        load_t(ft0, 0, 0, TR);
+        load_b(fb0, slab, 0);
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          TFrag& ft = (dx & 1) ? ft1 : ft0;
+          TFrag& ftn = (dx & 1) ? ft0 : ft1;
+#pragma unroll
+          for (int dy = 0; dy < 3; ++dy) {
+            const int step = dx * 3 + dy;
+            BFrag& fb = (step & 1) ? fb1 : fb0;
+            BFrag& fbn = (step & 1) ? fb0 : fb1;
+            if (step + 1 < 9) load_b(fbn, slab, ((step + 1) % 3) * 3 + (step + 1) / 3);
+            if (dx < 2) load_t(ftn, dx + 1, dy, dy + 1);
+            __builtin_amdgcn_sched_barrier(0);
+#ifdef UNETPP_WS_DBG
+            if (!(a->dbg & 4))
+#endif
+            {
+              const bool Z0 = FIRST && dx == 0;           // (a constant once the loops are unrolled)
+              ur_mfma(yo[0][dy], fb, ft, 0, Z0);
+              ur_mfma(yo[1][dy], fb, ft, 1, Z0);
+              if (cw == 0) { if (dy < 2) ur_mfma(ye[dy < 2 ? dy : 0], fb, ft, 2, Z0); }
+              else if (cw == C::NCONS - 1) { if (dy >= 1) ur_mfma(ye[dy >= 1 ? dy - 1 : 0], fb, ft, 2, Z0); }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+        WS_STAMP(1)
+      };
+      up_chunk(std::true_type());
+      ++g;
+      for (int c = 1; c < ur_nup; ++c, ++g) up_chunk(std::false_type());
+      // ---- fold: Z rows from the Y accumulators.  Behind the barrier that publishes the first skip chunk every consumer wave has
+      // left the last up chunk's stage buffer, and the producers do not refill it before the second barrier further down.
+      lds_barrier();
+      WS_STAMP(0)
+      typedef __attribute__((ext_vector_type(4))) float f32x4;
+      // slots 0 .. 11 (ur_slot) lie over the stage buffer, the four edge slots behind the scale / bias table (UR_EDGE_BYTES more LDS)
+      constexpr int UR_EDGE = 12;
+      char* xb0 = smem + ((g - 1) & 1) * C::BUF_BYTES + lane * 16;
+      char* xe = smem + C::LDS_BYTES + 32 * 8 - UR_EDGE * 4096 + lane * 16;
+      auto put = [&](int slot, const float16v& v) {
+        char* xb = slot >= UR_EDGE ? xe : xb0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *(f32x4*)(xb + slot * 4096 + q * 1024) = (f32x4){v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
+      };
+      auto get = [&](int slot) {
+        float16v v;
+        const char* xb = slot >= UR_EDGE ? xe : xb0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x4 v4 = *(const f32x4*)(xb + slot * 4096 + q * 1024);
+          v[4 * q] = v4[0]; v[4 * q + 1] = v4[1]; v[4 * q + 2] = v4[2]; v[4 * q + 3] = v4[3];
+        }
+        return v;
+      };
+      if (cw < C::NCONS - 1) { put(ur_slot(cw, 0), yo[1][0]); put(ur_slot(cw, 1), yo[1][1]); }
+      if (cw > 0) { put(ur_slot(cw - 1, 2), yo[0][1]); put(ur_slot(cw - 1, 3), yo[0][2]); }
+      // the edge rows' accumulators of waves 0 and 3 take the same way, through four slots of their own (UR_EDGE): every wave then
+      // folds the same program, and its registers hold six Y accumulators instead of eight while the Z rows form
+      if (cw == 0) { put(UR_EDGE, ye[0]); put(UR_EDGE + 1, ye[1]); }
+      if (cw == C::NCONS - 1) { put(UR_EDGE + 2, ye[0]); put(UR_EDGE + 3, ye[1]); }
+      lds_barrier();
+      const int prev_slot = cw == 0 ? UR_EDGE : ur_slot(cw - 1, 0);                      // (k0 + 2 w - 1; dy -1, 0)
+      const int next_slot = cw == C::NCONS - 1 ? UR_EDGE + 2 : ur_slot(cw, 2);            // (k0 + 2 w + 2; dy 0, +1)
+      // Y_dy of low row k0 + 2 w + l, l = -1 .. 2: the wave's own or one out of the exchange
+      auto ysel = [&](int l, int dy) -> float16v {
+        if (l == 0) return yo[0][dy];
+        if (l == 1) return yo[1][dy];
+        if (l < 0) return get(prev_slot + (dy < 2 ? dy : 0));
+        return get(next_slot + (dy >= 1 ? dy - 1 : 0));
+      };
+      const int Hs = H >> 1;
+      const float up_sh = Hs > 1 ? (float)(Hs - 1) / (float)(H - 1) : 0.f;      // (the producers' expression)
+#pragma unroll
+      for (int m = 0; m < MW; ++m) {
+        float16v z;
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+          const int l = ur_row(m, dy - 1);
+          const int yrow = y0 + cw * MW + m + dy - 1, r = (y0 >> 1) + 2 * cw + l;
+          const bool in = yrow >= 0 && yrow < H;       // a tap outside the image contributes nothing
+          const float f = up_frac(up_sh, yrow, r);
+          const float wa = in ? 1.f - f : 0.f, wb = in ? f : 0.f;
+          const float16v ya = ysel(l, dy);
+#pragma unroll
+          for (int e = 0; e < 16; ++e) z[e] = dy == 0 ? wa * ya[e] : fmaf(wa, ya[e], z[e]);
+          const float16v yb = ysel(l + 1, dy);
+#pragma unroll
+          for (int e = 0; e < 16; ++e) z[e] = fmaf(wb, yb[e], z[e]);
+        }
+        acc[m][0] = z;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      lds_barrier();
+      // a_off again, from a lane number the compiler cannot trace back: worked out here, per tile, the eighteen offsets take no
+      // registers while the Y accumulators are live
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+#pragma unroll
+      for (int r = 0; r < MW + 2; ++r)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          const int hp = (cw * MW + r) * HALO_W + (ln & 31) + dx;
+          a_off[r][dx] = (hp / PPP) * 1024 + ((ln >> 5) * PPP + hp % PPP) * 16;
+        }
+      WS_STAMP(3)
+    }
+    for (int c = UR ? ur_nup : c_begin; c < c_end; ++c, ++g) {
+      if (!(UR && c == ur_nup)) lds_barrier();            // chunk g is in stage buffer g & 1 (UR: the fold has met the first skip chunk's)
       WS_STAMP(0)
       const char* halo = smem + (g & 1) * C::BUF_BYTES;
       const char* slab = halo + C::HALO_BYTES;
@@ -1414,6 +1750,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs) {
 template <int P, bool POOL, int NW = 1, int MWP = 4, bool X8 = false, bool CAT2 = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_ws_splitk_kernel(ConvArgs) {
   conv3x3_ws_body<P, POOL, false, false, false, NW, MWP, X8, CAT2, true>();
+}
+// `exact`, Cout = 32, fused upsample, at least two skip chunks: the up chunks on low-resolution rows (UR, above)
+__global__ __launch_bounds__(512, 2) void conv3x3_ws_uprows_kernel(ConvArgs) {
+  conv3x3_ws_body<2, false, false, true, false, 1, 4, false, false, false, true>();
 }
 
 }  // namespace unetpp

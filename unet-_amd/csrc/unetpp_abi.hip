@@ -235,10 +235,10 @@ hipError_t launch_conv_k(const LaunchCtx& cx, const ConvArgs& a, hipStream_t s) 
 
 // wave-specialised kernel (conv3x3_ws.h): 16-row tiles (Cout = 32) or 8-row tiles (Cout % 64 == 0), one persistent workgroup per CU
 template <int P, bool POOL, bool HEAD, bool UPF, bool C0F = false, int NW = 1, int MW = 4, bool X8 = false, bool CAT2 = false>
-hipError_t launch_ws_k(const LaunchCtx& cx, ConvArgs a, hipStream_t s) {
+hipError_t launch_ws_k(const LaunchCtx& cx, ConvArgs a, hipStream_t s, bool uprows = false) {
   using C = WsCfg<P, UPF, C0F, NW, MW, X8>;
   a.tiles_x = (a.W + C::TW - 1) / C::TW; a.tiles_y = (a.H + C::TH - 1) / C::TH; a.nct = a.Cout / C::BN;
-  const int lds = C::LDS_BYTES + a.Cout * 8 + (HEAD ? ((a.head_C * 33 * 4 + 15) / 16) * 16 : 0);
+  const int lds = C::LDS_BYTES + a.Cout * 8 + (HEAD ? ((a.head_C * 33 * 4 + 15) / 16) * 16 : 0) + (uprows ? UR_EDGE_BYTES : 0);
   // Split-K plan (small batches): a layer with fewer tiles than a quarter of the CUs shares each tile's K-chunks among
   // `ksplit` workgroups -- the largest divisor of the chunk count that still leaves every workgroup four chunks and fits
   // the chip (measured at batch 1, 512x512: levels 3-4 gain 10-35 us per layer; two-way splits and two-chunk shares gain nothing:
@@ -266,6 +266,10 @@ hipError_t launch_ws_k(const LaunchCtx& cx, ConvArgs a, hipStream_t s) {
   if constexpr (!UPF && !C0F && !HEAD) {
     if (ks > 1) k = conv3x3_ws_splitk_kernel<P, POOL, NW, MW, X8, CAT2>;
   }
+  // `exact`, Cout = 32, fused upsample: the up chunks on low-resolution rows (conv3x3_ws.h, UR); same tiles, same LDS, same weights
+  if constexpr (P == 2 && UPF && !POOL && !HEAD && !C0F && NW == 1 && MW == 4 && !X8) {
+    if (uprows) k = conv3x3_ws_uprows_kernel;
+  }
   hipError_t st = allow_full_lds((const void*)k, cx.device);
   if (st != hipSuccess) return st;
   hipLaunchKernelGGL(k, grid, dim3(C::NT), lds, s, a);
@@ -273,7 +277,7 @@ hipError_t launch_ws_k(const LaunchCtx& cx, ConvArgs a, hipStream_t s) {
 }
 
 template <bool X8>
-hipError_t launch_ws_x(const LaunchCtx& cx, int P, const ConvArgs& a, bool pool, bool head, bool upf, bool c0f, hipStream_t s) {
+hipError_t launch_ws_x(const LaunchCtx& cx, int P, const ConvArgs& a, bool pool, bool head, bool upf, bool c0f, bool uprows, hipStream_t s) {
   if (P != 2 || (upf && (pool || head)) || (pool && head)) return hipErrorInvalidValue;
   if (a.Cout >= 64 && a.Cout % 64 == 0) {      // 8-row tiles, two 32-channel blocks per consumer wave, Cout / 64 channel tiles
     if (head || c0f) return hipErrorInvalidValue;
@@ -285,14 +289,14 @@ hipError_t launch_ws_x(const LaunchCtx& cx, int P, const ConvArgs& a, bool pool,
   if (a.in1 && !upf) return hipErrorInvalidValue;
   if (a.Cout != 32) return hipErrorInvalidValue;
   if (c0f) return (pool && !head && !upf && a.nchunks == 2) ? launch_ws_k<2, true, false, false, true, 1, 4, X8>(cx, a, s) : hipErrorInvalidValue;
-  if (upf) return launch_ws_k<2, false, false, true, false, 1, 4, X8>(cx, a, s);
+  if (upf) return launch_ws_k<2, false, false, true, false, 1, 4, X8>(cx, a, s, uprows && !X8);
   if (head) return launch_ws_k<2, false, true, false, false, 1, 4, X8>(cx, a, s);
   if (pool) return launch_ws_k<2, true, false, false, false, 1, 4, X8>(cx, a, s);
   return launch_ws_k<2, false, false, false, false, 1, 4, X8>(cx, a, s);
 }
 
-hipError_t launch_ws(const LaunchCtx& cx, int P, bool x8, const ConvArgs& a, bool pool, bool head, bool upf, bool c0f, hipStream_t s) {
-  return x8 ? launch_ws_x<true>(cx, P, a, pool, head, upf, c0f, s) : launch_ws_x<false>(cx, P, a, pool, head, upf, c0f, s);
+hipError_t launch_ws(const LaunchCtx& cx, int P, bool x8, const ConvArgs& a, bool pool, bool head, bool upf, bool c0f, bool uprows, hipStream_t s) {
+  return x8 ? launch_ws_x<true>(cx, P, a, pool, head, upf, c0f, uprows, s) : launch_ws_x<false>(cx, P, a, pool, head, upf, c0f, uprows, s);
 }
 
 template <int P, int KC, int NW, int MW, int WAVES>
@@ -1000,10 +1004,14 @@ static int forward_impl(unetpp_engine* e, const void* dev_input, int in_format, 
         char lbl[160];
         // labels end in the kernel's full template argument list, as rocprofv3 prints it (bench.py matches on it)
         auto tf = [](bool v) { return v ? "true" : "false"; };
-        if (L.ws) snprintf(lbl, sizeof lbl, "%s%s%s%s|conv3x3_ws_kernel<%d, %s, %s, %s, %s, %d, %d, %s, %s>", L.c0f ? "input+conv0_0.conv1+" : "", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "", P, tf(L.do_pool), tf(head), tf(L.upf), tf(L.c0f), L.cout == 32 ? 1 : 2, L.cout == 32 ? 4 : 2, tf(e->x8), tf(L.in2 >= 0 && !L.upf));
+        // `exact`, Cout = 32, fused upsample with at least two skip chunks (conv0_4.conv1): the kernel that multiplies the up chunks on
+        // low-resolution rows; debug_keep_intermediates keeps the plain fused-upsample kernel reachable for this layer
+        const bool uprows = L.ws && L.upf && P == 2 && !e->x8 && L.cout == 32 && !e->keep_all && t0.C >= 32 && t0.C % 16 == 0 && c1 >= 16 && c1 % 16 == 0;
+        if (uprows) snprintf(lbl, sizeof lbl, "%s+up|conv3x3_ws_uprows_kernel", L.name.c_str());
+        else if (L.ws) snprintf(lbl, sizeof lbl, "%s%s%s%s|conv3x3_ws_kernel<%d, %s, %s, %s, %s, %d, %d, %s, %s>", L.c0f ? "input+conv0_0.conv1+" : "", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "", P, tf(L.do_pool), tf(head), tf(L.upf), tf(L.c0f), L.cout == 32 ? 1 : 2, L.cout == 32 ? 4 : 2, tf(e->x8), tf(L.in2 >= 0 && !L.upf));
         else snprintf(lbl, sizeof lbl, "%s%s%s|conv3x3_bias_relu_kernel<%d, %d, %d, %d, %d, %s, %s, %s>", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "", P, L.KC, L.NW, mw, L.WAVES, tf(L.do_pool), tf(head), tf(L.upf));
         Lx.run(lbl, flops, bytes, [&] {
-          return L.ws ? launch_ws(LaunchCtx{e->cfg.device, e->num_cus, e->ksplit_max, e->ksplit_min_chunks, e->ksplit_gate}, P, e->x8, a, L.do_pool, head, L.upf, L.c0f, s)
+          return L.ws ? launch_ws(LaunchCtx{e->cfg.device, e->num_cus, e->ksplit_max, e->ksplit_min_chunks, e->ksplit_gate}, P, e->x8, a, L.do_pool, head, L.upf, L.c0f, uprows, s)
                     : launch_conv(LaunchCtx{e->cfg.device, e->num_cus}, P, L, mw, a, head, s);
         });
 #ifdef UNETPP_WS_DBG

@@ -356,7 +356,9 @@ class NestedUNet(PostProcessing):
         return out
 
     def debug_keep_intermediates(self, on: bool = True):
-        """Materialise x0_4 and run the head unfused (needed before debug_activation('x0_4'))."""
+        """Materialise x0_4 and run the head unfused (needed before debug_activation('x0_4')).  In 'exact' conv0_4.conv1 then
+        also runs in the plain fused-upsample kernel instead of conv3x3_ws_uprows_kernel: same layer, another
+        plan, logits within 5e-6."""
         self._keep_all = bool(on)                    # also applied to an engine that is (re)built later
         if self._handle is not None:
             _lib.load().unetpp_debug_keep_intermediates(self._handle, 1 if on else 0)

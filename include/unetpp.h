@@ -817,6 +817,91 @@ int unetpp_components_filter_mean(unetpp_engine* e, const int32_t* dev_labels, c
                                   int capacity, int64_t min_area, uint64_t thr_q, uint8_t out_value, uint8_t* dev_out,
                                   void* dev_workspace, void* stream);
 
+/* ---- the 6- and 7-class video loops: quality gate, class bits, class merge with its table, overlay --------------------------
+ * What infer_video.py, infer_video_v3_high_quality.py and infer_video_optimized.py do per frame around the network:
+ * FrameQualityGate.check (infer_video.py:73-118), the class clean-up with its priority merge (VideoInference.predict,
+ * infer_video.py:194-216; NestedUNetInference.predict, infer_video_v3_high_quality.py:105-173), per-class pixel counts and
+ * bounding boxes (infer_video.py:398, :421-445; validate_detection, infer_video_optimized.py:294-360) and overlay_mask
+ * (infer_video.py:220-243; infer_video_optimized.py:282-292).  unet_amd/multiclass.py is the NumPy form and holds the
+ * compositions; every result equals it exactly.  All entries queue their work on `stream` and allocate nothing (the resize
+ * tables of the threshold entry are built once per size pair, on first use, which synchronises).  No kernel is launched when an
+ * error is returned, and the outputs are untouched.
+ *
+ * Quality gate: dev_bgr uint8 [B,h,w,3], h, w >= 1, h * w <= 2^30.  dev_gray uint8 [B,h,w] = cvtColor(BGR2GRAY), the
+ *   arithmetic of the grey entry above.  Per frame, from five 64-bit integer sums (sum g, sum g^2, sum L, sum L^2, sum |g - g_prev|,
+ *   L the ksize-1 Laplacian [[0,1,0],[1,-4,1],[0,1,0]] with BORDER_REFLECT_101, accumulated with one integer atomic per sum
+ *   and workgroup: the same bits in any order of arrival), in float64:
+ *     dev_gray_std = sqrt((n S2 - S1^2) / n^2), dev_lap_var = (n SL2 - SL1^2) / n^2, dev_mad = S / n, n = h * w,
+ *   each quotient the correctly rounded quotient of the two exact integers.  The previous frame of frame i > 0 is frame i - 1 of the
+ *   batch (bad or not, as in the reference); that of frame 0 is dev_prev_gray uint8 [h,w], or NULL: mad = 0 for frame 0.
+ *   dev_reason uint8 [B], in the reference's order of tests: 1 gray_std < glitch_flat_th; 2 lap_var < blur_th and mad >
+ *   motion_th; 3 gray_std < flat_th; 4 ok; dev_is_bad uint8 [B] = reason != 4.  enable = 0 is the reference's first branch:
+ *   reason 0, not bad, lap_var = mad = 0, gray_std computed.  dev_workspace: unetpp_quality_gate_workspace_bytes bytes, 8-byte
+ *   aligned, cleared inside the call.  Two launches.  UNETPP_E_INVALID for NULL where not allowed, a bad shape, a NaN threshold,
+ *   a misaligned float64 output or workspace, dev_gray overlapping an input.
+ *
+ * Class bits: five probability planes float32 [src_h,src_w] per frame; plane k of frame b starts at dev_prob + b * frame_stride +
+ *   plane_offsets[k] (floats; plane_offsets is a HOST array of 5) and its pixels lie pixel_stride floats apart, so both
+ *   [B,C,h,w] (frame_stride C h w, pixel_stride 1, offsets k h w) and [B,h,w,C] (frame_stride h w C, pixel_stride C, offsets k)
+ *   are read in place.  dev_bits uint8 [B,dst_h,dst_w]; with p0..p4 the planes at that pixel, in float32 without contraction:
+ *     bit 0: p0 >= thresholds[0] and p0 > p1 * ratio      bit 1: p1 >= thresholds[1] and p1 > p0 * ratio
+ *     bits 2..4: pk >= thresholds[k]                      (thresholds: HOST array of 5; NaN sets no bit)
+ *   With (dst_h, dst_w) != (src_h, src_w) each plane is first sampled at the bit map's resolution as OpenCV's published
+ *   float32 INTER_LINEAR resize does: source coordinate (x + 0.5) scale - 0.5, clamped; S[sx] a0 + S[sx+1] a1 on two rows, then
+ *   r0 b0 + r1 b1, four taps per output pixel and no full-size float plane (cv2's own output is unpinned).  One launch.
+ *   h * w < 2^31 for both sizes, dst_h <= 65535.  UNETPP_E_INVALID for NULL, a bad shape, stride or offset, a NaN threshold.
+ *
+ * Class merge: dev_mask uint8 [B,h,w] (shape limits of the morphology entry).  One launch:
+ *   1. plane k (0 <= k < n_planes <= 6) = the pixels whose value v has bit k set in lut[v] (HOST array of 256; bits >= n_planes
+ *      must be clear).  For a label map plane k is "v in set k"; for a bit map from the entry above lut is the identity.
+ *   2. the steps that name plane k run on it in order, in LDS: UNETPP_MORPH_DILATE / UNETPP_MORPH_ERODE / UNETPP_MERGE_OPEN / UNETPP_MERGE_CLOSE with
+ *      elements[element], `iterations` times (open = erode^n then dilate^n, close = dilate^n then erode^n); semantics, elements and
+ *      the border rule are those of the morphology entry.  Opening or closing an empty plane gives an empty plane.
+ *   3. dev_out uint8 [B,h,w] (may be NULL with a table) = 0, then per plane in the order given, a later plane overwriting an
+ *      earlier one: out_values[k] (HOST array; 1..255), or for -1 the input pixel's own value.
+ *   4. dev_table (may be NULL) int32 [B,table_classes,5], 1 <= table_classes <= 256: per output value v < table_classes
+ *      {count, x0, y0, x1, y1}, x1 and y1 inclusive, all four -1 for count 0.  Accumulated per workgroup in LDS, then one atomic
+ *      add / min / max per non-empty value and workgroup; initialised inside the call.
+ *   Limits: those of the morphology entry applied to all planes together: at most 4 elements (63 x 63, row-convex), at most 8
+ *   steps, and the sum over every step of passes * (k - 1) at most 126 per axis (passes = iterations, twice that for open and
+ *   close).  Beyond them, and for n_planes > 6: UNETPP_E_UNSUPPORTED, never a wrong result.  UNETPP_E_INVALID for NULL where
+ *   not allowed, a bad shape, plane, op, element index, out value or lut entry, and dev_out overlapping dev_mask.
+ *   unetpp_merge_classes_layout reports the tiling (no engine, no device needed) as the morphology layout entry does.
+ *
+ * Overlay: dev_frames, dev_out uint8 [B,h,w,3]; dev_mask uint8 [B,h,w]; colors HOST uint8 [256,3] in the frames' channel order,
+ *   has_color HOST uint8 [256].  float32 without contraction:
+ *     UNETPP_OVERLAY_REGION    where mask > 0: uint8(w_frame * f + w_color * c), truncated, c the value's colour (0 without
+ *                              one); elsewhere the frame
+ *     UNETPP_OVERLAY_WEIGHTED  cv2.addWeighted(frame, w_frame, painted, w_color, 0) per OpenCV's published scalar loop:
+ *                              saturate_cast<uchar>(f * w_frame + p * w_color), round to nearest even; painted = the colour
+ *                              where the value is non-zero and has one, else the frame (cv2's own output is unpinned)
+ *   16-byte loads and stores when the three pointers are 16-byte aligned, bytes otherwise and for the tail.  0 <= weights <= 1.
+ *   UNETPP_E_INVALID for NULL, a bad shape, mode or weight, dev_out overlapping an input.  One launch. */
+enum { UNETPP_MERGE_OPEN = 6, UNETPP_MERGE_CLOSE = 7 };
+enum { UNETPP_OVERLAY_REGION = 0, UNETPP_OVERLAY_WEIGHTED = 1 };
+
+typedef struct unetpp_merge_step {
+  int plane, op, element, iterations;
+} unetpp_merge_step;
+
+size_t unetpp_quality_gate_workspace_bytes(int batch);
+int unetpp_quality_gate_u8(unetpp_engine* e, const uint8_t* dev_bgr, const uint8_t* dev_prev_gray, int batch, int h, int w,
+                           int enable, double blur_th, double flat_th, double motion_th, double glitch_flat_th,
+                           uint8_t* dev_gray, uint8_t* dev_is_bad, uint8_t* dev_reason, double* dev_lap_var,
+                           double* dev_gray_std, double* dev_mad, void* dev_workspace, void* stream);
+int unetpp_threshold_classes_f32(unetpp_engine* e, const float* dev_prob, int64_t frame_stride, int pixel_stride,
+                                 const int64_t* plane_offsets, int batch, int src_h, int src_w, const float* thresholds,
+                                 float ratio, int dst_h, int dst_w, uint8_t* dev_bits, void* stream);
+int unetpp_merge_classes(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, const uint8_t* lut, int n_planes,
+                         const int32_t* out_values, const unetpp_morph_element* elements, int n_elements,
+                         const unetpp_merge_step* steps, int n_steps, uint8_t* dev_out, int32_t* dev_table,
+                         int table_classes, void* stream);
+int unetpp_merge_classes_layout(int batch, int h, int w, int n_planes, const unetpp_morph_element* elements, int n_elements,
+                                const unetpp_merge_step* steps, int n_steps, int* band_rows, int* tile_cols);
+int unetpp_overlay_u8(unetpp_engine* e, const uint8_t* dev_frames, const uint8_t* dev_mask, int batch, int h, int w,
+                      const uint8_t* colors, const uint8_t* has_color, float w_frame, float w_color, int mode,
+                      uint8_t* dev_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

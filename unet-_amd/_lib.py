@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunetpp_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["unetpp_abi.hip", "unetpp_postproc.hip"]      # the engine; the post-processing entry points
-HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "frame_kernels.h", "components.h", "distance.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "nlmeans.h", "evaluation.h", "probmap.h", "geometry.h", "tiling.h", os.path.join("..", "..", "include", "unetpp.h")]
+HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "frame_kernels.h", "components.h", "distance.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "nlmeans.h", "evaluation.h", "probmap.h", "multiclass.h", "geometry.h", "tiling.h", os.path.join("..", "..", "include", "unetpp.h")]
 
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
 PREC_EXACT, PREC_FAST, PREC_EXACT8 = 0, 1, 2
@@ -54,6 +54,11 @@ class MorphStep(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("op", "dst", "a", "b", "element", "iterations")]
 
 
+class MergeStep(ctypes.Structure):
+    """unetpp_merge_step: `op` with elements[element] on plane `plane`, `iterations` times."""
+    _fields_ = [(n, ctypes.c_int) for n in ("plane", "op", "element", "iterations")]
+
+
 class BilateralTables(ctypes.Structure):
     """unetpp_bilateral_tables: the weights and taps of the bilateral filter, all in host memory."""
     _fields_ = [("radius", ctypes.c_int32), ("n_taps", ctypes.c_int32), ("color_w", ctypes.POINTER(ctypes.c_float)),
@@ -62,6 +67,8 @@ class BilateralTables(ctypes.Structure):
 
 ENHANCE_ALWAYS, ENHANCE_IF_GREY = 0, 1
 MORPH_OPS = {"dilate": 0, "erode": 1, "and": 2, "andnot": 3, "or": 4, "copy": 5}
+MERGE_OPS = {"dilate": 0, "erode": 1, "open": 6, "close": 7}                 # unetpp_merge_step.op
+OVERLAY_MODES = {"region": 0, "weighted": 1}
 DIST_METRICS = {"l1": 1, "l2": 2, "c": 3}          # UNETPP_DIST_*: cv2.DIST_L1, DIST_L2, DIST_C
 RULES = {"argmax": 0, "thresholded_argmax": 1, "strict_bg_check": 2, "exclusive": 3}
 
@@ -150,6 +157,15 @@ ABI = {
     "unetpp_roi_limit_workspace_bytes": (cs, [ci]),
     "unetpp_roi_limit_u8": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
     "unetpp_row_width_median": (ci, [vp, vp, ci, ci, vp, vp]),
+    "unetpp_quality_gate_workspace_bytes": (cs, [ci]),
+    "unetpp_quality_gate_u8": (ci, [vp, vp, vp, ci, ci, ci, ci, cd, cd, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "unetpp_threshold_classes_f32": (ci, [vp, vp, ctypes.c_int64, ci, ctypes.POINTER(ctypes.c_int64), ci, ci, ci, f32p, ctypes.c_float, ci, ci,
+                                          vp, vp]),
+    "unetpp_merge_classes": (ci, [vp, vp, ci, ci, ci, u8p, ci, i32p, ctypes.POINTER(MorphElement), ci, ctypes.POINTER(MergeStep), ci, vp, vp,
+                                  ci, vp]),
+    "unetpp_merge_classes_layout": (ci, [ci, ci, ci, ci, ctypes.POINTER(MorphElement), ci, ctypes.POINTER(MergeStep), ci,
+                                         ctypes.POINTER(ci), ctypes.POINTER(ci)]),
+    "unetpp_overlay_u8": (ci, [vp, vp, vp, ci, ci, ci, u8p, u8p, ctypes.c_float, ctypes.c_float, ci, vp, vp]),
 }
 ABI_SYMBOLS = list(ABI)
 

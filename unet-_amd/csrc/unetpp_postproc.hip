@@ -23,6 +23,7 @@
 #include "frame_kernels.h"
 #include "geometry.h"
 #include "morphology.h"
+#include "multiclass.h"
 #include "nlmeans.h"
 #include "probmap.h"
 #include "tiling.h"
@@ -897,17 +898,8 @@ struct MorphPlan {
   size_t lds_bytes = 0;
 };
 
-// Checks a program and lays its tiles out.  Everything the kernel indexes with is validated here.
-static int morph_plan(unetpp_engine* e, int batch, int h, int w, const unetpp_morph_element* elements, int n_elements,
-                      const unetpp_morph_step* steps, int n_steps, int result_plane, MorphPlan* plan) {
-  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
-  if (n_elements < 0 || n_elements > MORPH_MAX_ELEMENTS || (n_elements > 0 && !elements))
-    return fail(e, UNETPP_E_INVALID, "n_elements %d not in [0,%d]", n_elements, MORPH_MAX_ELEMENTS);
-  if (n_steps < 0 || n_steps > MORPH_MAX_STEPS || (n_steps > 0 && !steps))
-    return fail(e, UNETPP_E_INVALID, "n_steps %d not in [0,%d]", n_steps, MORPH_MAX_STEPS);
-  MorphArgs& A = plan->args;
-  std::memset(&A, 0, sizeof A);
-  int ax[MORPH_MAX_ELEMENTS], ay[MORPH_MAX_ELEMENTS];
+// Checks the elements and turns them into the kernels' sorted row runs; ax / ay receive the resolved anchors.
+static int morph_elements(unetpp_engine* e, const unetpp_morph_element* elements, int n_elements, MorphElem* out, int* ax, int* ay) {
   for (int k = 0; k < n_elements; ++k) {
     const unetpp_morph_element& el = elements[k];
     if (el.kw < 1 || el.kh < 1 || !el.host_data) return fail(e, UNETPP_E_INVALID, "element %d: bad size %dx%d or NULL data", k, el.kw, el.kh);
@@ -916,7 +908,7 @@ static int morph_plan(unetpp_engine* e, int batch, int h, int w, const unetpp_mo
     ax[k] = el.ax < 0 ? el.kw / 2 : el.ax;
     ay[k] = el.ay < 0 ? el.kh / 2 : el.ay;
     if (ax[k] >= el.kw || ay[k] >= el.kh) return fail(e, UNETPP_E_INVALID, "element %d: anchor (%d,%d) outside %dx%d", k, el.ax, el.ay, el.kw, el.kh);
-    MorphElem& E = A.elem[k];
+    MorphElem& E = out[k];
     for (int i = 0; i < el.kh; ++i) {
       const uint8_t* r = el.host_data + (size_t)i * el.kw;
       int first = -1, last = -1, count = 0;
@@ -932,6 +924,53 @@ static int morph_plan(unetpp_engine* e, int batch, int h, int w, const unetpp_mo
       return std::make_tuple(p.lo, p.hi, p.dy) < std::make_tuple(q.lo, q.hi, q.dy);
     });
   }
+  return UNETPP_OK;
+}
+
+// Lays the tiles of a bit-plane program out for planes of at most plane_words 64-bit words: bands of full-width rows while a
+// row and its halo fit, else tiles with a halo on all four sides.  *band_out stays 0 when nothing fits.
+static void morph_tiles(int plane_words, int batch, int h, int wpr, int halo, int left, int right, int* band_out, int* cw, int* hl, int* tw) {
+  *band_out = 0;
+  int band_max;
+  if (wpr * (halo + 1) <= plane_words) {            // bands of full-width rows: no horizontal halo
+    *cw = wpr; *hl = 0; *tw = wpr;
+    band_max = plane_words / wpr - halo;
+    // enough workgroups to fill the device before the bands grow: at most as much halo as core, never below 16 rows
+    int band = std::min(std::max(halo, 16), band_max);
+    while ((long long)batch * ((h + band - 1) / band) > 2048 && band * 2 <= band_max) band *= 2;
+    band = std::min(band, h);
+    // one thread per word and pass: grow the band until the window's words fill whole passes of the workgroup
+    int unit = MORPH_THREADS;
+    for (int a = MORPH_THREADS, b = wpr; b;) { const int r = a % b; a = b; b = r; unit = MORPH_THREADS / a; }
+    const int rows_up = (band + halo + unit - 1) / unit * unit;
+    if (rows_up - halo <= std::min(band_max, h)) band = rows_up - halo;
+    *band_out = band;
+  } else {                                                  // tiles with a halo on all four sides: the best core share
+    const int wl = (left + 63) / 64, wr = (right + 63) / 64;
+    double best = -1.0;
+    *cw = 0;
+    for (int c = 1; c <= std::min(wpr, 64); ++c) {
+      const int bm = std::min(plane_words / (c + wl + wr) - halo, h);
+      if (bm < 1) break;
+      const double share = (double)c * bm / ((double)(c + wl + wr) * (bm + halo));
+      if (share > best) { best = share; *cw = c; *band_out = bm; }
+    }
+    *hl = wl; *tw = *cw + wl + wr;
+  }
+}
+
+// Checks a program and lays its tiles out.  Everything the kernel indexes with is validated here.
+static int morph_plan(unetpp_engine* e, int batch, int h, int w, const unetpp_morph_element* elements, int n_elements,
+                      const unetpp_morph_step* steps, int n_steps, int result_plane, MorphPlan* plan) {
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if (n_elements < 0 || n_elements > MORPH_MAX_ELEMENTS || (n_elements > 0 && !elements))
+    return fail(e, UNETPP_E_INVALID, "n_elements %d not in [0,%d]", n_elements, MORPH_MAX_ELEMENTS);
+  if (n_steps < 0 || n_steps > MORPH_MAX_STEPS || (n_steps > 0 && !steps))
+    return fail(e, UNETPP_E_INVALID, "n_steps %d not in [0,%d]", n_steps, MORPH_MAX_STEPS);
+  MorphArgs& A = plan->args;
+  std::memset(&A, 0, sizeof A);
+  int ax[MORPH_MAX_ELEMENTS], ay[MORPH_MAX_ELEMENTS];
+  if (const int rc = morph_elements(e, elements, n_elements, A.elem, ax, ay)) return rc;
   bool written[MORPH_USER_PLANES] = {true, true, false, false};     // plane 1 is all zero without a second mask
   auto plane_ok = [](int p) { return p >= 0 && p < MORPH_USER_PLANES; };
   int up = 0, down = 0, left = 0, right = 0;
@@ -965,31 +1004,7 @@ static int morph_plan(unetpp_engine* e, int batch, int h, int w, const unetpp_mo
   A.n_steps = n_steps; A.result = result_plane;
   A.H = h; A.W = w; A.wpr = (w + 63) / 64;
   const int halo = up + down;
-  int band_max;
-  if (A.wpr * (halo + 1) <= MORPH_PLANE_WORDS) {            // bands of full-width rows: no horizontal halo
-    A.cw = A.wpr; A.hl = 0; A.tw = A.wpr;
-    band_max = MORPH_PLANE_WORDS / A.wpr - halo;
-    // enough workgroups to fill the device before the bands grow: at most as much halo as core, never below 16 rows
-    int band = std::min(std::max(halo, 16), band_max);
-    while ((long long)batch * ((h + band - 1) / band) > 2048 && band * 2 <= band_max) band *= 2;
-    band = std::min(band, h);
-    // one thread per word and pass: grow the band until the window's words fill whole passes of the workgroup
-    int unit = MORPH_THREADS;
-    for (int a = MORPH_THREADS, b = A.wpr; b;) { const int r = a % b; a = b; b = r; unit = MORPH_THREADS / a; }
-    const int rows_up = (band + halo + unit - 1) / unit * unit;
-    if (rows_up - halo <= std::min(band_max, h)) band = rows_up - halo;
-    A.band = band;
-  } else {                                                  // tiles with a halo on all four sides: the best core share
-    const int hl = (left + 63) / 64, hr = (right + 63) / 64;
-    double best = -1.0;
-    for (int cw = 1; cw <= std::min(A.wpr, 64); ++cw) {
-      const int bm = std::min(MORPH_PLANE_WORDS / (cw + hl + hr) - halo, h);
-      if (bm < 1) break;
-      const double share = (double)cw * bm / ((double)(cw + hl + hr) * (bm + halo));
-      if (share > best) { best = share; A.cw = cw; A.band = bm; }
-    }
-    A.hl = hl; A.tw = A.cw + hl + hr;
-  }
+  morph_tiles(MORPH_PLANE_WORDS, batch, h, A.wpr, halo, left, right, &A.band, &A.cw, &A.hl, &A.tw);
   A.up = up; A.rows = A.band + halo;
   plan->grid = tile_grid(A.wpr, h, A.cw, A.band, batch);
   plan->lds_bytes = (size_t)MORPH_PLANES * A.rows * A.tw * sizeof(unsigned long long);
@@ -1191,6 +1206,191 @@ int unetpp_tile_blend_f32(unetpp_engine* e, const float* dev_maps, int batch, in
     TILE_BLEND_CASE(5); TILE_BLEND_CASE(6); TILE_BLEND_CASE(7); TILE_BLEND_CASE(8);
   }
 #undef TILE_BLEND_CASE
+  return launched(e);
+}
+
+// ---- the 6- and 7-class video loops: quality gate, class bits, class merge with its table, overlay (multiclass.h) -----------
+size_t unetpp_quality_gate_workspace_bytes(int batch) {
+  return batch >= 1 && batch <= MAX_DIM ? align_up((size_t)batch * QG_SUMS * sizeof(uint64_t), 256) : 0;
+}
+
+int unetpp_quality_gate_u8(unetpp_engine* e, const uint8_t* dev_bgr, const uint8_t* dev_prev_gray, int batch, int h, int w, int enable,
+                           double blur_th, double flat_th, double motion_th, double glitch_flat_th, uint8_t* dev_gray, uint8_t* dev_is_bad,
+                           uint8_t* dev_reason, double* dev_lap_var, double* dev_gray_std, double* dev_mad, void* dev_workspace, void* stream) {
+  REQUIRE_ARGS(e, dev_bgr && dev_gray && dev_is_bad && dev_reason && dev_lap_var && dev_gray_std && dev_mad && dev_workspace);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if (blur_th != blur_th || flat_th != flat_th || motion_th != motion_th || glitch_flat_th != glitch_flat_th)
+    return fail(e, UNETPP_E_INVALID, "a threshold is NaN");
+  if ((uintptr_t)dev_workspace % 8 || (uintptr_t)dev_lap_var % 8 || (uintptr_t)dev_gray_std % 8 || (uintptr_t)dev_mad % 8)
+    return fail(e, UNETPP_E_INVALID, "dev_workspace and the float64 outputs must be 8-byte aligned");
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_bgr, 3 * n, dev_gray, n) || (dev_prev_gray && overlaps(dev_prev_gray, (size_t)h * w, dev_gray, n)))
+    return fail(e, UNETPP_E_INVALID, "dev_gray aliases an input: workgroups read pixels that others write");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(e, hipMemsetAsync(dev_workspace, 0, (size_t)batch * QG_SUMS * sizeof(uint64_t), s));
+  hipLaunchKernelGGL(quality_sums_kernel, tile_grid(w, h, QG_TW, QG_TH, batch), dim3(MC_THREADS), 0, s, dev_bgr, dev_prev_gray, h, w,
+                     (int)(w % 8 == 0 && (uintptr_t)dev_gray % 8 == 0), dev_gray, (unsigned long long*)dev_workspace);
+  hipLaunchKernelGGL(quality_finish_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, s, (const unsigned long long*)dev_workspace, batch,
+                     (unsigned long long)h * (unsigned long long)w, enable ? 1 : 0, blur_th, flat_th, motion_th, glitch_flat_th, dev_is_bad,
+                     dev_reason, dev_lap_var, dev_gray_std, dev_mad);
+  return launched(e);
+}
+
+int unetpp_threshold_classes_f32(unetpp_engine* e, const float* dev_prob, int64_t frame_stride, int pixel_stride, const int64_t* plane_offsets,
+                                 int batch, int src_h, int src_w, const float* thresholds, float ratio, int dst_h, int dst_w,
+                                 uint8_t* dev_bits, void* stream) {
+  REQUIRE_ARGS(e, dev_prob && plane_offsets && thresholds && dev_bits);
+  if (int rc = eval_shape_check(e, batch, src_h, src_w, 1ull << 31)) return rc;
+  if (int rc = eval_shape_check(e, batch, dst_h, dst_w, 1ull << 31)) return rc;
+  if (dst_h > MAX_DIM) return fail(e, UNETPP_E_INVALID, "dst_h %d: at most %d rows (a grid dimension)", dst_h, MAX_DIM);
+  if ((uintptr_t)dev_prob % 4) return fail(e, UNETPP_E_INVALID, "dev_prob must be 4-byte aligned");
+  const int64_t hw = (int64_t)src_h * src_w;
+  if (pixel_stride < 1 || pixel_stride > 256 || frame_stride < hw * pixel_stride || frame_stride >= (1ll << 40))
+    return fail(e, UNETPP_E_INVALID, "pixel_stride %d, frame_stride %lld: 1 <= pixel_stride <= 256, frame_stride >= src_h * src_w * pixel_stride",
+                pixel_stride, (long long)frame_stride);
+  ThresholdArgs A{};
+  for (int k = 0; k < TC_PLANES; ++k) {
+    // the last float of plane k lies inside the frame's frame_stride floats
+    if (plane_offsets[k] < 0 || plane_offsets[k] + (hw - 1) * pixel_stride >= frame_stride)
+      return fail(e, UNETPP_E_INVALID, "plane %d at offset %lld does not lie inside a frame of %lld floats", k, (long long)plane_offsets[k],
+                  (long long)frame_stride);
+    if (thresholds[k] != thresholds[k]) return fail(e, UNETPP_E_INVALID, "threshold %d is NaN", k);
+    A.chan_off[k] = plane_offsets[k];
+    A.thr[k] = thresholds[k];
+  }
+  if (ratio != ratio) return fail(e, UNETPP_E_INVALID, "ratio is NaN");
+  A.frame_stride = frame_stride; A.pixel_stride = pixel_stride; A.ratio = ratio;
+  A.sh = src_h; A.sw = src_w; A.H = dst_h; A.W = dst_w; A.resize = src_h != dst_h || src_w != dst_w;
+  ENTER_DEVICE(e);
+  void *xt = nullptr, *yt = nullptr;
+  if (A.resize) {
+    if (const int rc = resize_table(e, 2, src_w, dst_w, &xt)) return rc;
+    if (const int rc = resize_table(e, 2, src_h, dst_h, &yt)) return rc;
+  }
+  const dim3 grid((unsigned)((dst_w + TC_PX * MC_THREADS - 1) / (TC_PX * MC_THREADS)), (unsigned)dst_h, (unsigned)batch);
+  hipLaunchKernelGGL(threshold_classes_kernel, grid, dim3(MC_THREADS), 0, (hipStream_t)stream, dev_prob, A, (const int4*)xt, (const int4*)yt,
+                     (int)(dst_w % 4 == 0 && (uintptr_t)dev_bits % 4 == 0), dev_bits);
+  return launched(e);
+}
+
+struct MergePlan {
+  MergeArgs args;
+  dim3 grid;
+  size_t lds_bytes = 0;
+};
+
+// Checks the planes and their programs and lays the tiles out.  Everything the kernel indexes with is validated here.
+static int merge_plan(unetpp_engine* e, int batch, int h, int w, int n_planes, const unetpp_morph_element* elements, int n_elements,
+                      const unetpp_merge_step* steps, int n_steps, MergePlan* plan) {
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_INVALID, "bad shape %dx%dx%d", batch, h, w);
+  if (n_planes < 1) return fail(e, UNETPP_E_INVALID, "n_planes %d: at least 1", n_planes);
+  if (n_planes > MC_MAX_PLANES) return fail(e, UNETPP_E_UNSUPPORTED, "n_planes %d: at most %d", n_planes, MC_MAX_PLANES);
+  if (n_elements < 0 || (n_elements > 0 && !elements)) return fail(e, UNETPP_E_INVALID, "n_elements %d with NULL elements", n_elements);
+  if (n_steps < 0 || (n_steps > 0 && !steps)) return fail(e, UNETPP_E_INVALID, "n_steps %d with NULL steps", n_steps);
+  if (n_elements > MORPH_MAX_ELEMENTS) return fail(e, UNETPP_E_UNSUPPORTED, "n_elements %d: at most %d over all planes", n_elements, MORPH_MAX_ELEMENTS);
+  if (n_steps > MORPH_MAX_STEPS) return fail(e, UNETPP_E_UNSUPPORTED, "n_steps %d: at most %d over all planes", n_steps, MORPH_MAX_STEPS);
+  MergeArgs& A = plan->args;
+  std::memset(&A, 0, sizeof A);
+  int ax[MORPH_MAX_ELEMENTS], ay[MORPH_MAX_ELEMENTS];
+  if (const int rc = morph_elements(e, elements, n_elements, A.elem, ax, ay)) return rc;
+  int up[MC_MAX_PLANES] = {}, down[MC_MAX_PLANES] = {}, left[MC_MAX_PLANES] = {}, right[MC_MAX_PLANES] = {};
+  int reach_v = 0, reach_h = 0;
+  for (int s = 0; s < n_steps; ++s) {
+    const unetpp_merge_step& st = steps[s];
+    if (st.plane < 0 || st.plane >= n_planes) return fail(e, UNETPP_E_INVALID, "step %d: plane %d not in [0,%d)", s, st.plane, n_planes);
+    if (st.op != UNETPP_MORPH_DILATE && st.op != UNETPP_MORPH_ERODE && st.op != UNETPP_MERGE_OPEN && st.op != UNETPP_MERGE_CLOSE)
+      return fail(e, UNETPP_E_INVALID, "step %d: op %d is not dilate, erode, open or close", s, st.op);
+    if (st.element < 0 || st.element >= n_elements) return fail(e, UNETPP_E_INVALID, "step %d: element index %d not in [0,%d)", s, st.element, n_elements);
+    if (st.iterations < 1) return fail(e, UNETPP_E_INVALID, "step %d: iterations must be at least 1, got %d", s, st.iterations);
+    if (st.iterations > MORPH_MAX_REACH) return fail(e, UNETPP_E_UNSUPPORTED, "step %d: iterations %d beyond %d", s, st.iterations, MORPH_MAX_REACH);
+    const unetpp_morph_element& el = elements[st.element];
+    const int passes = (st.op == UNETPP_MERGE_OPEN || st.op == UNETPP_MERGE_CLOSE ? 2 : 1) * st.iterations;
+    up[st.plane] += passes * ay[st.element]; down[st.plane] += passes * (el.kh - 1 - ay[st.element]);
+    left[st.plane] += passes * ax[st.element]; right[st.plane] += passes * (el.kw - 1 - ax[st.element]);
+    reach_v += passes * (el.kh - 1); reach_h += passes * (el.kw - 1);
+    if (reach_v > MORPH_MAX_REACH || reach_h > MORPH_MAX_REACH)
+      return fail(e, UNETPP_E_UNSUPPORTED, "the programs' reach (sum of iterations * (k - 1) over the dilates and erodes of all planes) exceeds %d "
+                  "pixels (vertical %d, horizontal %d)", MORPH_MAX_REACH, reach_v, reach_h);
+    A.step[s] = MergeStep{st.plane, st.op, st.element, st.iterations};
+  }
+  A.n_steps = n_steps; A.n_planes = n_planes;
+  A.H = h; A.W = w; A.wpr = (w + 63) / 64;
+  // the window must hold the widest halo of any plane; a plane with a smaller one recomputes a little more than it needs
+  const int hu = *std::max_element(up, up + n_planes), hd = *std::max_element(down, down + n_planes);
+  const int hl = *std::max_element(left, left + n_planes), hr = *std::max_element(right, right + n_planes);
+  const int halo = hu + hd, plane_words = std::min(MORPH_PLANE_WORDS, MC_LDS_WORDS / (n_planes + 2));
+  morph_tiles(plane_words, batch, h, A.wpr, halo, hl, hr, &A.band, &A.cw, &A.hl, &A.tw);
+  A.up = hu; A.rows = A.band + halo;
+  if (A.band < 1 || A.cw < 1 || A.rows * A.tw > plane_words) return fail(e, UNETPP_E_STATE, "internal: merge tile layout");
+  plan->grid = tile_grid(A.wpr, h, A.cw, A.band, batch);
+  plan->lds_bytes = (size_t)(n_planes + 2) * A.rows * A.tw * sizeof(unsigned long long);
+  return UNETPP_OK;
+}
+
+int unetpp_merge_classes_layout(int batch, int h, int w, int n_planes, const unetpp_morph_element* elements, int n_elements,
+                                const unetpp_merge_step* steps, int n_steps, int* band_rows, int* tile_cols) {
+  if (!band_rows || !tile_cols) return fail(nullptr, UNETPP_E_INVALID, "null argument");
+  MergePlan plan;
+  if (const int rc = merge_plan(nullptr, batch, h, w, n_planes, elements, n_elements, steps, n_steps, &plan)) return rc;
+  *band_rows = plan.args.band;
+  *tile_cols = plan.args.cw * 64;
+  return UNETPP_OK;
+}
+
+int unetpp_merge_classes(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, const uint8_t* lut, int n_planes,
+                         const int32_t* out_values, const unetpp_morph_element* elements, int n_elements, const unetpp_merge_step* steps,
+                         int n_steps, uint8_t* dev_out, int32_t* dev_table, int table_classes, void* stream) {
+  REQUIRE_ARGS(e, dev_mask && lut && out_values && (dev_out || dev_table));
+  MergePlan plan;
+  if (const int rc = merge_plan(e, batch, h, w, n_planes, elements, n_elements, steps, n_steps, &plan)) return rc;
+  MergeArgs& A = plan.args;
+  for (int k = 0; k < n_planes; ++k) {
+    if (out_values[k] != -1 && (out_values[k] < 1 || out_values[k] > 255))
+      return fail(e, UNETPP_E_INVALID, "out_values[%d] = %d: 1..255, or -1 for the input pixel's own value", k, out_values[k]);
+    A.out_value[k] = out_values[k];
+  }
+  for (int v = 0; v < 256; ++v) {
+    if (lut[v] >> n_planes) return fail(e, UNETPP_E_INVALID, "lut[%d] = %d names a plane beyond the %d given", v, lut[v], n_planes);
+    A.lut[v] = lut[v];
+  }
+  if (dev_table && (table_classes < 1 || table_classes > 256)) return fail(e, UNETPP_E_INVALID, "table_classes %d: 1..256", table_classes);
+  if ((uintptr_t)dev_table % 4) return fail(e, UNETPP_E_INVALID, "dev_table must be 4-byte aligned");
+  const size_t n = (size_t)batch * h * w, tb = dev_table ? (size_t)batch * table_classes * MC_TABLE_COLS * sizeof(int32_t) : 0;
+  if (dev_out && overlaps(dev_mask, n, dev_out, n))
+    return fail(e, UNETPP_E_INVALID, "dev_out aliases dev_mask: every workgroup reads the halo rows its neighbours write");
+  if (dev_table && (overlaps(dev_mask, n, dev_table, tb) || (dev_out && overlaps(dev_out, n, dev_table, tb))))
+    return fail(e, UNETPP_E_INVALID, "dev_table overlaps a mask");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  A.vec_in = vec16(w, dev_mask); A.vec_out = dev_out ? vec16(w, dev_out) : 0;
+  A.table_classes = dev_table ? table_classes : 0;
+  if (dev_table) {
+    const int rows = batch * table_classes;
+    hipLaunchKernelGGL(merge_table_init_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, (int*)dev_table, rows);
+  }
+  hipLaunchKernelGGL(merge_classes_kernel, plan.grid, dim3(MORPH_THREADS), plan.lds_bytes, s, dev_mask, dev_out, (int*)dev_table, A);
+  return launched(e);
+}
+
+int unetpp_overlay_u8(unetpp_engine* e, const uint8_t* dev_frames, const uint8_t* dev_mask, int batch, int h, int w, const uint8_t* colors,
+                      const uint8_t* has_color, float w_frame, float w_color, int mode, uint8_t* dev_out, void* stream) {
+  REQUIRE_ARGS(e, dev_frames && dev_mask && colors && has_color && dev_out);
+  if (int rc = eval_shape_check(e, batch, h, w, 1ull << 31)) return rc;
+  if (mode != UNETPP_OVERLAY_REGION && mode != UNETPP_OVERLAY_WEIGHTED) return fail(e, UNETPP_E_INVALID, "mode %d: 0 (region) or 1 (weighted)", mode);
+  if (!(w_frame >= 0.f && w_frame <= 1.f && w_color >= 0.f && w_color <= 1.f))
+    return fail(e, UNETPP_E_INVALID, "weights %g, %g: both in [0,1]", (double)w_frame, (double)w_color);
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_out, 3 * n, dev_frames, 3 * n) || overlaps(dev_out, 3 * n, dev_mask, n))
+    return fail(e, UNETPP_E_INVALID, "dev_out aliases an input");
+  const size_t items = (n + OV_PX - 1) / OV_PX;
+  if ((items + MC_THREADS - 1) / MC_THREADS > 0x7fffffffull) return fail(e, UNETPP_E_UNSUPPORTED, "batch %d of %dx%d: too many pixels for one launch", batch, h, w);
+  OverlayColors C;
+  for (int v = 0; v < 256; ++v)
+    C.c[v] = (uint32_t)colors[3 * v] | (uint32_t)colors[3 * v + 1] << 8 | (uint32_t)colors[3 * v + 2] << 16 | (has_color[v] ? 1u << 24 : 0u);
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(overlay_kernel, dim3((unsigned)((items + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, (hipStream_t)stream, dev_frames,
+                     dev_mask, n, C, w_frame, w_color, mode, vec16(16, dev_frames, dev_mask, dev_out), dev_out);
   return launched(e);
 }
 

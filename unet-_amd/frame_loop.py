@@ -5,6 +5,8 @@ enhancement and the ROI crop in front of the same steps.  `segment_frames` start
 cv2.resize steps either side on the device (those two restate OpenCV's published
 algorithm and are parity-unpinned, see oracle/unetpp_oracle.py).  `measure_frames` is the tail of the production loop
 (infer_video_production.py:198-226): the diameter metrics and the defect analysis of every frame of a batch.
+`process_frames_multiclass` is the frame loop of the 6- and 7-class scripts (infer_video.py:359-464,
+infer_video_v3_high_quality.py, infer_video_optimized.py): quality gate, model, class clean-up, class table, overlay.
 """
 from __future__ import annotations
 
@@ -179,3 +181,64 @@ def process_frames_optimized(model, frames_bgr_u8, *, patch_size=384, stride=192
                                     channel_order=channel_order)
     _, pred_final = probmap.postprocess_probmap(model, output, channel=int(gate_class), **post)
     return pred_final, output
+
+
+def process_frames_multiclass(model, frames_bgr_u8, prev_gray=None, *, input_size, variant="video", colors, alpha=0.6, overlay_mode="region",
+                              num_classes=None, gate=None, thresholds=None, min_area_px=50, validate=None, device=None):
+    """The per-frame body of the 6- and 7-class video loops for B raw BGR frames of one size at once, the frames never leaving
+    the device (multiclass.py holds every step and its NumPy form):
+      1. FrameQualityGate.check on every frame (multiclass.quality_gate; `gate`: its thresholds and `enable`), prev_gray = the
+         grey frame before the batch or None; ONE read-back of the B flags
+      2. resize_frames of the good frames to input_size (an int or (h, w))
+      3. variant="video" (infer_video.py): segment(); variant="v3" (infer_video_v3_high_quality.py): predict_proba()
+      4. video: resize_masks to the frame size, then clean_classes_video; v3: predict_v3 (`thresholds`: its cable_thr, tape_thr,
+         defect_thr, ratio, channels)
+      5. the class table, written by the same launch as the cleaned mask
+      6. the overlay (`colors`, alpha, overlay_mode, classes >= the model's num_classes dropped from the colours)
+      7. ONE read-back of the tables (with the gate's three statistics)
+    Returns (records, overlays uint8 [B,H,W,3], gray uint8 [H,W] of the last frame: the next call's prev_gray), both tensors on
+    the device.  records[i] is None for a gated frame (its overlay is the frame), else {"reason", "lap_var", "gray_std", "mad",
+    "table" int32 [C,5] (count, x0, y0, x1, y1 per class), "events" (multiclass.defect_events with min_area_px)} and, with
+    `validate` (the keyword arguments of multiclass.validate_detection), "valid" and "defects".  Contours, rectangles, text,
+    cool-down counters and the window aggregator stay with the caller."""
+    import torch
+    from . import multiclass as mc
+    if variant not in ("video", "v3"):
+        raise ValueError(f"variant must be 'video' or 'v3', got {variant!r}")
+    x = frames_bgr_u8
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not x.is_cuda:
+        x = x.to(device if device is not None else f"cuda:{model._device_index or 0}", non_blocking=True)
+    is_bad, reason, lap_var, gray_std, mad, gray = mc.quality_gate(model, x, prev_gray, **(gate or {}))
+    flags = torch.stack((is_bad.to(torch.uint8), reason)).cpu().numpy()                      # read-back 1: 2 B bytes
+    b, fh, fw = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+    good = [i for i in range(b) if not flags[0, i]]
+    records = [None] * b
+    if not good:
+        return records, x.clone(), gray[-1]
+    xg = x if len(good) == b else x.index_select(0, torch.tensor(good, dtype=torch.int64, device=x.device))
+    th, tw = (int(input_size), int(input_size)) if isinstance(input_size, (int, np.integer)) else (int(input_size[0]), int(input_size[1]))
+    resized = xg if (fh, fw) == (th, tw) else model.resize_frames(xg, (th, tw))
+    c = model.num_classes if num_classes is None else int(num_classes)
+    if variant == "video":
+        mask, table = mc.clean_classes_video(model, model.resize_masks(model.segment(resized), (fw, fh)), num_classes=c)
+    else:
+        mask, table = mc.predict_v3(model, model.predict_proba(resized), (fh, fw), num_classes=c, **(thresholds or {}))
+    over = mc.overlay(model, xg, mask, colors, alpha, overlay_mode, model.num_classes)
+    if len(good) == b:
+        overlays = over
+    else:
+        overlays = x.clone()
+        overlays.index_copy_(0, torch.tensor(good, dtype=torch.int64, device=x.device), over)
+    stats = torch.stack((lap_var, gray_std, mad)).view(torch.int32).reshape(-1)               # float64 bits as int32 pairs
+    packed = torch.cat((table.reshape(-1), stats)).cpu().numpy()                               # read-back 2
+    tables = packed[:table.numel()].reshape(len(good), c, 5)
+    st = np.ascontiguousarray(packed[table.numel():]).view(np.float64).reshape(3, b)
+    for k, i in enumerate(good):
+        rec = {"reason": mc.REASONS[int(flags[1, i])], "lap_var": float(st[0, i]), "gray_std": float(st[1, i]), "mad": float(st[2, i]),
+               "table": tables[k].copy(), "events": mc.defect_events(tables[k], min_area_px=min_area_px)}
+        if validate is not None:
+            rec["valid"], rec["defects"] = mc.validate_detection(tables[k], (fh, fw), **validate)
+        records[i] = rec
+    return records, overlays, gray[-1]

@@ -105,16 +105,18 @@ def test_distance_and_ring_equal_numpy(torch_cuda, model, golden, shape):
 
 
 def test_views_at_an_odd_byte_offset(torch_cuda, model):
+    """37 x 53: the width alone selects the byte path.  32 x 128: every size is a multiple of 16, so the pointer decides."""
     torch = torch_cuda
-    r = np.random.default_rng(3)
-    m = (r.random((2, 37, 53)) >= 0.05).astype(np.uint8)
-    o = (r.random((2, 37, 53)) < 0.6).astype(np.uint8)
-    a, b = odd_view(torch, m), odd_view(torch, o)
-    want = np.stack([rb.distance_transform_np(f) for f in m])
-    assert np.array_equal(bits(rb.distance_transform(model, a).cpu().numpy()), bits(want))
-    ring = rb.distance_ring(model, a, b, 1, 3, invert=False)
-    assert np.array_equal(ring.cpu().numpy(), np.stack([rb.ring_np(f, g, 1, 3) for f, g in zip(m, o)]))
-    assert np.array_equal(rb.roi_limit(model, b, a, 2).cpu().numpy(), np.stack([rb.roi_limit_np(g, f, 2) for f, g in zip(m, o)]))
+    for shape in ((2, 37, 53), (2, 32, 128)):
+        r = np.random.default_rng(3)
+        m = (r.random(shape) >= 0.05).astype(np.uint8)
+        o = (r.random(shape) < 0.6).astype(np.uint8)
+        a, b = odd_view(torch, m), odd_view(torch, o)
+        want = np.stack([rb.distance_transform_np(f) for f in m])
+        assert np.array_equal(bits(rb.distance_transform(model, a).cpu().numpy()), bits(want)), shape
+        ring = rb.distance_ring(model, a, b, 1, 3, invert=False)
+        assert np.array_equal(ring.cpu().numpy(), np.stack([rb.ring_np(f, g, 1, 3) for f, g in zip(m, o)])), shape
+        assert np.array_equal(rb.roi_limit(model, b, a, 2).cpu().numpy(), np.stack([rb.roi_limit_np(g, f, 2) for f, g in zip(m, o)])), shape
 
 
 def test_wide_rows_and_far_zeros(torch_cuda, model):

@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/unetpp_roi.h"
 #include "abi_common.h"
 #include "components.h"
 #include "distance.h"
@@ -26,6 +27,7 @@
 #include "multiclass.h"
 #include "nlmeans.h"
 #include "probmap.h"
+#include "roi_loop.h"
 #include "tiling.h"
 
 using namespace unetpp;
@@ -1391,6 +1393,140 @@ int unetpp_overlay_u8(unetpp_engine* e, const uint8_t* dev_frames, const uint8_t
   ENTER_DEVICE(e);
   hipLaunchKernelGGL(overlay_kernel, dim3((unsigned)((items + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, (hipStream_t)stream, dev_frames,
                      dev_mask, n, C, w_frame, w_color, mode, vec16(16, dev_frames, dev_mask, dev_out), dev_out);
+  return launched(e);
+}
+
+// ---- the ROI and full-frame 3-class loops (roi_loop.h; include/unetpp_roi.h) ---------------------------------------------------
+struct RoiStatsWorkspace { size_t sums = 0, maxbits = 0, total = 0; };
+static bool roi_stats_layout(int batch, RoiStatsWorkspace* ws) {
+  if (batch < 1 || batch > MAX_DIM) return false;
+  Carve c;
+  ws->sums = c.take((size_t)batch * 3 * sizeof(unsigned long long));
+  ws->maxbits = c.take((size_t)batch * 3 * sizeof(unsigned));              // directly behind sums: one memset clears both
+  ws->total = c.end;
+  return true;
+}
+static bool roi_table_ok(const void* dev_roi) { return (uintptr_t)dev_roi % 4 == 0; }
+
+size_t unetpp_roi_projection_workspace_bytes(int batch, int w) {
+  return batch >= 1 && batch <= MAX_DIM && w >= 1 && w <= MAX_DIM ? align_up((size_t)batch * w * sizeof(int), 256) : 0;
+}
+
+size_t unetpp_roi_stats_workspace_bytes(int batch) {
+  RoiStatsWorkspace ws;
+  return roi_stats_layout(batch, &ws) ? ws.total : 0;
+}
+
+int unetpp_roi_from_edges_u8(unetpp_engine* e, const uint8_t* dev_edges, int batch, int h, int w, int32_t* dev_roi, void* dev_workspace,
+                             void* stream) {
+  REQUIRE_ROBUST(e, dev_edges && dev_roi && dev_workspace);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_UNSUPPORTED, "shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  if ((uintptr_t)dev_workspace % 4 || !roi_table_ok(dev_roi)) return fail(e, UNETPP_E_UNSUPPORTED, "dev_workspace and dev_roi must be 4-byte aligned");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  int* counts = (int*)dev_workspace;
+  HIP_TRY(e, hipMemsetAsync(counts, 0, (size_t)batch * w * sizeof(int), s));
+  hipLaunchKernelGGL(roi_column_count_kernel, dim3((unsigned)((w + ROI_THREADS - 1) / ROI_THREADS), (unsigned)((h + ROI_BAND - 1) / ROI_BAND), (unsigned)batch),
+                     dim3(ROI_THREADS), 0, s, dev_edges, h, w, counts);
+  hipLaunchKernelGGL(roi_decide_kernel, dim3((unsigned)batch), dim3(ROI_THREADS), 0, s, (const int*)counts, w, (int*)dev_roi);
+  return launched(e);
+}
+
+int unetpp_roi_crop_resize_u8(unetpp_engine* e, const uint8_t* dev_frames, int batch, int h, int w, int channels, const int32_t* dev_roi,
+                              uint8_t* dev_out, int out_h, int out_w, void* stream) {
+  REQUIRE_ROBUST(e, dev_frames && dev_roi && dev_out);
+  if (!shape_ok(batch, h, w, MASK_SHAPE) || !shape_ok(batch, out_h, out_w, MASK_SHAPE) || channels < 1 || channels > 4)
+    return fail(e, UNETPP_E_UNSUPPORTED, "crop_resize: bad shape %dx%dx%dx%d -> %dx%d", batch, h, w, channels, out_h, out_w);
+  if (!roi_table_ok(dev_roi)) return fail(e, UNETPP_E_UNSUPPORTED, "dev_roi must be 4-byte aligned");
+  if (overlaps(dev_frames, (size_t)batch * h * w * channels, dev_out, (size_t)batch * out_h * out_w * channels))
+    return fail(e, UNETPP_E_UNSUPPORTED, "dev_out aliases dev_frames");
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(roi_crop_resize_kernel, dim3((unsigned)((out_w + ROI_THREADS - 1) / ROI_THREADS), (unsigned)out_h, (unsigned)batch), dim3(ROI_THREADS), 0,
+                     (hipStream_t)stream, dev_frames, h, w, channels, (const int*)dev_roi, out_h, out_w, dev_out);
+  return launched(e);
+}
+
+static int roi_probs_check(unetpp_engine* e, const float* dev_probs, int batch, int channels, int h, int w) {
+  if (!shape_ok(batch, h, w, MASK_SHAPE) || channels < 3 || channels > MAX_DIM)
+    return fail(e, UNETPP_E_UNSUPPORTED, "probabilities %dx%dx%dx%d: 3 <= channels, 1 <= h, w <= 65535, h * w <= 2^30", batch, channels, h, w);
+  if ((uintptr_t)dev_probs % 4) return fail(e, UNETPP_E_UNSUPPORTED, "dev_probs must be 4-byte aligned");
+  return UNETPP_OK;
+}
+
+int unetpp_roi_adaptive_thresholds_f32(unetpp_engine* e, const float* dev_probs, int batch, int channels, int h, int w, float* dev_thresholds,
+                                       float* dev_means, float* dev_maxima, void* dev_workspace, void* stream) {
+  REQUIRE_ROBUST(e, dev_probs && dev_thresholds && dev_means && dev_maxima && dev_workspace);
+  if (int rc = roi_probs_check(e, dev_probs, batch, channels, h, w)) return rc;
+  RoiStatsWorkspace ws;
+  roi_stats_layout(batch, &ws);
+  if ((uintptr_t)dev_workspace % 8 || ((uintptr_t)dev_thresholds | (uintptr_t)dev_means | (uintptr_t)dev_maxima) % 4)
+    return fail(e, UNETPP_E_UNSUPPORTED, "dev_workspace must be 8-byte aligned, the tables 4-byte aligned");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned hw = (unsigned)h * (unsigned)w;
+  unsigned long long* sums = (unsigned long long*)((char*)dev_workspace + ws.sums);
+  unsigned* maxbits = (unsigned*)((char*)dev_workspace + ws.maxbits);
+  HIP_TRY(e, hipMemsetAsync(dev_workspace, 0, ws.total, s));
+  hipLaunchKernelGGL(roi_plane_sums_kernel, dim3((hw + PM_SPAN - 1) / PM_SPAN, 3u, (unsigned)batch), dim3(ROI_THREADS), 0, s, dev_probs, channels, hw, sums,
+                     maxbits);
+  hipLaunchKernelGGL(roi_thresholds_kernel, dim3((unsigned)((batch + ROI_THREADS - 1) / ROI_THREADS)), dim3(ROI_THREADS), 0, s,
+                     (const unsigned long long*)sums, (const unsigned*)maxbits, batch, hw, dev_thresholds, dev_means, dev_maxima);
+  return launched(e);
+}
+
+int unetpp_roi_ultra_strict_f32(unetpp_engine* e, const float* dev_probs, int batch, int channels, int h, int w, const float* dev_thresholds,
+                                uint8_t* dev_cable, uint8_t* dev_tape, void* stream) {
+  REQUIRE_ROBUST(e, dev_probs && dev_thresholds && dev_cable && dev_tape);
+  if (int rc = roi_probs_check(e, dev_probs, batch, channels, h, w)) return rc;
+  if ((uintptr_t)dev_thresholds % 4) return fail(e, UNETPP_E_UNSUPPORTED, "dev_thresholds must be 4-byte aligned");
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_cable, n, dev_tape, n) || overlaps(dev_probs, n * channels * sizeof(float), dev_cable, n) ||
+      overlaps(dev_probs, n * channels * sizeof(float), dev_tape, n))
+    return fail(e, UNETPP_E_UNSUPPORTED, "the masks overlap each other or dev_probs");
+  ENTER_DEVICE(e);
+  const unsigned hw = (unsigned)h * (unsigned)w;
+  hipLaunchKernelGGL(roi_ultra_strict_kernel, dim3((hw + PM_SPAN - 1) / PM_SPAN, (unsigned)batch), dim3(ROI_THREADS), 0, (hipStream_t)stream, dev_probs,
+                     channels, hw, dev_thresholds, dev_cable, dev_tape);
+  return launched(e);
+}
+
+int unetpp_roi_components_select(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num, const int32_t* dev_stats, const uint64_t* dev_sums,
+                                 int batch, int h, int w, int capacity, int rule, const unetpp_roi_cc_rule* params, uint8_t out_value, uint8_t* dev_out,
+                                 void* dev_workspace, void* stream) {
+  REQUIRE_ROBUST(e, dev_labels && dev_num && dev_stats && dev_sums && params && dev_out && dev_workspace);
+  CcWorkspace ws;
+  if (capacity < 2 || !cc_layout(batch, h, w, capacity, &ws))
+    return fail(e, UNETPP_E_UNSUPPORTED, "bad shape %dx%dx%d or capacity %d", batch, h, w, capacity);
+  if (rule != UNETPP_ROI_RULE_GEOMETRY && rule != UNETPP_ROI_RULE_PRIMARY) return fail(e, UNETPP_E_UNSUPPORTED, "unknown rule %d", rule);
+  const RoiCcRule r{params->min_area, params->min_aspect, params->wide_width, params->edge_lo, params->edge_hi, params->large_area};
+  if (std::isnan(r.min_area) || std::isnan(r.min_aspect) || std::isnan(r.wide_width) || std::isnan(r.edge_lo) || std::isnan(r.edge_hi) ||
+      std::isnan(r.large_area))
+    return fail(e, UNETPP_E_UNSUPPORTED, "component rule: NaN parameter");
+  if (out_value == 0) return fail(e, UNETPP_E_UNSUPPORTED, "out_value must not be 0");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  uint8_t* keep = (uint8_t*)dev_workspace + ws.keep;
+  hipLaunchKernelGGL(roi_cc_select_kernel, dim3((unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_num, (const int*)dev_stats,
+                     (const unsigned long long*)dev_sums, w, capacity, rule, r, keep);
+  hipLaunchKernelGGL(cc_apply_kernel, dim3((unsigned)ws.nchunk, (unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_labels,
+                     (const uint8_t*)keep, hw, capacity, vec16(hw, dev_labels, dev_out), (unsigned)out_value, dev_out);
+  return launched(e);
+}
+
+int unetpp_roi_paste_masks_u8(unetpp_engine* e, const uint8_t* dev_mask0, const uint8_t* dev_mask1, int batch, int h, int w, const int32_t* dev_roi,
+                              uint8_t* dev_out0, uint8_t* dev_out1, int out_h, int out_w, void* stream) {
+  REQUIRE_ROBUST(e, dev_mask0 && dev_mask1 && dev_roi && dev_out0 && dev_out1);
+  if (!shape_ok(batch, h, w, MASK_SHAPE) || !shape_ok(batch, out_h, out_w, MASK_SHAPE))
+    return fail(e, UNETPP_E_UNSUPPORTED, "paste_masks: bad shape %dx%dx%d -> %dx%d", batch, h, w, out_h, out_w);
+  if (!roi_table_ok(dev_roi)) return fail(e, UNETPP_E_UNSUPPORTED, "dev_roi must be 4-byte aligned");
+  const size_t n_in = (size_t)batch * h * w, n_out = (size_t)batch * out_h * out_w;
+  if (overlaps(dev_out0, n_out, dev_out1, n_out) || overlaps(dev_out0, n_out, dev_mask0, n_in) || overlaps(dev_out0, n_out, dev_mask1, n_in) ||
+      overlaps(dev_out1, n_out, dev_mask0, n_in) || overlaps(dev_out1, n_out, dev_mask1, n_in))
+    return fail(e, UNETPP_E_UNSUPPORTED, "an output overlaps the other output or an input");
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(roi_paste_kernel, dim3((unsigned)((out_w + ROI_THREADS - 1) / ROI_THREADS), (unsigned)out_h, (unsigned)batch), dim3(ROI_THREADS), 0,
+                     (hipStream_t)stream, dev_mask0, dev_mask1, h, w, (const int*)dev_roi, out_h, out_w, dev_out0, dev_out1);
   return launched(e);
 }
 

@@ -7,6 +7,8 @@ algorithm and are parity-unpinned, see oracle/unetpp_oracle.py).  `measure_frame
 (infer_video_production.py:198-226): the diameter metrics and the defect analysis of every frame of a batch.
 `process_frames_multiclass` is the frame loop of the 6- and 7-class scripts (infer_video.py:359-464,
 infer_video_v3_high_quality.py, infer_video_optimized.py): quality gate, model, class clean-up, class table, overlay.
+`process_frames_roi` and `process_frames_3class_full` are infer_frame of infer_video_roi.py (:193-259) and of
+infer_video_3class_full.py (:193-261): the two 3-class loops that decide things per frame from the frame itself (roi_loop.py).
 """
 from __future__ import annotations
 
@@ -242,3 +244,80 @@ def process_frames_multiclass(model, frames_bgr_u8, prev_gray=None, *, input_siz
             rec["valid"], rec["defects"] = mc.validate_detection(tables[k], (fh, fw), **validate)
         records[i] = rec
     return records, overlays, gray[-1]
+
+
+def _raise_loop_overflow(what, nums, k):
+    for name, col in nums:
+        for i, v in enumerate(col):
+            if v > k:
+                raise RuntimeError(f"{what}: frame {i} has num = {v} labels in its {name} labelling (background included), more than "
+                                   f"max_components = {k}: raise max_components")
+
+
+def process_frames_roi(model, frames_bgr_u8, *, use_roi=True, input_size=512, max_components=8192, device=None, **geometry):
+    """infer_frame of infer_video_roi.py (:193-259) for B raw BGR frames of one size at once, every step on the device
+    (roi_loop.py holds every step and its NumPy form):
+      1. detect_roi_by_projection (roi_loop.detect_roi; use_roi=False: the whole frame)
+      2. the crop and cv2.resize to input_size, the source width read from the device table
+      3. the model's probabilities (predict_proba)
+      4. adaptive_thresholding and ultra_strict_threshold with that frame's own thresholds
+      5. refine_mask_by_geometry on both masks (`geometry`: its min_area, min_aspect, wide_width, edge_lo, edge_hi, large_area)
+      6. cv2.resize INTER_NEAREST back and the paste into the full frame
+      7. ONE read-back: the two coverages, the ROI table and the labellings' num
+    Returns (mask_cable, mask_tape uint8 0/1 [B,H,W] on the device, metrics: a list of B dicts with cable_coverage,
+    tape_coverage and roi = (x_min, x_max), roi int32 [B,4] on the device).  A frame whose ROI is empty (valid = 0; the
+    reference's cv2.resize raises there) gets zero masks and zero coverages.  Overlay, text and events stay on the host."""
+    import torch
+    from . import roi_loop as rl
+    x = frames_bgr_u8
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not x.is_cuda:
+        x = x.to(device if device is not None else f"cuda:{model._device_index or 0}", non_blocking=True)
+    b, fh, fw = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+    k, size = int(max_components), int(input_size)
+    roi = rl.detect_roi(model, x) if use_roi else rl.full_roi(model, x)
+    probs = model.predict_proba(rl.crop_resize(model, x, roi, size))
+    cable, tape, counts, _ = rl.postprocess_roi(model, probs, roi, (fh, fw), max_components=k, **geometry)
+    table = torch.cat((counts, roi), dim=1).cpu().tolist()                                    # the read-back: 8 B integers
+    _raise_loop_overflow("process_frames_roi", (("cable", [r[2] for r in table]), ("tape", [r[3] for r in table])), k)
+    metrics = [{"cable_coverage": r[0] / (size * size), "tape_coverage": r[1] / (size * size), "roi": (r[4], r[5])} for r in table]
+    return cable, tape, metrics, roi
+
+
+def process_frames_3class_full(model, frames_bgr_u8, *, input_size=512, t_cable=0.45, t_tape=0.50, bg_margin=0.15, use_cc_filter=True,
+                               cc_min_area_cable=1000, cc_min_area_tape=500, cable_min_aspect=1.6, tape_dilate_px=15, max_components=8192,
+                               device=None):
+    """infer_frame of infer_video_3class_full.py (:193-261) for B raw BGR frames of one size at once, every step on the device:
+    resize_frames to input_size, segment_thresholded(rule="thresholded_argmax"), select_primary_component on the cable,
+    tape & dilate(cable, ELLIPSE 2 tape_dilate_px + 1) for the frames whose cable is not empty (one morphology program),
+    keep_largest_cc on the tape (filter_components, rule="largest"), resize_masks to the frame size,
+    measure_diameters_simple and the coverages at model size.  Returns (mask_cable, mask_tape uint8 0/1 [B,H,W], metrics: a
+    list of B dicts of robust.MEASURE_FIELDS, pred uint8 [B,input_size,input_size] with cable 1 and tape 2); the metrics and
+    the labellings' num are the one read-back."""
+    import torch
+    from . import robust
+    from . import roi_loop as rl
+    x = frames_bgr_u8
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not x.is_cuda:
+        x = x.to(device if device is not None else f"cuda:{model._device_index or 0}", non_blocking=True)
+    fh, fw = int(x.shape[1]), int(x.shape[2])
+    k, size = int(max_components), int(input_size)
+    resized = x if (fh, fw) == (size, size) else model.resize_frames(x, (size, size))
+    cable_s, tape_s = model.segment_thresholded(resized, "thresholded_argmax", t_cable, t_tape, bg_margin)
+    n = size * size
+    if use_cc_filter:
+        cable, tape, cable_s, tape_s, table = rl.postprocess_3class_full(
+            model, cable_s, tape_s, (fh, fw), cc_min_area_cable=cc_min_area_cable, cc_min_area_tape=cc_min_area_tape,
+            cable_min_aspect=cable_min_aspect, tape_dilate_px=tape_dilate_px, max_components=k)
+    else:
+        cable, tape = model.resize_masks(cable_s, (fw, fh)), model.resize_masks(tape_s, (fw, fh))
+        table = robust._measure_table(model, cable_s, tape_s)
+    pred = torch.where(tape_s > 0, torch.full_like(tape_s, 2), cable_s)   # pred_mask[cable > 0] = 1, then [tape > 0] = 2
+    rows = table.cpu().tolist()                                            # the read-back
+    if use_cc_filter:
+        _raise_loop_overflow("process_frames_3class_full", (("cable", [int(r[5]) for r in rows]), ("tape", [int(r[6]) for r in rows])), k)
+    metrics = [dict(zip(robust.MEASURE_FIELDS, r[:3] + [int(r[3]) / n, int(r[4]) / n])) for r in rows]
+    return cable, tape, metrics, pred

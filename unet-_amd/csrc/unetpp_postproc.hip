@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/unetpp_loss.h"
 #include "../../include/unetpp_roi.h"
 #include "abi_common.h"
 #include "components.h"
@@ -23,6 +24,7 @@
 #include "evaluation.h"
 #include "frame_kernels.h"
 #include "geometry.h"
+#include "loss.h"
 #include "morphology.h"
 #include "multiclass.h"
 #include "nlmeans.h"
@@ -1527,6 +1529,49 @@ int unetpp_roi_paste_masks_u8(unetpp_engine* e, const uint8_t* dev_mask0, const 
   ENTER_DEVICE(e);
   hipLaunchKernelGGL(roi_paste_kernel, dim3((unsigned)((out_w + ROI_THREADS - 1) / ROI_THREADS), (unsigned)out_h, (unsigned)batch), dim3(ROI_THREADS), 0,
                      (hipStream_t)stream, dev_mask0, dev_mask1, h, w, (const int*)dev_roi, out_h, out_w, dev_out0, dev_out1);
+  return launched(e);
+}
+
+// ---- validation losses: the five sums per frame and class (loss.h; include/unetpp_loss.h) ---------------------------------------
+int unetpp_loss_layout(int* span_pixels) {
+  if (!span_pixels) return UNETPP_E_UNSUPPORTED;
+  *span_pixels = LS_SPAN;
+  return UNETPP_OK;
+}
+
+int unetpp_loss_sums_f32(unetpp_engine* e, const float* dev_logits, const uint8_t* dev_target, int batch, int classes, int h, int w, int gamma,
+                         uint64_t* dev_table, uint32_t* dev_outside, void* stream) {
+  REQUIRE_ROBUST(e, dev_logits && dev_target && dev_table && dev_outside);
+  if (batch < 1 || batch > MAX_DIM || h < 1 || w < 1 || (size_t)h * (size_t)w > LS_MAX_PIXELS)
+    return fail(e, UNETPP_E_UNSUPPORTED, "loss sums: shape %dx%dx%d outside 1 <= batch <= 65535, h, w >= 1, h * w <= 2^22", batch, h, w);
+  if (classes < 2 || classes > LS_MAX_CLASSES || gamma < 0 || gamma > LS_MAX_GAMMA)
+    return fail(e, UNETPP_E_UNSUPPORTED, "loss sums: classes %d outside 2..8 or gamma %d outside 0..4", classes, gamma);
+  if ((uintptr_t)dev_logits % 4 || (uintptr_t)dev_table % 8 || (uintptr_t)dev_outside % 4)
+    return fail(e, UNETPP_E_UNSUPPORTED, "dev_logits and dev_outside must be 4-byte aligned, dev_table 8-byte aligned");
+  const size_t hw = (size_t)h * w, n_logits = (size_t)batch * classes * hw * sizeof(float), n_target = (size_t)batch * hw;
+  const size_t n_table = (size_t)batch * classes * LS_COLUMNS * sizeof(unsigned long long), n_outside = (size_t)batch * 2 * sizeof(unsigned);
+  if (overlaps(dev_table, n_table, dev_outside, n_outside) || overlaps(dev_table, n_table, dev_logits, n_logits) ||
+      overlaps(dev_table, n_table, dev_target, n_target) || overlaps(dev_outside, n_outside, dev_logits, n_logits) ||
+      overlaps(dev_outside, n_outside, dev_target, n_target))
+    return fail(e, UNETPP_E_UNSUPPORTED, "loss sums: an output overlaps the other output or an input");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  if ((const char*)dev_outside == (const char*)dev_table + n_table) {
+    HIP_TRY(e, hipMemsetAsync(dev_table, 0, n_table + n_outside, s));
+  } else {
+    HIP_TRY(e, hipMemsetAsync(dev_table, 0, n_table, s));
+    HIP_TRY(e, hipMemsetAsync(dev_outside, 0, n_outside, s));
+  }
+  const dim3 grid((unsigned)((hw + LS_GROUP - 1 + LS_SPAN - 1) / LS_SPAN), (unsigned)batch);
+#define LOSS_SUMS_CASE(C)                                                                                                   \
+  case C:                                                                                                                   \
+    hipLaunchKernelGGL(loss_sums_kernel<C>, grid, dim3(LS_THREADS), 0, s, dev_logits, dev_target, (unsigned)hw, gamma,       \
+                       (unsigned long long*)dev_table, (unsigned*)dev_outside);                                              \
+    break
+  switch (classes) {
+    LOSS_SUMS_CASE(2); LOSS_SUMS_CASE(3); LOSS_SUMS_CASE(4); LOSS_SUMS_CASE(5); LOSS_SUMS_CASE(6); LOSS_SUMS_CASE(7); LOSS_SUMS_CASE(8);
+  }
+#undef LOSS_SUMS_CASE
   return launched(e);
 }
 

@@ -260,7 +260,8 @@ __device__ __forceinline__ void ws_epilogue(KernArgs<ConvArgs> a, const float16v
 // the constant 1 and the partial buffer, the counters and the share arithmetic are not compiled.
 // The arguments are read in place (KernArgs, conv3x3_mfma.h): each role fetches the fields it uses, and what a role needs
 // once per tile it reads again at the tile boundary instead of holding it across the chunk loop.
-// UR (conv3x3_ws_uprows_kernel, `exact`, Cout = 32, fused upsample): the up chunks are multiplied on LOW-RESOLUTION ROWS and
+// UR (conv3x3_ws_uprows_kernel, `exact`, fused upsample, 32 output channels per workgroup: Cout = 32, or Cout = 64 as two channel
+// tiles per pixel tile): the up chunks are multiplied on LOW-RESOLUTION ROWS and
 // interpolated in y afterwards, in the accumulators.  The upsample is separable,
 //   U[y'] = (1 - f(y')) T[r(y')] + f(y') T[r(y') + 1],     T[r] = the x-interpolation of low row r at full-resolution columns,
 // so with Y_dy[r][x] = sum_dx W[dy, dx] T[r][x + dx] (a 1x3 product on a low row, 32 pixels on the lanes)
@@ -272,19 +273,22 @@ __device__ __forceinline__ void ws_epilogue(KernArgs<ConvArgs> a, const float16v
 //   * producers, up chunk: x-interpolation only, into the image T = low rows k0 - 1 .. k0 + 8 x columns x0 - 1 .. x0 + 32 (zeros
 //     outside the image) in the halo image's record layout; the low-res records of a tile's first up chunk arrive during the
 //     previous tile's last chunk;
-//   * consumer wave w: Y_dy[k0 + 2 w], Y_dy[k0 + 2 w + 1] for the three dy; wave 0 also (k0 - 1; dy -1, 0), wave 3 also
-//     (k0 + 8; dy 0, +1): 8, 6, 6, 8 accumulators, 72 MFMAs per up chunk in the busiest wave instead of 108;
+//   * consumer wave w: Y_dy[k0 + 2 w], Y_dy[k0 + 2 w + 1] for the three dy, and ONE of the four edge accumulators: wave 0
+//     (k0 - 1; dy -1), wave 1 (k0 - 1; dy 0), wave 2 (k0 + 8; dy 0), wave 3 (k0 + 8; dy +1) (all of T is in the stage buffer, any
+//     wave can read its first or last row): seven accumulators each, 63 MFMAs per up chunk in every wave instead of 108
+//     (tests/test_uprows_balance_host.py restates this plan; the 8, 6, 6, 8 plan of tests/test_uprows_host.py preceded it);
 //   * fold, behind the last up chunk: wave w needs (k0 + 2 w - 1; dy -1, 0) from wave w - 1 and (k0 + 2 w + 2; dy 0, +1) from
 //     wave w + 1.  They pass through the stage buffer the last up chunk has released (48 KB); the producers hold that buffer's
-//     refill back behind two extra barriers.  The edge rows of waves 0 and 3 go through LDS as well (16 KB behind the scale /
-//     bias table), so that six, not eight, Y accumulators are live beside the four Z rows: 249 registers, no spill.  Each Z row
-//     sums its terms in the fixed order dy = -1, 0, +1, lower row first: bitwise reproducible and batch-row invariant.
+//     refill back behind two extra barriers.  The four edge accumulators go through LDS as well (16 KB behind the scale /
+//     bias table; wave w writes edge slot w, waves 0 and 3 read them), so that six Y accumulators are live beside the four Z
+//     rows.  Each Z row sums its terms in the fixed order dy = -1, 0, +1, lower row first: bitwise reproducible and batch-row
+//     invariant.
 // ur_row / ur_slot: the ownership table, restated in tests/test_uprows_host.py.
 __host__ __device__ constexpr int ur_row(int m, int dy) { return (m + dy + 1) / 2 - 1; }      // low row of image row 4 w + m + dy, relative to k0 + 2 w: -1 .. 2
 // exchange slots (one accumulator, 4 KB each) of the boundary between waves b and b + 1: 0, 1 = (k0 + 2 b + 1; dy -1, 0) going up
 // to wave b + 1, 2, 3 = (k0 + 2 b + 2; dy 0, +1) going down to wave b
 __host__ __device__ constexpr int ur_slot(int boundary, int i) { return boundary * 4 + i; }
-constexpr int UR_EDGE_BYTES = 4 * 4096;      // LDS behind the scale / bias table: (k0 - 1; dy -1, 0) of wave 0, (k0 + 8; dy 0, +1) of wave 3
+constexpr int UR_EDGE_BYTES = 4 * 4096;      // LDS behind the scale / bias table: (k0 - 1; dy -1, 0) from waves 0, 1, (k0 + 8; dy 0, +1) from waves 2, 3
 
 // fraction of the bilinear x2 upsample (align_corners=True) at destination index `dst` whose lower source index is `i0`
 __device__ __forceinline__ float up_frac(float scale, int dst, int i0) {
@@ -294,7 +298,7 @@ __device__ __forceinline__ float up_frac(float scale, int dst, int i0) {
 template <int P, bool POOL, bool HEAD, bool UPF, bool C0F, int NW, int MWP, bool X8, bool CAT2, bool SPLITK, bool UR = false>
 __device__ __forceinline__ void conv3x3_ws_body() {
   using C = WsCfg<P, UPF, C0F, NW, MWP, X8>;
-  static_assert(!UR || (UPF && P == 2 && !X8 && NW == 1 && MWP == 4 && !SPLITK), "low-row up chunks: exact, Cout = 32, fused upsample");
+  static_assert(!UR || (UPF && P == 2 && !X8 && NW == 1 && MWP == 4 && !SPLITK), "low-row up chunks: exact, 32 channels per workgroup, fused upsample");
   static_assert(!SPLITK || (!UPF && !C0F && !HEAD), "split-K: plain and pooling layers only (launch_ws_k)");
   KernArgs<ConvArgs> a = kernargs<ConvArgs>();
   static_assert(!C0F || (!UPF && !HEAD && P == 2 && NW == 1), "fused first block: exact mode, no other fusion in the loader");
@@ -1269,7 +1273,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
   };
 
   // UR: fragment offsets into the image T (rows k0 - 1 .. k0 + 8, the halo image's layout): this wave's two rows k0 + 2 w,
-  // k0 + 2 w + 1 and, waves 0 and 3, the tile's first / last row of T
+  // k0 + 2 w + 1 and the tile's first (waves 0, 1) / last (waves 2, 3) row of T
   constexpr int TR = UR ? 3 : 1;
   int t_off[TR][3];
   if (UR) {
@@ -1277,7 +1281,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
     for (int r = 0; r < TR; ++r)
 #pragma unroll
       for (int dx = 0; dx < 3; ++dx) {
-        const int tr = r < 2 ? 2 * cw + 1 + r : (cw == 0 ? 0 : C::LSH - 1);
+        const int tr = r < 2 ? 2 * cw + 1 + r : (2 * cw < C::NCONS ? 0 : C::LSH - 1);
         const int hp = tr * HALO_W + (lane & 31) + dx;
         t_off[r][dx] = (hp / PPP) * 1024 + ((lane >> 5) * PPP + hp % PPP) * 16;
       }
@@ -1336,7 +1340,8 @@ __device__ __forceinline__ void conv3x3_ws_body() {
     // loop below is left with the skip chunks
     const int ur_nup = UR ? a->nchunks - nch0 : 0;
     if constexpr (UR) {
-      float16v yo[2][3], ye[2];                           // Y_dy of the wave's two rows [row][dy + 1]; of its edge row (wave 0: dy -1, 0; wave 3: dy 0, +1)
+      static_assert(C::NCONS == 4, "one edge accumulator per consumer wave");
+      float16v yo[2][3], ye;                              // Y_dy of the wave's two rows [row][dy + 1]; its edge accumulator (wave 0: dy -1, waves 1, 2: dy 0, wave 3: dy +1)
       // (the tile's first up chunk is a copy of the code that starts every accumulator from the MFMA's zero operand: no test per step)
       auto up_chunk = [&](auto first_tag) {
         constexpr bool FIRST = decltype(first_tag)::value;
@@ -1354,7 +1359,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
         auto load_t = [&](TFrag& f, int dx, int r0, int r1) {
 #pragma unroll
           for (int r = 0; r < TR; ++r)
-            if (r >= r0 && r < r1 && (r < 2 || cw == 0 || cw == C::NCONS - 1)) {
+            if (r >= r0 && r < r1) {
               const char* p = halo + t_off[r][dx];
               f.h[r] = *(const half8*)p;
               f.l[r] = *(const half8*)(p + KG * PPP * 16);
@@ -1381,8 +1386,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
               const bool Z0 = FIRST && dx == 0;           // (a constant once the loops are unrolled)
               ur_mfma(yo[0][dy], fb, ft, 0, Z0);
               ur_mfma(yo[1][dy], fb, ft, 1, Z0);
-              if (cw == 0) { if (dy < 2) ur_mfma(ye[dy < 2 ? dy : 0], fb, ft, 2, Z0); }
-              else if (cw == C::NCONS - 1) { if (dy >= 1) ur_mfma(ye[dy >= 1 ? dy - 1 : 0], fb, ft, 2, Z0); }
+              if (dy == 0 ? cw == 0 : dy == 2 ? cw == C::NCONS - 1 : (cw != 0 && cw != C::NCONS - 1)) ur_mfma(ye, fb, ft, 2, Z0);
             }
             __builtin_amdgcn_sched_barrier(0);
           }
@@ -1400,7 +1404,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       // slots 0 .. 11 (ur_slot) lie over the stage buffer, the four edge slots behind the scale / bias table (UR_EDGE_BYTES more LDS)
       constexpr int UR_EDGE = 12;
       char* xb0 = smem + ((g - 1) & 1) * C::BUF_BYTES + lane * 16;
-      char* xe = smem + C::LDS_BYTES + 32 * 8 - UR_EDGE * 4096 + lane * 16;
+      char* xe = smem + C::LDS_BYTES + a->Cout * 8 - UR_EDGE * 4096 + lane * 16;      // (the table holds all Cout channels, nct tiles of 32)
       auto put = [&](int slot, const float16v& v) {
         char* xb = slot >= UR_EDGE ? xe : xb0;
 #pragma unroll
@@ -1418,10 +1422,9 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       };
       if (cw < C::NCONS - 1) { put(ur_slot(cw, 0), yo[1][0]); put(ur_slot(cw, 1), yo[1][1]); }
       if (cw > 0) { put(ur_slot(cw - 1, 2), yo[0][1]); put(ur_slot(cw - 1, 3), yo[0][2]); }
-      // the edge rows' accumulators of waves 0 and 3 take the same way, through four slots of their own (UR_EDGE): every wave then
-      // folds the same program, and its registers hold six Y accumulators instead of eight while the Z rows form
-      if (cw == 0) { put(UR_EDGE, ye[0]); put(UR_EDGE + 1, ye[1]); }
-      if (cw == C::NCONS - 1) { put(UR_EDGE + 2, ye[0]); put(UR_EDGE + 3, ye[1]); }
+      // the four edge accumulators take the same way, through four slots of their own (UR_EDGE + w from wave w): every wave then
+      // folds the same program, and its registers hold six Y accumulators while the Z rows form
+      put(UR_EDGE + cw, ye);
       lds_barrier();
       const int prev_slot = cw == 0 ? UR_EDGE : ur_slot(cw - 1, 0);                      // (k0 + 2 w - 1; dy -1, 0)
       const int next_slot = cw == C::NCONS - 1 ? UR_EDGE + 2 : ur_slot(cw, 2);            // (k0 + 2 w + 2; dy 0, +1)
@@ -1751,7 +1754,8 @@ template <int P, bool POOL, int NW = 1, int MWP = 4, bool X8 = false, bool CAT2 
 __global__ __launch_bounds__(512, 2) void conv3x3_ws_splitk_kernel(ConvArgs) {
   conv3x3_ws_body<P, POOL, false, false, false, NW, MWP, X8, CAT2, true>();
 }
-// `exact`, Cout = 32, fused upsample, at least two skip chunks: the up chunks on low-resolution rows (UR, above)
+// `exact`, fused upsample, at least two skip chunks, Cout = 32 or 64 (nct = Cout / 32 channel tiles per pixel tile, each with
+// its own 32-channel weight slabs): the up chunks on low-resolution rows (UR, above)
 __global__ __launch_bounds__(512, 2) void conv3x3_ws_uprows_kernel(ConvArgs) {
   conv3x3_ws_body<2, false, false, true, false, 1, 4, false, false, false, true>();
 }

@@ -70,6 +70,7 @@ struct ConvLayer {
   bool c0f = false;             // conv0_0.conv2 computing conv0_0.conv1 itself from the caller's input (conv3x3_ws.h, C0F)
   bool upf = false;             // in2 is the LOW-resolution tensor: the loader does the bilinear x2 itself (no `up` tensor)
   bool ws = false;              // runs in the wave-specialised kernel (conv3x3_ws.h), else the lock-step one: fixes the weight layout too
+  bool uprows = false;          // fused upsample on low-resolution rows (conv3x3_ws_uprows_kernel): 32-channel weight tiles (NW = 1)
   size_t w_off = 0, b_off = 0;  // float offsets inside the canonical blob payload
   int KC = 16, NW = 1, MW = 2, WAVES = 8;
   int nchunks = 1;
@@ -266,7 +267,8 @@ hipError_t launch_ws_k(const LaunchCtx& cx, ConvArgs a, hipStream_t s, bool upro
   if constexpr (!UPF && !C0F && !HEAD) {
     if (ks > 1) k = conv3x3_ws_splitk_kernel<P, POOL, NW, MW, X8, CAT2>;
   }
-  // `exact`, Cout = 32, fused upsample: the up chunks on low-resolution rows (conv3x3_ws.h, UR); same tiles, same LDS, same weights
+  // `exact`, fused upsample, 32 channels per workgroup: the up chunks on low-resolution rows (conv3x3_ws.h, UR); same tiles, same LDS,
+  // same weights as the plain 1 x 4 kernel (a.nct = Cout / 32 channel tiles per pixel tile)
   if constexpr (P == 2 && UPF && !POOL && !HEAD && !C0F && NW == 1 && MW == 4 && !X8) {
     if (uprows) k = conv3x3_ws_uprows_kernel;
   }
@@ -279,6 +281,10 @@ hipError_t launch_ws_k(const LaunchCtx& cx, ConvArgs a, hipStream_t s, bool upro
 template <bool X8>
 hipError_t launch_ws_x(const LaunchCtx& cx, int P, const ConvArgs& a, bool pool, bool head, bool upf, bool c0f, bool uprows, hipStream_t s) {
   if (P != 2 || (upf && (pool || head)) || (pool && head)) return hipErrorInvalidValue;
+  if (uprows) {      // planned in unetpp_create: Cout / 32 channel tiles per 16-row pixel tile, weights packed to match
+    if (X8 || !upf || c0f || (a.Cout != 32 && a.Cout != 64)) return hipErrorInvalidValue;
+    return launch_ws_k<2, false, false, true, false, 1, 4, X8>(cx, a, s, true);
+  }
   if (a.Cout >= 64 && a.Cout % 64 == 0) {      // 8-row tiles, two 32-channel blocks per consumer wave, Cout / 64 channel tiles
     if (head || c0f) return hipErrorInvalidValue;
     if (upf) return launch_ws_k<2, false, false, true, false, 2, 2, X8>(cx, a, s);
@@ -289,7 +295,7 @@ hipError_t launch_ws_x(const LaunchCtx& cx, int P, const ConvArgs& a, bool pool,
   if (a.in1 && !upf) return hipErrorInvalidValue;
   if (a.Cout != 32) return hipErrorInvalidValue;
   if (c0f) return (pool && !head && !upf && a.nchunks == 2) ? launch_ws_k<2, true, false, false, true, 1, 4, X8>(cx, a, s) : hipErrorInvalidValue;
-  if (upf) return launch_ws_k<2, false, false, true, false, 1, 4, X8>(cx, a, s, uprows && !X8);
+  if (upf) return launch_ws_k<2, false, false, true, false, 1, 4, X8>(cx, a, s);
   if (head) return launch_ws_k<2, false, true, false, false, 1, 4, X8>(cx, a, s);
   if (pool) return launch_ws_k<2, true, false, false, false, 1, 4, X8>(cx, a, s);
   return launch_ws_k<2, false, false, false, false, 1, 4, X8>(cx, a, s);
@@ -638,6 +644,21 @@ int unetpp_create(const unetpp_config* cfg, unetpp_engine** out) {
   // exact modes the wave-specialised one, except SimpleUNet's two-source decoder convs in exact, which stay on the
   // lock-step kernel (same speed, and results that do not depend on a split-K plan: DESIGN.md 5.6); fast: lock-step.
   for (ConvLayer& L : e->convs) L.ws = P == 2 && (L.in2 < 0 || L.upf || e->x8);
+  // `exact`, fused upsample with at least two skip chunks, Cout = 32 or 64 (conv0_4.conv1, conv1_3.conv1): the kernel that multiplies
+  // the up chunks on low-resolution rows, 32 output channels per workgroup -- Cout = 64 runs as two channel tiles per pixel tile, so
+  // its weights are packed in 32-channel slabs (NW = 1; L.MW x L.WAVES stays the 16-row tile).  Cout >= 128 would repeat halo and
+  // interpolation four to eight times per pixel tile and stays on the 2 x 2 kernel.  UNETPP_UPROWS=levels overrides, e.g. "0"
+  // (level 0 only) or "none".
+  {
+    const char* ul = getenv("UNETPP_UPROWS");
+    for (ConvLayer& L : e->convs) {
+      if (!L.ws || !L.upf || P != 2 || e->x8 || (L.cout != 32 && L.cout != 64) || L.lvl > 9) continue;
+      const int c0 = e->tensors[L.in].C, c1 = e->tensors[L.in2].C;
+      if (c0 < 32 || c0 % 16 || c1 < 16 || c1 % 16 || strchr(ul ? ul : "01", '0' + L.lvl) == nullptr) continue;
+      L.uprows = true;
+      L.NW = 1;
+    }
+  }
   if (e->x8)      // EXACT8 exists in the wave-specialised kernel only: every conv must have a variant there (launch_ws_x)
     for (const ConvLayer& L : e->convs)
       if (!L.ws || (L.cout != 32 && L.cout % 64) || (L.in2 >= 0 && (L.do_pool || (!L.upf && L.cout % 64)))) {
@@ -1004,9 +1025,9 @@ static int forward_impl(unetpp_engine* e, const void* dev_input, int in_format, 
         char lbl[160];
         // labels end in the kernel's full template argument list, as rocprofv3 prints it (bench.py matches on it)
         auto tf = [](bool v) { return v ? "true" : "false"; };
-        // `exact`, Cout = 32, fused upsample with at least two skip chunks (conv0_4.conv1): the kernel that multiplies the up chunks on
-        // low-resolution rows; debug_keep_intermediates keeps the plain fused-upsample kernel reachable for this layer
-        const bool uprows = L.ws && L.upf && P == 2 && !e->x8 && L.cout == 32 && !e->keep_all && t0.C >= 32 && t0.C % 16 == 0 && c1 >= 16 && c1 % 16 == 0;
+        // the layers planned for the low-row kernel (unetpp_create); debug_keep_intermediates keeps the plain fused-upsample kernel
+        // reachable for conv0_4.conv1 (Cout = 32: one weight layout for both kernels), and for that layer only
+        const bool uprows = L.uprows && !(e->keep_all && L.cout == 32);
         if (uprows) snprintf(lbl, sizeof lbl, "%s+up|conv3x3_ws_uprows_kernel", L.name.c_str());
         else if (L.ws) snprintf(lbl, sizeof lbl, "%s%s%s%s|conv3x3_ws_kernel<%d, %s, %s, %s, %s, %d, %d, %s, %s>", L.c0f ? "input+conv0_0.conv1+" : "", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "", P, tf(L.do_pool), tf(head), tf(L.upf), tf(L.c0f), L.cout == 32 ? 1 : 2, L.cout == 32 ? 4 : 2, tf(e->x8), tf(L.in2 >= 0 && !L.upf));
         else snprintf(lbl, sizeof lbl, "%s%s%s|conv3x3_bias_relu_kernel<%d, %d, %d, %d, %d, %s, %s, %s>", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "", P, L.KC, L.NW, mw, L.WAVES, tf(L.do_pool), tf(head), tf(L.upf));

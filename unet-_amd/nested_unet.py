@@ -358,7 +358,8 @@ class NestedUNet(PostProcessing):
     def debug_keep_intermediates(self, on: bool = True):
         """Materialise x0_4 and run the head unfused (needed before debug_activation('x0_4')).  In 'exact' conv0_4.conv1 then
         also runs in the plain fused-upsample kernel instead of conv3x3_ws_uprows_kernel: same layer, another
-        plan, logits within 5e-6."""
+        plan, logits within 5e-6.  That layer only: conv1_3.conv1, which runs in the same kernel as two 32-channel tiles, keeps
+        the plan its engine was created with (UNETPP_UPROWS picks the levels; its weights are packed for that kernel)."""
         self._keep_all = bool(on)                    # also applied to an engine that is (re)built later
         if self._handle is not None:
             _lib.load().unetpp_debug_keep_intermediates(self._handle, 1 if on else 0)

@@ -13,10 +13,12 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/unetpp_contours.h"
 #include "../../include/unetpp_loss.h"
 #include "../../include/unetpp_roi.h"
 #include "abi_common.h"
 #include "components.h"
+#include "contours.h"
 #include "distance.h"
 #include "edges.h"
 #include "edges_multi.h"
@@ -1572,6 +1574,133 @@ int unetpp_loss_sums_f32(unetpp_engine* e, const float* dev_logits, const uint8_
     LOSS_SUMS_CASE(2); LOSS_SUMS_CASE(3); LOSS_SUMS_CASE(4); LOSS_SUMS_CASE(5); LOSS_SUMS_CASE(6); LOSS_SUMS_CASE(7); LOSS_SUMS_CASE(8);
   }
 #undef LOSS_SUMS_CASE
+  return launched(e);
+}
+
+// ---- external contours, the enclosing circle, paste and the chained overlay (contours.h; include/unetpp_contours.h) ---------------
+struct CtWorkspace { size_t plane = 0, inside = 0, bg_labels = 0, bg_num = 0, flags = 0, rows = 0, cc = 0, total = 0; };
+static bool ct_layout(int batch, int h, int w, int capacity, CtWorkspace* ws) {
+  if (batch < 1 || batch > MAX_DIM || h < 1 || w < 1 || h > CT_MAX_SIDE || w > CT_MAX_SIDE || capacity < 2) return false;
+  CcWorkspace cc;
+  if (!cc_layout(batch, h, w, capacity, &cc)) return false;
+  const size_t hw = (size_t)h * w;
+  Carve c;
+  ws->plane = c.take(hw * batch);
+  ws->inside = c.take(hw * batch);
+  ws->bg_labels = c.take(hw * batch * sizeof(int));
+  ws->bg_num = c.take((size_t)batch * sizeof(int));
+  ws->flags = c.take((hw + 1) * batch);
+  ws->rows = c.take((size_t)h * batch * sizeof(unsigned));
+  ws->cc = c.take(cc.total);
+  ws->total = c.end;
+  return true;
+}
+static const char* const CT_SHAPE_TEXT = "outside 1 <= batch <= 65535, 1 <= h, w <= 4095, capacity >= 2";
+
+size_t unetpp_contours_workspace_bytes(int batch, int h, int w, int capacity) {
+  CtWorkspace ws;
+  return ct_layout(batch, h, w, capacity, &ws) ? ws.total : 0;
+}
+
+int unetpp_contour_areas_u8(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, int match_class, int capacity, int32_t* dev_labels,
+                            int32_t* dev_num, uint64_t* dev_area2, uint8_t* dev_border, void* dev_workspace, void* stream) {
+  REQUIRE_ROBUST(e, dev_mask && dev_labels && dev_num && dev_area2 && dev_workspace);
+  CtWorkspace ws;
+  if (!ct_layout(batch, h, w, capacity, &ws)) return fail(e, UNETPP_E_UNSUPPORTED, "contour areas: %dx%dx%d, capacity %d %s", batch, h, w, capacity, CT_SHAPE_TEXT);
+  if (match_class > 255) return fail(e, UNETPP_E_UNSUPPORTED, "match_class %d out of range", match_class);
+  if ((uintptr_t)dev_workspace % 16 || (uintptr_t)dev_labels % 4 || (uintptr_t)dev_num % 4 || (uintptr_t)dev_area2 % 8)
+    return fail(e, UNETPP_E_UNSUPPORTED, "dev_workspace must be 16-byte aligned, dev_labels and dev_num 4-byte, dev_area2 8-byte");
+  const size_t hw = (size_t)h * w, n = hw * batch, n_area = (size_t)batch * capacity * sizeof(unsigned long long);
+  const void* outs[] = {dev_labels, dev_num, dev_area2, dev_border, dev_workspace};
+  const size_t sizes[] = {n * sizeof(int), (size_t)batch * sizeof(int), n_area, dev_border ? n : 0, ws.total};
+  for (int i = 0; i < 5; ++i) {
+    if (!sizes[i]) continue;
+    if (overlaps(outs[i], sizes[i], dev_mask, n)) return fail(e, UNETPP_E_UNSUPPORTED, "contour areas: an output or the workspace overlaps the mask");
+    for (int j = i + 1; j < 5; ++j)
+      if (sizes[j] && overlaps(outs[i], sizes[i], outs[j], sizes[j])) return fail(e, UNETPP_E_UNSUPPORTED, "contour areas: two outputs overlap");
+  }
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  char* base = (char*)dev_workspace;
+  uint8_t* plane = (uint8_t*)(base + ws.plane);
+  uint8_t* inside = (uint8_t*)(base + ws.inside);
+  int* bg_labels = (int*)(base + ws.bg_labels);
+  uint8_t* flags = (uint8_t*)(base + ws.flags);
+  const unsigned flat_blocks = (unsigned)((n + (size_t)CT_THREADS * CT_PX - 1) / ((size_t)CT_THREADS * CT_PX));
+  const dim3 blk(CT_THREADS);
+  HIP_TRY(e, hipMemsetAsync(flags, 0, (hw + 1) * batch, s));
+  HIP_TRY(e, hipMemsetAsync(dev_area2, 0, n_area, s));
+  hipLaunchKernelGGL(ct_background_kernel, dim3(flat_blocks), blk, 0, s, dev_mask, n, match_class, (int)((uintptr_t)dev_mask % 16 == 0), plane);
+  if (int rc = unetpp_components(e, plane, batch, h, w, 1, 4, capacity, bg_labels, (int32_t*)(base + ws.bg_num), nullptr, nullptr, base + ws.cc, stream))
+    return rc;
+  hipLaunchKernelGGL(ct_edge_flags_kernel, dim3((unsigned)((2 * w + 2 * h + CT_THREADS - 1) / CT_THREADS), (unsigned)batch), blk, 0, s,
+                     (const int*)bg_labels, h, w, flags);
+  hipLaunchKernelGGL(ct_inside_kernel, dim3(flat_blocks), blk, 0, s, (const int*)bg_labels, (const uint8_t*)flags, batch, h, w,
+                     (int)((uintptr_t)dev_border % 16 == 0), inside, dev_border);
+  if (int rc = unetpp_components(e, inside, batch, h, w, 1, 8, capacity, dev_labels, dev_num, nullptr, nullptr, base + ws.cc, stream)) return rc;
+  hipLaunchKernelGGL(ct_area_kernel, dim3((unsigned)((w + 1 + CT_THREADS * CT_WIN - 1) / (CT_THREADS * CT_WIN)), (unsigned)(h + 1), (unsigned)batch), blk,
+                     0, s, (const int*)dev_labels, h, w, capacity, (unsigned long long*)dev_area2);
+  return launched(e);
+}
+
+int unetpp_contour_circle(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num, const uint64_t* dev_area2, int batch, int h, int w,
+                          int capacity, int32_t* dev_support, void* dev_workspace, void* stream) {
+  REQUIRE_ROBUST(e, dev_labels && dev_num && dev_area2 && dev_support && dev_workspace);
+  CtWorkspace ws;
+  if (!ct_layout(batch, h, w, capacity, &ws)) return fail(e, UNETPP_E_UNSUPPORTED, "contour circle: %dx%dx%d, capacity %d %s", batch, h, w, capacity, CT_SHAPE_TEXT);
+  if ((uintptr_t)dev_workspace % 16 || (uintptr_t)dev_labels % 4 || (uintptr_t)dev_num % 4 || (uintptr_t)dev_area2 % 8 || (uintptr_t)dev_support % 4)
+    return fail(e, UNETPP_E_UNSUPPORTED, "dev_workspace must be 16-byte aligned, dev_labels, dev_num and dev_support 4-byte, dev_area2 8-byte");
+  const size_t n_support = (size_t)batch * 8 * sizeof(int);
+  if (overlaps(dev_support, n_support, dev_labels, (size_t)batch * h * w * sizeof(int)) || overlaps(dev_support, n_support, dev_num, (size_t)batch * sizeof(int)) ||
+      overlaps(dev_support, n_support, dev_area2, (size_t)batch * capacity * sizeof(unsigned long long)) ||
+      overlaps(dev_support, n_support, dev_workspace, ws.total))
+    return fail(e, UNETPP_E_UNSUPPORTED, "contour circle: dev_support overlaps an input or the workspace");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  unsigned* rows = (unsigned*)((char*)dev_workspace + ws.rows);
+  hipLaunchKernelGGL(ct_choose_kernel, dim3((unsigned)batch), dim3(CT_THREADS), 0, s, (const int*)dev_num, (const unsigned long long*)dev_area2, capacity,
+                     (int*)dev_support);
+  hipLaunchKernelGGL(ct_row_extremes_kernel, dim3((unsigned)h, (unsigned)batch), dim3(64), 0, s, (const int*)dev_labels, (const int*)dev_support, h, w, rows);
+  hipLaunchKernelGGL(ct_circle_kernel, dim3((unsigned)batch), dim3(CT_THREADS), 0, s, (const unsigned*)rows, h, (int*)dev_support);
+  return launched(e);
+}
+
+int unetpp_paste_roi_u8(unetpp_engine* e, const uint8_t* dev_masks, int batch, int h, int w, int roi_x, int roi_y, int roi_w, int roi_h, int out_h,
+                        int out_w, uint8_t* dev_out, void* stream) {
+  REQUIRE_ROBUST(e, dev_masks && dev_out);
+  if (!shape_ok(batch, h, w, MASK_SHAPE) || !shape_ok(batch, out_h, out_w, MASK_SHAPE) || (size_t)batch * out_h * out_w > (1ull << 40))
+    return fail(e, UNETPP_E_UNSUPPORTED, "paste_roi: bad shape %dx%dx%d -> %dx%d", batch, h, w, out_h, out_w);
+  const long long x1 = std::max(0, roi_x), y1 = std::max(0, roi_y);
+  const long long x2 = std::min<long long>(out_w, (long long)roi_x + roi_w), y2 = std::min<long long>(out_h, (long long)roi_y + roi_h);
+  const long long pw = std::min<long long>(w, x2 - x1), ph = std::min<long long>(h, y2 - y1);
+  if (pw < 1 || ph < 1) return fail(e, UNETPP_E_UNSUPPORTED, "paste_roi: roi (%d, %d, %d, %d) misses the %dx%d frame", roi_x, roi_y, roi_w, roi_h, out_h, out_w);
+  const size_t n_in = (size_t)batch * h * w, n_out = (size_t)batch * out_h * out_w;
+  if (overlaps(dev_out, n_out, dev_masks, n_in)) return fail(e, UNETPP_E_UNSUPPORTED, "paste_roi: dev_out overlaps dev_masks");
+  const int pad = (int)((uintptr_t)dev_out % 16);
+  const size_t blocks = (n_out + pad + (size_t)CT_THREADS * CT_PX - 1) / ((size_t)CT_THREADS * CT_PX);
+  if (blocks > 0x7fffffffull) return fail(e, UNETPP_E_UNSUPPORTED, "paste_roi: too many pixels for one launch");
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(ct_paste_kernel, dim3((unsigned)blocks), dim3(CT_THREADS), 0, (hipStream_t)stream, dev_masks, batch, h, w, (int)x1, (int)y1, (int)pw,
+                     (int)ph, out_h, out_w, pad, dev_out);
+  return launched(e);
+}
+
+int unetpp_overlay_chain_u8(unetpp_engine* e, const uint8_t* dev_frames, const uint8_t* dev_cable, const uint8_t* dev_tape, const uint8_t* dev_burr,
+                            int batch, int h, int w, const uint8_t* host_table, uint8_t* dev_out, void* stream) {
+  REQUIRE_ROBUST(e, dev_frames && dev_cable && dev_tape && dev_burr && host_table && dev_out);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_UNSUPPORTED, "overlay chain: bad shape %dx%dx%d", batch, h, w);
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_out, 3 * n, dev_frames, 3 * n) || overlaps(dev_out, 3 * n, dev_cable, n) || overlaps(dev_out, 3 * n, dev_tape, n) ||
+      overlaps(dev_out, 3 * n, dev_burr, n))
+    return fail(e, UNETPP_E_UNSUPPORTED, "overlay chain: dev_out overlaps an input");
+  const int pad = (int)((uintptr_t)dev_out % 16);
+  const size_t blocks = (3 * n + pad + (size_t)CT_THREADS * CT_PX - 1) / ((size_t)CT_THREADS * CT_PX);
+  if (blocks > 0x7fffffffull) return fail(e, UNETPP_E_UNSUPPORTED, "overlay chain: too many pixels for one launch");
+  CtOverlayTable T;
+  std::memcpy(T.w, host_table, sizeof(T.w));
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(ct_overlay_kernel, dim3((unsigned)blocks), dim3(CT_THREADS), 0, (hipStream_t)stream, dev_frames, dev_cable, dev_tape, dev_burr,
+                     (long long)(3 * n), T, pad, (int)((uintptr_t)dev_frames % 16 == (uintptr_t)pad), dev_out);
   return launched(e);
 }
 

@@ -9,6 +9,8 @@ algorithm and are parity-unpinned, see oracle/unetpp_oracle.py).  `measure_frame
 infer_video_v3_high_quality.py, infer_video_optimized.py): quality gate, model, class clean-up, class table, overlay.
 `process_frames_roi` and `process_frames_3class_full` are infer_frame of infer_video_roi.py (:193-259) and of
 infer_video_3class_full.py (:193-261): the two 3-class loops that decide things per frame from the frame itself (roi_loop.py).
+`process_frames_refactored_full` is the whole body of the refactored loop (infer_video_refactored.py:346-405): the head above,
+postprocess_masks, the paste, the two contour diameters, the burr mask, the coverages and the overlay (contours.py).
 """
 from __future__ import annotations
 
@@ -321,3 +323,75 @@ def process_frames_3class_full(model, frames_bgr_u8, *, input_size=512, t_cable=
         _raise_loop_overflow("process_frames_3class_full", (("cable", [int(r[5]) for r in rows]), ("tape", [int(r[6]) for r in rows])), k)
     metrics = [dict(zip(robust.MEASURE_FIELDS, r[:3] + [int(r[3]) / n, int(r[4]) / n])) for r in rows]
     return cable, tape, metrics, pred
+
+
+_REFACTORED_POST = ("min_area", "min_aspect", "max_center_offset", "ring_dilate", "ring_erode")
+_REFACTORED_BURR = ("band_out", "laplacian_threshold", "burr_min_area", "burr_max_area")
+
+
+def process_frames_refactored_full(model, frames_bgr_u8, roi_xywh, input_size=512, *, max_components=8192, device=None, **cfg):
+    """The per-frame body of infer_video_refactored.py (:346-405) for B raw BGR frames of one size at once, every step on the
+    device (contours.py holds the new steps and their NumPy forms):
+      1. process_frames_refactored: preprocess_frame, crop_roi, model_inference (:346-352)
+      2. the class map at the crop's size and postprocess_masks (:355-364; `cfg`: PostprocessConfig's min_area, min_aspect,
+         max_center_offset, ring_dilate, ring_erode; roi_width is the ROI's w)
+      3. paste_roi_mask of both masks into the full frame (:367-371)
+      4. measure_diameter of both: the smallest circle around the largest external contour (:374-375)
+      5. get_burr_mask_rulebased on cvtColor(frame, BGR2GRAY) and the full-frame cable mask (:380-381; `cfg`: BurrConfig's
+         band_out, laplacian_threshold, burr_min_area, burr_max_area)
+      6. the three counts behind has_burr and the two coverages (:382-386)
+      7. the three blends of create_overlay (:191-201)
+      8. ONE read-back: the two support tables, the labellings' num and the three counts per frame
+    Every other keyword of `cfg` goes to process_frames_refactored (enable, threshold, PreprocessConfig's fields).  Returns
+    (metrics: a list of B dicts with FrameMetrics' fields dc_px, dt_px, delta_d_px, ratio (None when dc_px == 0), has_burr,
+    cable_coverage, tape_coverage; overlays uint8 [B,H,W,3]; (mask_cable, mask_tape, mask_burr) uint8 0/255 [B,H,W]), the
+    tensors on the device.  ValueError for a frame with more than max_components labels in a labelling, frames of 4096 or
+    more pixels a side, or a ROI that misses the frame.  The component filters inside steps 2 and 5 run with check=False: a
+    frame with more than max_components - 1 components there gets an empty mask from them, as they document, and no
+    read-back of their own.  EventDetector, putText and the CSV stay on the host."""
+    import torch
+    from . import contours as ct
+    x = frames_bgr_u8
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not x.is_cuda:
+        x = x.to(device if device is not None else f"cuda:{model._device_index or 0}", non_blocking=True)
+    if x.dim() != 4:
+        raise ValueError("frames must be uint8 [B,H,W,3]")
+    b, fh, fw = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+    ct.check_frame_shape(fh, fw)
+    k = ct.check_max_components(max_components)
+    rx, ry, rw, rh = (int(v) for v in roi_xywh)
+    post = {n: cfg.pop(n) for n in _REFACTORED_POST if n in cfg}
+    burr = {n[5:] if n.startswith("burr_") else n: cfg.pop(n) for n in _REFACTORED_BURR if n in cfg}
+    from . import enhance as en
+    x1, y1, x2, y2 = en.roi_bounds(fh, fw, roi_xywh)
+    if x2 <= x1 or y2 <= y1:
+        raise ValueError(f"roi {(rx, ry, rw, rh)} does not meet the {fh}x{fw} frame")
+    pred, _, _ = process_frames_refactored(model, x, roi_xywh, input_size, **cfg)
+    pred_roi = model.resize_masks(pred, (x2 - x1, y2 - y1))
+    cable_roi, tape_roi = model.postprocess_masks(pred_roi, 1, 2, roi_width=rw, max_components=k, check=False, **post)
+    return _refactored_tail(model, x, cable_roi, tape_roi, roi_xywh, k, burr)
+
+
+def _refactored_tail(model, x, cable_roi, tape_roi, roi_xywh, k, burr):
+    """Lines :366-405 for frames uint8 [B,H,W,3] and the two post-processed ROI masks, all on the device: steps 3-8 of
+    process_frames_refactored_full (scripts/contours_bench.py times exactly this)."""
+    import torch
+    from . import contours as ct
+    fh, fw = int(x.shape[1]), int(x.shape[2])
+    cable = ct.paste_roi_masks(model, cable_roi, roi_xywh, (fh, fw))
+    tape = ct.paste_roi_masks(model, tape_roi, roi_xywh, (fh, fw))
+    sup_c, num_c, _ = ct._support(model, cable, -1, k)
+    sup_t, num_t, _ = ct._support(model, tape, -1, k)
+    mask_burr = model.burr_mask_rulebased(model.bgr_to_gray(x), cable, -1, max_components=k, check=False, **burr)
+    counts = torch.stack((model.count_nonzero(cable), model.count_nonzero(tape), model.count_nonzero(mask_burr), num_c, num_t), dim=1)
+    overlays = ct.create_overlay_masks(model, x, cable, tape, mask_burr)
+    rows = torch.cat((sup_c, sup_t, counts), dim=1).cpu().numpy()                              # the read-back: 21 B integers
+    ct._raise_contour_overflow("process_frames_refactored_full", (("cable", rows[:, 19].tolist()), ("tape", rows[:, 20].tolist())), k)
+    metrics = []
+    for (_, rc), (_, rt), r in zip(ct.circle_from_support(rows[:, 0:8]), ct.circle_from_support(rows[:, 8:16]), rows):
+        dc, dt = 2.0 * rc, 2.0 * rt
+        metrics.append({"dc_px": dc, "dt_px": dt, "delta_d_px": dt - dc, "ratio": dt / dc if dc > 0 else None, "has_burr": bool(r[18] > 0),
+                        "cable_coverage": int(r[16]) / (fw * fh), "tape_coverage": int(r[17]) / (fw * fh)})
+    return metrics, overlays, (cable, tape, mask_burr)

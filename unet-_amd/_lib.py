@@ -14,9 +14,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunetpp_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["unetpp_abi.hip", "unetpp_postproc.hip"]      # the engine; the post-processing entry points
-HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "frame_kernels.h", "components.h", "distance.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "nlmeans.h", "evaluation.h", "probmap.h", "multiclass.h", "geometry.h", "tiling.h", "roi_loop.h", "loss.h", "contours.h", os.path.join("..", "..", "include", "unetpp.h"),
+HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "convt2x2_mfma.h", "aux_kernels.h", "frame_kernels.h", "components.h", "distance.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "nlmeans.h", "evaluation.h", "probmap.h", "multiclass.h", "geometry.h", "tiling.h", "roi_loop.h", "loss.h", "contours.h", "simple_loops.h", os.path.join("..", "..", "include", "unetpp.h"),
            os.path.join("..", "..", "include", "unetpp_roi.h"), os.path.join("..", "..", "include", "unetpp_loss.h"),
-           os.path.join("..", "..", "include", "unetpp_contours.h")]
+           os.path.join("..", "..", "include", "unetpp_contours.h"), os.path.join("..", "..", "include", "unetpp_simple_loops.h")]
 
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
 PREC_EXACT, PREC_FAST, PREC_EXACT8 = 0, 1, 2
@@ -206,6 +206,17 @@ ABI_CONTOURS = {
     "unetpp_overlay_chain_u8": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, u8p, vp, vp]),
 }
 
+PIXEL_RULES = {"relative": 0, "confidence": 1}     # UNETPP_PIXEL_*
+
+# every symbol include/unetpp_simple_loops.h declares; load() applies all five tables
+ABI_SIMPLE_LOOPS = {
+    "unetpp_pixel_rules_f32": (ci, [vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, vp, vp]),
+    "unetpp_components_keep": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ctypes.c_uint8, vp, vp, vp]),
+    "unetpp_tape_position_filter_u8": (ci, [vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp]),
+    "unetpp_column_band_u8": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp]),
+    "unetpp_mask_join_u8": (ci, [vp, vp, ci, vp, ci, vp, ci, ci, ci, ci, vp, vp]),
+}
+
 # -fno-slp-vectorize: the SLP vectoriser turns pairs of float operations into v_pk_mul_f32 / v_pk_fma_f32, and a packed
 # fp32 instruction issued beside another wave's MFMA stream on the same SIMD takes 26-58 cycles instead of 5-7
 # (scripts/microbench/valu_beside_mfma.hip) -- the loader waves of the wave-specialised kernels run exactly there.
@@ -300,7 +311,8 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
             raise RuntimeError(f"{LIB_PATH} {what}: build it with __graft_entry__.build(); there is no CPU fallback")
         build()
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_ROI.items()) + list(ABI_LOSS.items()) + list(ABI_CONTOURS.items()):
+    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_ROI.items()) + list(ABI_LOSS.items()) + list(ABI_CONTOURS.items()) + list(
+            ABI_SIMPLE_LOOPS.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     ver = lib.unetpp_version().decode()

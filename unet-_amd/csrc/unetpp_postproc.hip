@@ -16,6 +16,7 @@
 #include "../../include/unetpp_contours.h"
 #include "../../include/unetpp_loss.h"
 #include "../../include/unetpp_roi.h"
+#include "../../include/unetpp_simple_loops.h"
 #include "abi_common.h"
 #include "components.h"
 #include "contours.h"
@@ -32,6 +33,7 @@
 #include "nlmeans.h"
 #include "probmap.h"
 #include "roi_loop.h"
+#include "simple_loops.h"
 #include "tiling.h"
 
 using namespace unetpp;
@@ -1701,6 +1703,104 @@ int unetpp_overlay_chain_u8(unetpp_engine* e, const uint8_t* dev_frames, const u
   ENTER_DEVICE(e);
   hipLaunchKernelGGL(ct_overlay_kernel, dim3((unsigned)blocks), dim3(CT_THREADS), 0, (hipStream_t)stream, dev_frames, dev_cable, dev_tape, dev_burr,
                      (long long)(3 * n), T, pad, (int)((uintptr_t)dev_frames % 16 == (uintptr_t)pad), dev_out);
+  return launched(e);
+}
+
+// ---- the pixel and component rules of the spatial, fixed and simple loops (simple_loops.h, include/unetpp_simple_loops.h) ------------
+int unetpp_pixel_rules_f32(unetpp_engine* e, const float* dev_probs, int64_t frame_stride, int64_t plane_stride, int64_t pixel_stride, int batch, int h,
+                           int w, int rule, float a, float b, uint8_t* dev_cable, uint8_t* dev_tape, void* stream) {
+  REQUIRE_ROBUST(e, dev_probs && dev_cable && dev_tape);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_UNSUPPORTED, "pixel rules: shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  if (rule != UNETPP_PIXEL_RELATIVE && rule != UNETPP_PIXEL_CONFIDENCE) return fail(e, UNETPP_E_UNSUPPORTED, "pixel rules: unknown rule %d", rule);
+  if (std::isnan(a) || std::isnan(b)) return fail(e, UNETPP_E_UNSUPPORTED, "pixel rules: NaN parameter");
+  const long long hw = (long long)h * w;
+  const long long lim = 1ll << 40;                           // keeps every product below inside int64
+  if (frame_stride < 1 || plane_stride < 1 || pixel_stride < 1 || frame_stride > lim || plane_stride > lim || pixel_stride > (1 << 20) ||
+      2 * plane_stride + (hw - 1) * pixel_stride + 1 > frame_stride)
+    return fail(e, UNETPP_E_UNSUPPORTED, "pixel rules: strides (%lld, %lld, %lld) do not hold three planes of %lld pixels in one frame",
+                (long long)frame_stride, (long long)plane_stride, (long long)pixel_stride, hw);
+  if ((uintptr_t)dev_probs % 4) return fail(e, UNETPP_E_UNSUPPORTED, "pixel rules: dev_probs must be 4-byte aligned");
+  const size_t n = (size_t)batch * hw, np_ = (size_t)batch * (size_t)frame_stride * sizeof(float);
+  if (overlaps(dev_cable, n, dev_tape, n) || overlaps(dev_probs, np_, dev_cable, n) || overlaps(dev_probs, np_, dev_tape, n))
+    return fail(e, UNETPP_E_UNSUPPORTED, "pixel rules: the masks overlap each other or dev_probs");
+  ENTER_DEVICE(e);
+  const long long span = (long long)SL_THREADS * SL_PX;
+  hipLaunchKernelGGL(sl_pixel_rules_kernel, dim3((unsigned)((hw + span - 1) / span), (unsigned)batch), dim3(SL_THREADS), 0, (hipStream_t)stream, dev_probs,
+                     (long long)frame_stride, (long long)plane_stride, (long long)pixel_stride, hw, rule, a, b, dev_cable, dev_tape);
+  return launched(e);
+}
+
+int unetpp_components_keep(unetpp_engine* e, const int32_t* dev_labels, const int32_t* dev_num, const int32_t* dev_stats, int batch, int h, int w,
+                           int capacity, int min_area, int max_area, int min_width, uint8_t out_value, uint8_t* dev_out, void* dev_workspace,
+                           void* stream) {
+  REQUIRE_ROBUST(e, dev_labels && dev_num && dev_stats && dev_out && dev_workspace);
+  CcWorkspace ws;
+  if (capacity < 2 || !cc_layout(batch, h, w, capacity, &ws))
+    return fail(e, UNETPP_E_UNSUPPORTED, "components keep: bad shape %dx%dx%d or capacity %d", batch, h, w, capacity);
+  if (out_value == 0) return fail(e, UNETPP_E_UNSUPPORTED, "out_value must not be 0");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  const int hw = h * w;
+  uint8_t* keep = (uint8_t*)dev_workspace + ws.keep;
+  hipLaunchKernelGGL(sl_keep_select_kernel, dim3((unsigned)batch), dim3(SL_THREADS), 0, s, (const int*)dev_num, (const int*)dev_stats, capacity, min_area,
+                     max_area, min_width, keep);
+  hipLaunchKernelGGL(cc_apply_kernel, dim3((unsigned)ws.nchunk, (unsigned)batch), dim3(CC_THREADS), 0, s, (const int*)dev_labels,
+                     (const uint8_t*)keep, hw, capacity, vec16(hw, dev_labels, dev_out), (unsigned)out_value, dev_out);
+  return launched(e);
+}
+
+int unetpp_tape_position_filter_u8(unetpp_engine* e, const uint8_t* dev_tape, int tape_match, const uint8_t* dev_cable, int cable_match, int batch,
+                                   int h, int w, uint8_t* dev_out, int32_t* dev_table, void* stream) {
+  REQUIRE_ROBUST(e, dev_tape && dev_cable && dev_out && dev_table);
+  if (tape_match > 255 || cable_match > 255) return fail(e, UNETPP_E_UNSUPPORTED, "tape filter: match value out of range");
+  if (!shape_ok(batch, h, w, MASK_SHAPE) || (size_t)h * w > (size_t)UNETPP_TAPE_MAX_PIXELS)
+    return fail(e, UNETPP_E_UNSUPPORTED, "tape filter: shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^23", batch, h, w);
+  if ((uintptr_t)dev_table % 4) return fail(e, UNETPP_E_UNSUPPORTED, "tape filter: dev_table must be 4-byte aligned");
+  const size_t n = (size_t)batch * h * w, nt = (size_t)batch * SL_TABLE * sizeof(int32_t);
+  if (overlaps(dev_out, n, dev_tape, n) || (dev_cable != dev_tape && overlaps(dev_out, n, dev_cable, n)) || overlaps(dev_table, nt, dev_out, n) ||
+      overlaps(dev_table, nt, dev_tape, n) || overlaps(dev_table, nt, dev_cable, n))
+    return fail(e, UNETPP_E_UNSUPPORTED, "tape filter: dev_out or dev_table overlaps another buffer");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  int* table = (int*)dev_table;
+  HIP_TRY(e, hipMemsetAsync(table, 0, nt, s));
+  const dim3 rows((unsigned)((h + SL_THREADS / SL_WAVE - 1) / (SL_THREADS / SL_WAVE)), (unsigned)batch);
+  hipLaunchKernelGGL(sl_tape_sums_kernel, rows, dim3(SL_THREADS), 0, s, dev_tape, tape_match, dev_cable, cable_match, h, w, table);
+  hipLaunchKernelGGL(sl_tape_filtered_kernel, rows, dim3(SL_THREADS), 0, s, dev_tape, tape_match, h, w, table);
+  hipLaunchKernelGGL(sl_tape_finish_kernel, dim3((unsigned)((batch + SL_THREADS - 1) / SL_THREADS)), dim3(SL_THREADS), 0, s, batch, w, table);
+  const int vec = w % 4 == 0 && ((uintptr_t)dev_tape | (uintptr_t)dev_out) % 4 == 0;
+  hipLaunchKernelGGL(sl_tape_apply_kernel, dim3((unsigned)((w + 4 * SL_THREADS - 1) / (4 * SL_THREADS)), (unsigned)h, (unsigned)batch), dim3(SL_THREADS), 0,
+                     s, dev_tape, tape_match, (const int*)table, h, w, vec, dev_out);
+  return launched(e);
+}
+
+int unetpp_column_band_u8(unetpp_engine* e, const uint8_t* dev_mask, int batch, int h, int w, int x_start, int x_end, uint8_t* dev_out, void* stream) {
+  REQUIRE_ROBUST(e, dev_mask && dev_out);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_UNSUPPORTED, "column band: shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  if (x_start < 0 || x_start > w || x_end < 0 || x_end > w) return fail(e, UNETPP_E_UNSUPPORTED, "column band: columns [%d, %d) outside 0..%d", x_start, x_end, w);
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_mask, n, dev_out, n)) return fail(e, UNETPP_E_UNSUPPORTED, "column band: dev_out overlaps dev_mask");
+  ENTER_DEVICE(e);
+  const int vec = w % 4 == 0 && ((uintptr_t)dev_mask | (uintptr_t)dev_out) % 4 == 0;
+  hipLaunchKernelGGL(sl_column_band_kernel, dim3((unsigned)((w + 4 * SL_THREADS - 1) / (4 * SL_THREADS)), (unsigned)h, (unsigned)batch), dim3(SL_THREADS), 0,
+                     (hipStream_t)stream, dev_mask, h, w, x_start, x_end, vec, dev_out);
+  return launched(e);
+}
+
+int unetpp_mask_join_u8(unetpp_engine* e, const uint8_t* dev_a, int and_a, const uint8_t* dev_b, int or_b, const uint8_t* dev_c, int or_c, int batch,
+                        int h, int w, uint8_t* dev_out, void* stream) {
+  REQUIRE_ROBUST(e, dev_a && dev_out);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_UNSUPPORTED, "mask join: shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  if (and_a < 0 || and_a > 255 || or_b < 0 || or_b > 255 || or_c < 0 || or_c > 255) return fail(e, UNETPP_E_UNSUPPORTED, "mask join: a bit mask outside 0..255");
+  const size_t n = (size_t)batch * h * w;
+  if (overlaps(dev_out, n, dev_a, n) || (dev_b && overlaps(dev_out, n, dev_b, n)) || (dev_c && overlaps(dev_out, n, dev_c, n)))
+    return fail(e, UNETPP_E_UNSUPPORTED, "mask join: dev_out overlaps an input");
+  const size_t blocks = (n + 4 * (size_t)SL_THREADS - 1) / (4 * (size_t)SL_THREADS);
+  if (blocks > 0x7fffffffull) return fail(e, UNETPP_E_UNSUPPORTED, "mask join: too many pixels for one launch");
+  ENTER_DEVICE(e);
+  const int vec = n % 4 == 0 && ((uintptr_t)dev_a | (uintptr_t)dev_b | (uintptr_t)dev_c | (uintptr_t)dev_out) % 4 == 0;
+  hipLaunchKernelGGL(sl_join_kernel, dim3((unsigned)blocks), dim3(SL_THREADS), 0, (hipStream_t)stream, dev_a, (unsigned)and_a, dev_b, (unsigned)or_b, dev_c,
+                     (unsigned)or_c, (long long)n, vec, dev_out);
   return launched(e);
 }
 

@@ -11,6 +11,9 @@ infer_video_v3_high_quality.py, infer_video_optimized.py): quality gate, model, 
 infer_video_3class_full.py (:193-261): the two 3-class loops that decide things per frame from the frame itself (roi_loop.py).
 `process_frames_refactored_full` is the whole body of the refactored loop (infer_video_refactored.py:346-405): the head above,
 postprocess_masks, the paste, the two contour diameters, the burr mask, the coverages and the overlay (contours.py).
+`process_frames_spatial`, `process_frames_fixed`, `process_frames_confidence` and `process_frames_simple` are infer_frame of
+infer_video_spatial.py, infer_video_fixed.py, infer_video_simple_v2.py and predict of infer_video_simple.py,
+infer_video_simple_optimized.py and infer_video_simple_backup.py (simple_loops.py holds their steps and NumPy forms).
 """
 from __future__ import annotations
 
@@ -395,3 +398,125 @@ def _refactored_tail(model, x, cable_roi, tape_roi, roi_xywh, k, burr):
         metrics.append({"dc_px": dc, "dt_px": dt, "delta_d_px": dt - dc, "ratio": dt / dc if dc > 0 else None, "has_burr": bool(r[18] > 0),
                         "cable_coverage": int(r[16]) / (fw * fh), "tape_coverage": int(r[17]) / (fw * fh)})
     return metrics, overlays, (cable, tape, mask_burr)
+
+
+def _device_frames(model, frames_bgr_u8, device):
+    import torch
+    x = frames_bgr_u8
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if not x.is_cuda:
+        x = x.to(device if device is not None else f"cuda:{model._device_index or 0}", non_blocking=True)
+    return x
+
+
+def _resized(model, x, size):
+    return x if (int(x.shape[1]), int(x.shape[2])) == (size, size) else model.resize_frames(x, (size, size))
+
+
+def process_frames_spatial(model, frames_bgr_u8, *, input_size=512, cable_bg_ratio=2.0, tape_bg_ratio=2.5, max_components=8192, device=None):
+    """infer_frame of infer_video_spatial.py (:123-171) for B raw BGR frames of one size at once, every step on the device
+    (simple_loops.py holds the new steps and their NumPy forms): resize_frames to input_size, predict_proba,
+    relative_threshold, spatial_filter with 30 / 200 on the cable and 20 / 150 on the tape (filter_components,
+    rule="spatial"), the focus band (column_band), resize_masks to the frame size, the coverages of the masks at model size.
+    Returns (mask_cable, mask_tape uint8 0/1 [B,H,W], metrics: a list of B dicts with cable_coverage and tape_coverage, probs
+    float32 [B,C,input_size,input_size]), the tensors on the device; the two counts and the labellings' num are the one
+    read-back."""
+    import torch
+    from . import simple_loops as sl
+    x = _device_frames(model, frames_bgr_u8, device)
+    fh, fw = int(x.shape[1]), int(x.shape[2])
+    k, size = int(max_components), int(input_size)
+    probs = model.predict_proba(_resized(model, x, size))
+    cable_s, tape_s = sl.relative_threshold(model, probs, cable_bg_ratio, tape_bg_ratio)
+    cable_s, num_c = sl._filter_spatial(model, cable_s, 30, 200, k)
+    tape_s, num_t = sl._filter_spatial(model, tape_s, 20, 150, k)
+    cable_s, tape_s = sl.column_band(model, cable_s), sl.column_band(model, tape_s)
+    cable, tape = model.resize_masks(cable_s, (fw, fh)), model.resize_masks(tape_s, (fw, fh))
+    rows = torch.stack((model.count_nonzero(cable_s), model.count_nonzero(tape_s), num_c, num_t), dim=1).cpu().tolist()   # the read-back
+    _raise_loop_overflow("process_frames_spatial", (("cable", [r[2] for r in rows]), ("tape", [r[3] for r in rows])), k)
+    metrics = [{"cable_coverage": r[0] / (size * size), "tape_coverage": r[1] / (size * size)} for r in rows]
+    return cable, tape, metrics, probs
+
+
+def _measured_tail(model, what, cable_s, tape_s, frame_hw, nums, k):
+    """The common end of infer_frame in infer_video_fixed.py (:210-234) and infer_video_simple_v2.py (:135-159): the masks
+    resized to the frame, measure_diameters_simple and the coverages at model size, pred_mask; one read-back."""
+    import torch
+    from . import robust
+    fh, fw = frame_hw
+    n = int(cable_s.shape[1]) * int(cable_s.shape[2])
+    cable, tape = model.resize_masks(cable_s, (fw, fh)), model.resize_masks(tape_s, (fw, fh))
+    table = robust._measure_table(model, cable_s, tape_s)
+    pred = torch.where(tape_s > 0, torch.full_like(tape_s, 2), cable_s)   # pred_mask[cable > 0] = 1, then [tape > 0] = 2
+    if nums:
+        table = torch.cat((table, torch.stack(nums, dim=1).to(torch.float64)), dim=1)
+    rows = table.cpu().tolist()                                            # the read-back
+    if nums:
+        _raise_loop_overflow(what, (("cable", [int(r[5]) for r in rows]), ("tape", [int(r[6]) for r in rows])), k)
+    metrics = [dict(zip(robust.MEASURE_FIELDS, r[:3] + [int(r[3]) / n, int(r[4]) / n])) for r in rows]
+    return cable, tape, metrics, pred
+
+
+def process_frames_fixed(model, frames_bgr_u8, *, input_size=512, conf_cable=0.6, conf_tape=0.65, bg_margin=0.4, min_area_cable=3000,
+                         min_area_tape=1500, max_area_cable=100000, max_area_tape=80000, max_components=8192, device=None):
+    """infer_frame of infer_video_fixed.py (:168-234) for B raw BGR frames of one size at once, every step on the device:
+    resize_frames to input_size, segment_thresholded(rule="strict_bg_check"), filter_by_size_and_shape on both masks
+    (simple_loops.keep_components), resize_masks to the frame size, measure_diameters_simple and the coverages at model size.
+    Returns (mask_cable, mask_tape uint8 0/1 [B,H,W], metrics: a list of B dicts of robust.MEASURE_FIELDS, pred uint8
+    [B,input_size,input_size] with cable 1 and tape 2); the metrics and the labellings' num are the one read-back."""
+    from . import simple_loops as sl
+    x = _device_frames(model, frames_bgr_u8, device)
+    k, size = int(max_components), int(input_size)
+    cable_s, tape_s = model.segment_thresholded(_resized(model, x, size), "strict_bg_check", conf_cable, conf_tape, bg_margin)
+    cable_s, num_c, _ = sl._keep(model, cable_s, min_area_cable, max_area_cable, 0, -1, 1, k)
+    tape_s, num_t, _ = sl._keep(model, tape_s, min_area_tape, max_area_tape, 0, -1, 1, k)
+    return _measured_tail(model, "process_frames_fixed", cable_s, tape_s, (int(x.shape[1]), int(x.shape[2])), [num_c, num_t], k)
+
+
+def process_frames_confidence(model, frames_bgr_u8, *, input_size=512, conf_threshold=0.3, device=None):
+    """infer_frame of infer_video_simple_v2.py (:110-159) for B raw BGR frames of one size at once, every step on the device:
+    resize_frames to input_size, predict_proba, simple_threshold (simple_loops.confidence_threshold), no filter, then the tail
+    of process_frames_fixed.  Returns (mask_cable, mask_tape, metrics, pred, probs float32 [B,C,input_size,input_size])."""
+    from . import simple_loops as sl
+    x = _device_frames(model, frames_bgr_u8, device)
+    probs = model.predict_proba(_resized(model, x, int(input_size)))
+    cable_s, tape_s = sl.confidence_threshold(model, probs, conf_threshold)
+    return _measured_tail(model, "process_frames_confidence", cable_s, tape_s, (int(x.shape[1]), int(x.shape[2])), [], 0) + (probs,)
+
+
+def process_frames_simple(model, frames_bgr_u8, variant="simple", input_size=256, colors=None, alpha=0.5, *, want_table=True, max_components=8192,
+                          device=None, **tape):
+    """SimpleInference.predict of infer_video_simple.py (variant "simple", :81-154), infer_video_simple_optimized.py
+    ("optimized", :139-234) and infer_video_simple_backup.py ("backup", :61-88) for B raw BGR frames of one size at once on a
+    SimpleUNet (or any 7-class model), every step on the device: resize_frames to input_size (256 in the first two scripts),
+    then predict_proba and simple_loops.predict_simple (`tape`: its min_tape_area, min_tape_width, min_burr_area), or for
+    "backup" segment, resize_masks and simple_loops.predict_simple_backup.  With `colors` ({class: (b, g, r)}) the region blend
+    of overlay_mask follows (multiclass.overlay, mode="region"); its drawContours stays on the host.  Returns (map uint8 [B,H,W]
+    at frame size, table int32 [B,256,5] or None, overlays uint8 [B,H,W,3] or None), all on the device; the only
+    synchronisation is the overflow check of the labellings' num after the last launch ("backup" labels nothing and
+    never synchronises)."""
+    from . import multiclass as mc
+    from . import simple_loops as sl
+    if variant not in ("simple", "optimized", "backup"):
+        raise ValueError(f"variant must be 'simple', 'optimized' or 'backup', got {variant!r}")
+    x = _device_frames(model, frames_bgr_u8, device)
+    fh, fw = int(x.shape[1]), int(x.shape[2])
+    resized = _resized(model, x, int(input_size))
+    num = None
+    if variant == "backup":
+        if tape:
+            raise ValueError(f"variant 'backup' takes no filter constants, got {sorted(tape)}")
+        res = sl.predict_simple_backup(model, model.resize_masks(model.segment(resized), (fw, fh)), want_table=want_table)
+        out, table = res if want_table else (res, None)
+    else:
+        kw = dict(min_tape_area=500, min_tape_width=20, min_burr_area=100)
+        if set(tape) - set(kw):
+            raise ValueError(f"unknown filter constants {sorted(set(tape) - set(kw))}")
+        kw.update(tape)
+        out, table, _, num, k = sl._predict_simple(model, model.predict_proba(resized), (fh, fw), variant, kw["min_tape_area"], kw["min_tape_width"],
+                                                   kw["min_burr_area"], want_table, max_components)
+    over = None if colors is None else mc.overlay(model, x, out, colors, alpha, "region", model.num_classes)
+    if num is not None:
+        model._raise_num_overflow(num, k)                                     # the read-back, after the last launch
+    return out, table, over

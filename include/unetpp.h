@@ -91,7 +91,18 @@ typedef struct unetpp_config {
 } unetpp_config;
 
 /* NestedUNet.__init__ + .to(device) (src/models/unetpp.py:40-91, infer_two_stage_burr.py:214):
- * allocates the activation workspace for (micro_batch, max_h, max_w) on cfg->device. */
+ * allocates the activation workspace for (micro_batch, max_h, max_w) on cfg->device.
+ *
+ * Environment switches, read once here (an engine keeps the plan it was created with):
+ *   UNETPP_KSPLIT=max[,min chunks[,gate]]  split-K of small launches (default 16,4,4; 1 = off)
+ *   UNETPP_TAPMM=levels                    decoder levels that take the low-resolution GEMM (default "23"; "none" = off)
+ *   UNETPP_UPROWS=levels                   decoder levels whose up chunks run on low-resolution rows (default "01")
+ *   UNETPP_PLAN_CUS=n                      plan every launch (grid sizes, split-K, tile heights, up-sum tiles) for n compute
+ *                                          units instead of the device's own count: a test and diagnosis aid that makes the
+ *                                          persistent workgroups walk several tiles each at small shapes.  Results depend on
+ *                                          it only through the split-K summation order.  n must be a whole number with
+ *                                          1 <= n <= the device's count (launches only ever get smaller), else
+ *                                          UNETPP_E_INVALID; a malformed value is refused before the device is looked at. */
 int unetpp_create(const unetpp_config* cfg, unetpp_engine** out);
 
 /* del model */
@@ -441,6 +452,9 @@ int unetpp_profile_read(unetpp_engine* e, float* ms_out, int n);
 const char* unetpp_profile_name(const unetpp_engine* e, int i);
 /* algorithmic FLOPs and minimum HBM bytes (read+write) of launch i for the last forward's shape */
 int unetpp_profile_work(const unetpp_engine* e, int i, double* flops, double* bytes);
+/* the launch plan of launch i: out = {grid (workgroups), tiles (split-K shares counted), ksplit, rows per wave}; all 0 for a
+ * launch that is not persistent (one workgroup per tile), rows per wave 0 for the low-resolution GEMM */
+int unetpp_profile_plan(const unetpp_engine* e, int i, int out[4]);
 
 /* ---- debug (layer-by-layer parity tests) -------------------------------------------------------
  * Copies the named activation of the LAST micro-batch processed ("x0_0", "x1_0", ..., "x0_4"; also a block's first conv

@@ -78,6 +78,7 @@ SIGNATURES = {
     'preprocess_frames': ("(self, frames, enable: 'bool' = True, threshold: 'float' = 10.0, *, clip_limit: 'float' = 2.0, tile_grid=8, gamma: "
         "'float' = 0.8, denoise_method: 'str' = 'bilateral', denoise_strength: 'int' = 5, return_decisions: 'bool' = False)"),
     'profile': "(self, on: 'bool' = True)",
+    'profile_plan': '(self)',
     'profile_read': '(self)',
     'raise_on_range_error': '(self)',
     'resize_frames': '(self, frames, size_hw)',
@@ -108,7 +109,7 @@ def public(cls):
 
 def test_public_methods_and_signatures_are_unchanged():
     from unet_amd.nested_unet import NestedUNet, SimpleUNet
-    assert len(SIGNATURES) == 60
+    assert len(SIGNATURES) == 61
     assert {n: str(inspect.signature(getattr(NestedUNet, n))) for n in public(NestedUNet)} == SIGNATURES
     assert public(SimpleUNet) == sorted(SIGNATURES)
 

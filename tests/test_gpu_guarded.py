@@ -51,6 +51,7 @@ EXCLUDED = {
     "unetpp_load_weights": "load: writes the engine's own weights", "unetpp_load_weights_device": "load: reads a device blob, writes the engine's own weights",
     "unetpp_workspace_bytes": "size query", "unetpp_status": "status", "unetpp_profile_enable": "profile", "unetpp_profile_count": "profile",
     "unetpp_profile_read": "profile: host buffer", "unetpp_profile_name": "profile", "unetpp_profile_work": "profile",
+    "unetpp_profile_plan": "profile: host buffer",
     "unetpp_debug_read": "debug: host buffer", "unetpp_debug_keep_intermediates": "debug", "unetpp_ds_blob_bytes": "size query",
     "unetpp_load_ds_heads": "load: writes the engine's own heads", "unetpp_components_workspace_bytes": "size query",
     "unetpp_morphology_layout": "layout query", "unetpp_canny_workspace_bytes": "size query", "unetpp_canny_layout": "layout query",

@@ -108,6 +108,7 @@ ABI = {
     "unetpp_profile_read": (ci, [vp, f32p, ci]),
     "unetpp_profile_name": (ctypes.c_char_p, [vp, ci]),
     "unetpp_profile_work": (ci, [vp, ci, ctypes.POINTER(cd), ctypes.POINTER(cd)]),
+    "unetpp_profile_plan": (ci, [vp, ci, ctypes.POINTER(ci)]),
     "unetpp_debug_read": (ctypes.c_longlong, [vp, ctypes.c_char_p, f32p, cs]),
     "unetpp_debug_keep_intermediates": (ci, [vp, ci]),
     "unetpp_ds_blob_bytes": (cs, [ci]),

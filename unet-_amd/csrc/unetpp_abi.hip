@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -102,6 +103,7 @@ struct ProfRec {
   double flops = 0, bytes = 0;
   int ev0 = -1, ev1 = -1;   // indices into the engine's event pool: launches on one stream are back to
                             // back, so a launch's start event is the previous launch's end event
+  int plan[4] = {0, 0, 0, 0};   // persistent launches: grid, tiles (split shares counted), ksplit, rows per wave (unetpp_profile_plan)
 };
 
 }  // namespace
@@ -217,7 +219,11 @@ size_t blob_payload_floats(int arch, int C, int cin, int* n_layers = nullptr) {
 }
 
 // ---- conv dispatch ---------------------------------------------------------------------------
-struct LaunchCtx { int device; int num_cus; int ksplit_max = 1, ksplit_min_chunks = 4, ksplit_gate = 4; };   // per engine: one process may drive engines on several devices
+struct LaunchCtx {      // per engine: one process may drive engines on several devices
+  int device; int num_cus; int ksplit_max = 1, ksplit_min_chunks = 4, ksplit_gate = 4;
+  int* plan = nullptr;      // profiling on: the launch's ProfRec::plan, else null
+  void report(int grid, int tiles, int ks, int rows) const { if (plan) { plan[0] = grid; plan[1] = tiles; plan[2] = ks; plan[3] = rows; } }
+};
 
 template <int P, int KC, int NW, int MW, int WAVES, bool POOL, bool HEAD, bool UPF = false>
 hipError_t launch_conv_k(const LaunchCtx& cx, const ConvArgs& a, hipStream_t s) {
@@ -227,6 +233,7 @@ hipError_t launch_conv_k(const LaunchCtx& cx, const ConvArgs& a, hipStream_t s) 
   const int total = a.N * a.tiles_x * a.tiles_y * a.nct;
   const int per_cu = std::max(1, std::min(2, (160 * 1024) / lds));
   dim3 grid((unsigned)std::min(total, cx.num_cus * per_cu));
+  cx.report((int)grid.x, total, 1, MW);
   auto k = conv3x3_bias_relu_kernel<P, KC, NW, MW, WAVES, POOL, HEAD, UPF>;
   hipError_t st = allow_full_lds((const void*)k, cx.device);
   if (st != hipSuccess) return st;
@@ -253,6 +260,7 @@ hipError_t launch_ws_k(const LaunchCtx& cx, ConvArgs a, hipStream_t s, bool upro
   a.ksplit = ks;
   const int total = tiles * ks;
   dim3 grid((unsigned)std::min(total, cx.num_cus));
+  cx.report((int)grid.x, total, ks, MW);
   {      // the grid size in the kernel's tile-number radix (its workgroups step through the tiles by G)
     int t = (int)grid.x;
     a.gdec[0] = t % ks; t /= ks;
@@ -369,6 +377,7 @@ struct Launcher {
   unetpp_engine* e;
   hipStream_t s;
   int rc = UNETPP_OK;
+  int* plan = nullptr;      // inside run(), profiling on: where the launch writes its plan (LaunchCtx::plan)
   template <class F>
   void run(const std::string& name, double flops, double bytes, F&& f) {
     if (rc) return;
@@ -386,6 +395,7 @@ struct Launcher {
       if ((size_t)e->prof_used >= e->prof.size()) e->prof.push_back(ProfRec());
       r = &e->prof[e->prof_used++];
       r->name = name; r->flops = flops; r->bytes = bytes;
+      std::fill(r->plan, r->plan + 4, 0);
       if (e->prof_prev_ev >= 0 && e->prof_prev_stream == s) {
         r->ev0 = e->prof_prev_ev;
       } else {
@@ -394,7 +404,9 @@ struct Launcher {
         (void)hipEventRecord(e->evpool[r->ev0], s);
       }
     }
+    plan = r ? r->plan : nullptr;
     hipError_t st = f();
+    plan = nullptr;
     if (st == hipSuccess) st = hipGetLastError();
     if (r) {
       r->ev1 = new_event();
@@ -611,6 +623,16 @@ int unetpp_create(const unetpp_config* cfg, unetpp_engine** out) {
   // full-resolution tensor has 64 channels x (1 or 2) fp16 planes
   if ((double)cfg->max_h * cfg->max_w * 64 * 2 * (cfg->precision == UNETPP_PREC_FAST ? 1 : 2) >= 2147483648.0)
     return fail(nullptr, UNETPP_E_UNSUPPORTED, "max shape %dx%d too large for 32-bit tensor offsets", cfg->max_h, cfg->max_w);
+  // UNETPP_PLAN_CUS=n: plan every launch for n compute units instead of the device's own count (include/unetpp.h)
+  int plan_cus = 0;
+  if (const char* pc = getenv("UNETPP_PLAN_CUS")) {
+    char* end = nullptr;
+    errno = 0;
+    const long v = strtol(pc, &end, 10);
+    if (end == pc || *end != '\0' || errno != 0 || v < 1 || v > (1 << 20))
+      return fail(nullptr, UNETPP_E_INVALID, "UNETPP_PLAN_CUS='%s': a whole number of compute units >= 1 required", pc);
+    plan_cus = (int)v;
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(nullptr, UNETPP_E_HIP, "no HIP device available: this engine has no CPU fallback");
@@ -622,6 +644,14 @@ int unetpp_create(const unetpp_config* cfg, unetpp_engine** out) {
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) e->num_cus = prop.multiProcessorCount;
+  }
+  if (plan_cus > 0) {      // only ever smaller launches than the device's own plan: never a grid that is not resident at once
+    if (plan_cus > e->num_cus) {
+      const int have = e->num_cus;
+      delete e;
+      return fail(nullptr, UNETPP_E_INVALID, "UNETPP_PLAN_CUS=%d exceeds the device's %d compute units", plan_cus, have);
+    }
+    e->num_cus = plan_cus;
   }
   e->cfg = *cfg;
   e->P = cfg->precision == UNETPP_PREC_FAST ? 1 : 2;
@@ -1032,8 +1062,8 @@ static int forward_impl(unetpp_engine* e, const void* dev_input, int in_format, 
         else if (L.ws) snprintf(lbl, sizeof lbl, "%s%s%s%s|conv3x3_ws_kernel<%d, %s, %s, %s, %s, %d, %d, %s, %s>", L.c0f ? "input+conv0_0.conv1+" : "", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "", P, tf(L.do_pool), tf(head), tf(L.upf), tf(L.c0f), L.cout == 32 ? 1 : 2, L.cout == 32 ? 4 : 2, tf(e->x8), tf(L.in2 >= 0 && !L.upf));
         else snprintf(lbl, sizeof lbl, "%s%s%s|conv3x3_bias_relu_kernel<%d, %d, %d, %d, %d, %s, %s, %s>", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "", P, L.KC, L.NW, mw, L.WAVES, tf(L.do_pool), tf(head), tf(L.upf));
         Lx.run(lbl, flops, bytes, [&] {
-          return L.ws ? launch_ws(LaunchCtx{e->cfg.device, e->num_cus, e->ksplit_max, e->ksplit_min_chunks, e->ksplit_gate}, P, e->x8, a, L.do_pool, head, L.upf, L.c0f, uprows, s)
-                    : launch_conv(LaunchCtx{e->cfg.device, e->num_cus}, P, L, mw, a, head, s);
+          return L.ws ? launch_ws(LaunchCtx{e->cfg.device, e->num_cus, e->ksplit_max, e->ksplit_min_chunks, e->ksplit_gate, Lx.plan}, P, e->x8, a, L.do_pool, head, L.upf, L.c0f, uprows, s)
+                    : launch_conv(LaunchCtx{e->cfg.device, e->num_cus, 1, 4, 4, Lx.plan}, P, L, mw, a, head, s);
         });
 #ifdef UNETPP_WS_DBG
         if (stamp_this && L.ws) {
@@ -1093,7 +1123,9 @@ static int forward_impl(unetpp_engine* e, const void* dev_input, int in_format, 
             auto k = e->x8 ? tapmm_ws_kernel<true> : tapmm_ws_kernel<false>;
             hipError_t st = allow_full_lds((const void*)k, e->cfg.device);
             if (st != hipSuccess) return st;
-            hipLaunchKernelGGL(k, dim3((unsigned)std::min(tiles, e->num_cus)), dim3(TapmmCfg::NT), TapmmCfg::LDS_BYTES, s, t);
+            const int grid = std::min(tiles, e->num_cus);
+            if (Lx.plan) { Lx.plan[0] = grid; Lx.plan[1] = tiles; Lx.plan[2] = 1; Lx.plan[3] = 0; }      // (a GEMM tile has no rows per wave)
+            hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(TapmmCfg::NT), TapmmCfg::LDS_BYTES, s, t);
             return hipSuccess;
           });
         } else {
@@ -1330,6 +1362,11 @@ int unetpp_profile_work(const unetpp_engine* e, int i, double* flops, double* by
   if (!e || i < 0 || i >= e->prof_used) return UNETPP_E_INVALID;
   if (flops) *flops = e->prof[i].flops;
   if (bytes) *bytes = e->prof[i].bytes;
+  return UNETPP_OK;
+}
+int unetpp_profile_plan(const unetpp_engine* e, int i, int out[4]) {
+  if (!e || !out || i < 0 || i >= e->prof_used) return UNETPP_E_INVALID;
+  std::copy(e->prof[i].plan, e->prof[i].plan + 4, out);
   return UNETPP_OK;
 }
 

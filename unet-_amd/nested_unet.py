@@ -355,6 +355,19 @@ class NestedUNet(PostProcessing):
             out.append((lib.unetpp_profile_name(self._handle, i).decode(), float(ms[i]), fl.value, by.value))
         return out
 
+    def profile_plan(self):
+        """[(launch name, grid, tiles, ksplit, rows per wave)] of the last forward (profiling on), in profile_read()'s
+        order: the plan of every persistent launch (tiles counts split-K shares); zeros for the other launches."""
+        lib = _lib.load()
+        out = []
+        for i in range(lib.unetpp_profile_count(self._handle)):
+            plan = (ctypes.c_int * 4)()
+            rc = lib.unetpp_profile_plan(self._handle, i, plan)
+            if rc != 0:
+                raise RuntimeError(self._err(rc))
+            out.append((lib.unetpp_profile_name(self._handle, i).decode(), *[int(v) for v in plan]))
+        return out
+
     def debug_keep_intermediates(self, on: bool = True):
         """Materialise x0_4 and run the head unfused (needed before debug_activation('x0_4')).  In 'exact' conv0_4.conv1 then
         also runs in the plain fused-upsample kernel instead of conv3x3_ws_uprows_kernel: same layer, another

@@ -15,6 +15,7 @@
 
 #include "../../include/unetpp_contours.h"
 #include "../../include/unetpp_loss.h"
+#include "../../include/unetpp_raw.h"
 #include "../../include/unetpp_roi.h"
 #include "../../include/unetpp_simple_loops.h"
 #include "abi_common.h"
@@ -32,6 +33,7 @@
 #include "multiclass.h"
 #include "nlmeans.h"
 #include "probmap.h"
+#include "raw_frames.h"
 #include "roi_loop.h"
 #include "simple_loops.h"
 #include "tiling.h"
@@ -1801,6 +1803,65 @@ int unetpp_mask_join_u8(unetpp_engine* e, const uint8_t* dev_a, int and_a, const
   const int vec = n % 4 == 0 && ((uintptr_t)dev_a | (uintptr_t)dev_b | (uintptr_t)dev_c | (uintptr_t)dev_out) % 4 == 0;
   hipLaunchKernelGGL(sl_join_kernel, dim3((unsigned)blocks), dim3(SL_THREADS), 0, (hipStream_t)stream, dev_a, (unsigned)and_a, dev_b, (unsigned)or_b, dev_c,
                      (unsigned)or_c, (long long)n, vec, dev_out);
+  return launched(e);
+}
+
+// ---- raw camera frames: the demosaic alone and fused into the resize (raw_frames.h, include/unetpp_raw.h) -----------------------------
+static int raw_check(unetpp_engine* e, const char* what, int64_t row_stride, int64_t frame_stride, int batch, int h, int w, int pattern,
+                     size_t* extent) {
+  if (pattern < UNETPP_RAW_BG || pattern > UNETPP_RAW_MONO) return fail(e, UNETPP_E_UNSUPPORTED, "%s: unknown pattern %d", what, pattern);
+  const ShapeLimits lim{pattern == UNETPP_RAW_MONO ? 1 : 3, MAX_DIM, true};
+  if (!shape_ok(batch, h, w, lim))
+    return fail(e, UNETPP_E_UNSUPPORTED, "%s: shape %dx%dx%d outside %d <= h, w <= 65535, h * w <= 2^30", what, batch, h, w, lim.min_side);
+  const long long cap = 1ll << 40;                           // keeps every product below inside int64
+  if (row_stride < w || row_stride > cap || frame_stride > cap || frame_stride < (long long)(h - 1) * row_stride + w)
+    return fail(e, UNETPP_E_UNSUPPORTED, "%s: strides (%lld, %lld) do not hold rows of %d bytes and frames of %d rows", what, (long long)row_stride,
+                (long long)frame_stride, w, h);
+  *extent = (size_t)(batch - 1) * (size_t)frame_stride + (size_t)(h - 1) * (size_t)row_stride + (size_t)w;
+  return UNETPP_OK;
+}
+
+int unetpp_raw_to_bgr_u8(unetpp_engine* e, const uint8_t* dev_raw, int64_t row_stride, int64_t frame_stride, int batch, int h, int w, int pattern,
+                         uint8_t* dev_bgr, uint8_t* dev_gray, void* stream) {
+  REQUIRE_ROBUST(e, dev_raw && (dev_bgr || dev_gray));
+  size_t n_in = 0;
+  if (int rc = raw_check(e, "raw to bgr", row_stride, frame_stride, batch, h, w, pattern, &n_in)) return rc;
+  const size_t n = (size_t)batch * h * w;
+  if ((dev_bgr && overlaps(dev_raw, n_in, dev_bgr, 3 * n)) || (dev_gray && overlaps(dev_raw, n_in, dev_gray, n)) ||
+      (dev_bgr && dev_gray && overlaps(dev_bgr, 3 * n, dev_gray, n)))
+    return fail(e, UNETPP_E_UNSUPPORTED, "raw to bgr: an output overlaps dev_raw or the other output");
+  ENTER_DEVICE(e);
+  const bool mono = pattern == UNETPP_RAW_MONO;
+  const dim3 grid = tile_grid(mono ? w : w - 1, mono ? h : h - 1, RF_TW, RF_TH, batch);      // raw_frames.h: a Bayer frame's last tile takes the last column and row
+  const int vec_in = (uintptr_t)dev_raw % 16 == 0 && row_stride % 16 == 0 && frame_stride % 16 == 0;
+#define RF_LAUNCH(RY, RX, MONO)                                                                                                            \
+  hipLaunchKernelGGL((rf_to_bgr_kernel<RY, RX, MONO>), grid, dim3(RF_THREADS), 0, (hipStream_t)stream, dev_raw, (long long)row_stride, \
+                     (long long)frame_stride, h, w, vec_in, dev_bgr, dev_gray)
+  switch (pattern) {
+    case UNETPP_RAW_BG: RF_LAUNCH(0, 0, false); break;
+    case UNETPP_RAW_GB: RF_LAUNCH(0, 1, false); break;
+    case UNETPP_RAW_RG: RF_LAUNCH(1, 1, false); break;
+    case UNETPP_RAW_GR: RF_LAUNCH(1, 0, false); break;
+    default: RF_LAUNCH(0, 0, true); break;
+  }
+#undef RF_LAUNCH
+  return launched(e);
+}
+
+int unetpp_raw_resize_u8(unetpp_engine* e, const uint8_t* dev_raw, int64_t row_stride, int64_t frame_stride, int batch, int h, int w, int pattern,
+                         int x0, int y0, int cw, int ch, uint8_t* dev_out, int oh, int ow, void* stream) {
+  REQUIRE_ROBUST(e, dev_raw && dev_out);
+  size_t n_in = 0;
+  if (int rc = raw_check(e, "raw resize", row_stride, frame_stride, batch, h, w, pattern, &n_in)) return rc;
+  if (!shape_ok(batch, oh, ow, MASK_SHAPE)) return fail(e, UNETPP_E_UNSUPPORTED, "raw resize: output %dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", oh, ow);
+  if (x0 < 0 || y0 < 0 || cw < 1 || ch < 1 || x0 > w - cw || y0 > h - ch)
+    return fail(e, UNETPP_E_UNSUPPORTED, "raw resize: the crop (x %d, y %d, %d x %d) does not lie inside the %dx%d frame", x0, y0, cw, ch, h, w);
+  if (overlaps(dev_raw, n_in, dev_out, (size_t)batch * oh * ow * 3)) return fail(e, UNETPP_E_UNSUPPORTED, "raw resize: dev_out overlaps dev_raw");
+  ENTER_DEVICE(e);
+  static const int red_site[5][2] = {{0, 0}, {0, 1}, {1, 1}, {1, 0}, {0, 0}};      // (row parity, column parity) by UNETPP_RAW_*
+  hipLaunchKernelGGL(rf_resize_kernel, tile_grid(ow, oh, RF_OTW, RF_OTH, batch), dim3(RF_THREADS), 0, (hipStream_t)stream, dev_raw,
+                     (long long)row_stride, (long long)frame_stride, h, w, red_site[pattern][0], red_site[pattern][1],
+                     (int)(pattern == UNETPP_RAW_MONO), x0, y0, cw, ch, oh, ow, dev_out);
   return launched(e);
 }
 

@@ -14,6 +14,8 @@ postprocess_masks, the paste, the two contour diameters, the burr mask, the cove
 `process_frames_spatial`, `process_frames_fixed`, `process_frames_confidence` and `process_frames_simple` are infer_frame of
 infer_video_spatial.py, infer_video_fixed.py, infer_video_simple_v2.py and predict of infer_video_simple.py,
 infer_video_simple_optimized.py and infer_video_simple_backup.py (simple_loops.py holds their steps and NumPy forms).
+`process_raw_frames` is `process_frames` from the camera's one-byte-per-pixel buffer (GigECameraHarvester.read,
+src/camera/gige_harvester.py:116-129): the demosaic of _to_bgr runs inside the resize launch (raw_frames.py).
 """
 from __future__ import annotations
 
@@ -76,6 +78,27 @@ def process_frames(model, frames_bgr_u8, target_size=(512, 512), roi="fixed", de
         roi = map_roi_to_original((fw, fh), (tw, th))
     cable = model.resize_masks(pred, (fw, fh), match_class=1, roi=roi)
     tape = model.resize_masks(pred, (fw, fh), match_class=2, roi=roi)
+    return pred, cable, tape
+
+
+def process_raw_frames(model, raw_u8, pixel_format, target_size=(512, 512), roi="fixed", want_gray=False, device=None):
+    """GigECameraHarvester.read (src/camera/gige_harvester.py:116-129) followed by process_frames, for B raw frames uint8 [B,H,W]
+    in the camera's `pixel_format` ("BayerRG8", "BayerBG8", "Mono8", ...; raw_frames.pattern_of reads it as _to_bgr does): one
+    launch takes the raw bytes to the network's uint8 input (raw_frames.resize), the full-size BGR frame is never written, and
+    the tail is process_frames' own.  Returns what process_frames(model, raw_frames.to_bgr(model, raw_u8, pixel_format), ...)
+    returns, bit for bit; with want_gray also the full-size grey frame uint8 [B,H,W] that model.detect_burrs reads."""
+    from . import raw_frames as rf
+    x = _device_frames(model, raw_u8, device)
+    pattern = rf.pattern_of(pixel_format)
+    fh, fw = int(x.shape[1]), int(x.shape[2])
+    tw, th = int(target_size[0]), int(target_size[1])
+    pred = model.segment(rf.resize(model, x, pattern, (th, tw)))
+    if roi == "fixed":
+        roi = map_roi_to_original((fw, fh), (tw, th))
+    cable = model.resize_masks(pred, (fw, fh), match_class=1, roi=roi)
+    tape = model.resize_masks(pred, (fw, fh), match_class=2, roi=roi)
+    if want_gray:
+        return pred, cable, tape, rf.to_gray(model, x, pattern=pattern)
     return pred, cable, tape
 
 

@@ -129,6 +129,18 @@ def test_binding_table_covers_the_header_and_types_every_symbol():
     assert [n for n in _lib.ABI_SYMBOLS if getattr(lib, n).argtypes is None] == []
 
 
+@pytest.mark.parametrize("cls", ["NestedUNet", "SimpleUNet"])
+@pytest.mark.parametrize("C", [0, 9, -1])
+def test_a_class_count_outside_1_to_8_is_refused_with_the_engines_message(C, cls):
+    """unetpp_create checks num_classes before it touches a device: the heads keep 8 class slots in registers"""
+    from unet_amd import nested_unet
+    model = getattr(nested_unet, cls)(C).to("cuda:0")
+    with pytest.raises(RuntimeError) as err:
+        model._ensure_engine(1, 16, 16)
+    assert str(err.value) == f"unetpp_create failed (-1): num_classes={C} out of range [1,8]"
+    assert model._handle is None
+
+
 # ---- the tensor check: (text after the tensor's name, which host tensor, the methods, extra positional arguments) ------
 MASK, FRAMES, WIDTHS, MAPS, NUM = "mask", "frames", "widths", "maps", "num"
 TWO = ("constrain_tape_to_ring", "burrs_from_edges", "burr_mask_dog", "detect_burrs", "burr_mask_rulebased", "detect_burrs_enhanced",

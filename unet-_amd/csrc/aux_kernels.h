@@ -360,9 +360,9 @@ __device__ __forceinline__ void head_epilogue(const float (&lg)[HEAD_FUSED_MAX_C
     if (lg[c] > best) { best = lg[c]; besti = c; }
   is_cable = besti == 1; is_tape = besti == 2;
   if (want_probs || rule) {
-    float sum = 0.f;
 #pragma unroll
-    for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) { pe[c] = (c < C) ? expf(lg[c] - best) : 0.f; sum += pe[c]; }
+    for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) pe[c] = (c < C) ? expf(lg[c] - best) : 0.f;
+    const float sum = softmax_denominator(pe);
 #pragma unroll
     for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) pe[c] = pe[c] / sum;
     if (rule) apply_rule(rule, pe[0], pe[1], pe[2], t_cable, t_tape, bg_margin, ct_margin, is_cable, is_tape);

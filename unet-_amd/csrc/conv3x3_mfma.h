@@ -398,6 +398,19 @@ __device__ __forceinline__ void pack_store_rows8(const float (&v)[16], half_t* d
 
 constexpr int HEAD_FUSED_MAX_CLASSES = 8;   // the fused head keeps all logits in registers
 
+// Softmax denominator of a head: the sum of pe[c] = exp(lg[c] - max) in [0, 1] (0 in the slots c >= C), as a symmetric
+// function of the classes.  A float32 sum in class order depends on which class holds which logit (the probabilities of a
+// checkpoint with permuted head rows would differ in the last bit, tests/test_gpu_head_classes.py); here every term is rounded
+// to a multiple of 2^-28 on its own and the integers are added, which no order changes: at most 8 * 2^28 = 2^31 fits 32 bits,
+// the error is at most 8 * 2^-29 before the one rounding to float32, below a class-ordered float32 sum's.  One class: exactly
+// 1; C equal logits: exactly C.  A NaN term adds nothing (its own quotient is still NaN).
+__device__ __forceinline__ float softmax_denominator(const float (&pe)[HEAD_FUSED_MAX_CLASSES]) {
+  unsigned q = 0;
+#pragma unroll
+  for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) q += __float2uint_rn(pe[c] * 268435456.f);
+  return (float)q * (1.f / 268435456.f);
+}
+
 // UPF = fused bilinear upsample (reference unetpp.py:76,112-116: cat([skip, self.up(low)])): the second source `in1`
 // is then the LOW-resolution tensor [N][C1/16][H/2][W/2][P][16] itself; the loader interpolates each chunk's halo
 // image from it (align_corners=True: src = dst*(in-1)/(out-1), same arithmetic as upsample2x_kernel) instead of
@@ -824,12 +837,10 @@ void conv3x3_bias_relu_kernel(ConvArgs a) {
               if (lg[c] > best) { best = lg[c]; besti = c; }        // first maximal class wins
             bool is_cable = besti == 1, is_tape = besti == 2;
             if (a.probs || a.rule) {      // uniform: softmax_np = exp(x - max) / sum, fp32
-              float pe[HEAD_FUSED_MAX_CLASSES], sum = 0.f;
+              float pe[HEAD_FUSED_MAX_CLASSES];
 #pragma unroll
-              for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) {
-                pe[c] = (c < a.head_C) ? expf(lg[c] - best) : 0.f;
-                sum += pe[c];
-              }
+              for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) pe[c] = (c < a.head_C) ? expf(lg[c] - best) : 0.f;
+              const float sum = softmax_denominator(pe);
 #pragma unroll
               for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) {
                 pe[c] = pe[c] / sum;

@@ -193,12 +193,10 @@ __device__ __forceinline__ void ws_epilogue(KernArgs<ConvArgs> a, const float16v
         if (lg[c] > best) { best = lg[c]; besti = c; }        // first maximal class wins
       bool is_cable = besti == 1, is_tape = besti == 2;
       if (a->probs || a->rule) {      // uniform: softmax_np = exp(x - max) / sum, fp32
-        float pe[HEAD_FUSED_MAX_CLASSES], sum = 0.f;
+        float pe[HEAD_FUSED_MAX_CLASSES];
 #pragma unroll
-        for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) {
-          pe[c] = (c < a->head_C) ? expf(lg[c] - best) : 0.f;
-          sum += pe[c];
-        }
+        for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) pe[c] = (c < a->head_C) ? expf(lg[c] - best) : 0.f;
+        const float sum = softmax_denominator(pe);
 #pragma unroll
         for (int c = 0; c < HEAD_FUSED_MAX_CLASSES; ++c) {
           pe[c] = pe[c] / sum;

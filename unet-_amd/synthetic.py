@@ -229,3 +229,59 @@ def rescale_simple_state_dict(sd: dict, site: str, k: int) -> dict:
         else:
             _mul(out, key, down, cols)
     return out
+
+
+# ----------------------------------------------------------------------------- moving the 1x1 heads through the class indices
+# `final` (unetpp.py:85,119; simple_unet.py:92,124) and the deep-supervision heads ds1_3 / ds2_2 / ds3_1 (unetpp.py:87-91) are
+# one weight row and one bias per class.  He-normal rows let two or three classes win everywhere, so most class indices are
+# never the answer of a test; the constructors below put a chosen row at a chosen index, tie two classes bit for bit, or pin
+# every logit to a constant (tests/test_head_classes_host.py, tests/test_gpu_head_classes.py).
+HEAD_NAMES = ("final", "ds1_3", "ds2_2", "ds3_1")
+
+
+def _heads(sd):
+    return [h for h in HEAD_NAMES if h + ".weight" in sd]
+
+
+def _head_copy(sd, head):
+    """(weight, bias) of one head as fresh float32 arrays (the input dict's arrays are never written)"""
+    return (np.array(sd[head + ".weight"], dtype=np.float32, copy=True), np.array(sd[head + ".bias"], dtype=np.float32, copy=True))
+
+
+def rotate_head(sd: dict, j: int) -> dict:
+    """A copy of a state dict in which class c of every head has row and bias (c - j) mod C of the original: the logits are
+    the original's, rolled by j along the class axis."""
+    out = dict(sd)
+    for head in _heads(sd):
+        w, b = _head_copy(sd, head)
+        out[head + ".weight"] = np.ascontiguousarray(np.roll(w, int(j), axis=0))
+        out[head + ".bias"] = np.ascontiguousarray(np.roll(b, int(j), axis=0))
+    return out
+
+
+def tie_head(sd: dict, a: int, b: int) -> dict:
+    """A copy in which row and bias b of every head are bit copies of row and bias a: classes a and b tie at every pixel."""
+    out = dict(sd)
+    for head in _heads(sd):
+        w, bias = _head_copy(sd, head)
+        C = w.shape[0]
+        if not (0 <= a < C and 0 <= b < C and a != b):
+            raise ValueError(f"tie_head: classes {a}, {b} of {C}")
+        w[b] = w[a]
+        bias[b] = bias[a]
+        out[head + ".weight"], out[head + ".bias"] = w, bias
+    return out
+
+
+def constant_head(sd: dict, biases) -> dict:
+    """A copy whose head weights are all +0.0 and whose biases are `biases` [C]: every logit of every pixel is its class's
+    bias exactly (bias + sum of fma(v, +0.0, .) over finite v >= 0)."""
+    out = dict(sd)
+    for head in _heads(sd):
+        w, _ = _head_copy(sd, head)
+        bias = np.array(biases, dtype=np.float32, copy=True).reshape(-1)
+        if bias.shape[0] != w.shape[0] or not np.isfinite(bias).all():
+            raise ValueError(f"constant_head: {bias.shape[0]} finite biases wanted for {w.shape[0]} classes")
+        out[head + ".weight"] = np.zeros_like(w)                 # +0.0, never -0.0
+        out[head + ".bias"] = bias
+    return out

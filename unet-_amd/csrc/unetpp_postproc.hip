@@ -18,6 +18,7 @@
 #include "../../include/unetpp_raw.h"
 #include "../../include/unetpp_roi.h"
 #include "../../include/unetpp_simple_loops.h"
+#include "../../include/unetpp_two_stage.h"
 #include "abi_common.h"
 #include "components.h"
 #include "contours.h"
@@ -37,6 +38,7 @@
 #include "roi_loop.h"
 #include "simple_loops.h"
 #include "tiling.h"
+#include "two_stage.h"
 
 using namespace unetpp;
 
@@ -1862,6 +1864,66 @@ int unetpp_raw_resize_u8(unetpp_engine* e, const uint8_t* dev_raw, int64_t row_s
   hipLaunchKernelGGL(rf_resize_kernel, tile_grid(ow, oh, RF_OTW, RF_OTH, batch), dim3(RF_THREADS), 0, (hipStream_t)stream, dev_raw,
                      (long long)row_stride, (long long)frame_stride, h, w, red_site[pattern][0], red_site[pattern][1],
                      (int)(pattern == UNETPP_RAW_MONO), x0, y0, cw, ch, oh, ow, dev_out);
+  return launched(e);
+}
+
+// ---- the two-stage loop's own steps: class masks with their sums, the overlay, the rotation (two_stage.h, include/unetpp_two_stage.h) --
+int unetpp_two_stage_masks_u8(unetpp_engine* e, const uint8_t* dev_pred, int batch, int th, int tw, uint8_t* dev_cable, uint8_t* dev_tape, int fh,
+                              int fw, int x1, int y1, int x2, int y2, int64_t* dev_counts, void* stream) {
+#pragma clang fp contract(off)
+  REQUIRE_ROBUST(e, dev_pred && dev_cable && dev_tape && dev_counts);
+  if (!shape_ok(batch, th, tw, MASK_SHAPE) || !shape_ok(batch, fh, fw, MASK_SHAPE))
+    return fail(e, UNETPP_E_UNSUPPORTED, "two-stage masks: shape %dx%dx%d -> %dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, th, tw, fh, fw);
+  if (x1 < 0 || y1 < 0 || x2 < 0 || y2 < 0) return fail(e, UNETPP_E_UNSUPPORTED, "two-stage masks: negative ROI bound (%d, %d, %d, %d)", x1, y1, x2, y2);
+  if ((uintptr_t)dev_counts % 8) return fail(e, UNETPP_E_UNSUPPORTED, "two-stage masks: dev_counts must be 8-byte aligned");
+  const size_t n_in = (size_t)batch * th * tw, n = (size_t)batch * fh * fw, nc = (size_t)batch * 2 * sizeof(int64_t);
+  if (overlaps(dev_cable, n, dev_tape, n) || overlaps(dev_pred, n_in, dev_cable, n) || overlaps(dev_pred, n_in, dev_tape, n) ||
+      overlaps(dev_counts, nc, dev_pred, n_in) || overlaps(dev_counts, nc, dev_cable, n) || overlaps(dev_counts, nc, dev_tape, n))
+    return fail(e, UNETPP_E_UNSUPPORTED, "two-stage masks: an output overlaps dev_pred or another output");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(e, hipMemsetAsync(dev_counts, 0, nc, s));
+  const double ifx = 1.0 / ((double)fw / (double)tw), ify = 1.0 / ((double)fh / (double)th);      // resizeNN's inverse scales (nearest_table)
+  hipLaunchKernelGGL(ts_masks_kernel, tile_grid(fw, fh, TS_MW, TS_MH, batch), dim3(TS_THREADS), 0, s, dev_pred, th, tw, fh, fw, ifx, ify, x1, y1,
+                     x2, y2, dev_cable, dev_tape, (unsigned long long*)dev_counts);
+  return launched(e);
+}
+
+int unetpp_two_stage_overlay_u8(unetpp_engine* e, const uint8_t* dev_frames, const uint8_t* dev_cable, const uint8_t* dev_tape,
+                                const uint8_t* dev_burr, int batch, int h, int w, int x1, int y1, int x2, int y2, const uint8_t* dev_table,
+                                uint8_t* dev_out, int64_t* dev_burr_count, void* stream) {
+  REQUIRE_ROBUST(e, dev_frames && dev_cable && dev_tape && dev_burr && dev_table && dev_out && dev_burr_count);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_UNSUPPORTED, "two-stage overlay: shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  if (x1 < 0 || y1 < 0 || x2 < 0 || y2 < 0) return fail(e, UNETPP_E_UNSUPPORTED, "two-stage overlay: negative ROI bound (%d, %d, %d, %d)", x1, y1, x2, y2);
+  if ((uintptr_t)dev_burr_count % 8) return fail(e, UNETPP_E_UNSUPPORTED, "two-stage overlay: dev_burr_count must be 8-byte aligned");
+  const size_t n = (size_t)batch * h * w, nc = (size_t)batch * sizeof(int64_t);
+  const void* ins[5] = {dev_frames, dev_cable, dev_tape, dev_burr, dev_table};
+  const size_t in_bytes[5] = {3 * n, n, n, n, (size_t)TS_OV_TABLE};
+  for (int i = 0; i < 5; ++i)
+    if (overlaps(dev_out, 3 * n, ins[i], in_bytes[i]) || overlaps(dev_burr_count, nc, ins[i], in_bytes[i]))
+      return fail(e, UNETPP_E_UNSUPPORTED, "two-stage overlay: an output overlaps an input");
+  if (overlaps(dev_out, 3 * n, dev_burr_count, nc)) return fail(e, UNETPP_E_UNSUPPORTED, "two-stage overlay: the outputs overlap");
+  ENTER_DEVICE(e);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(e, hipMemsetAsync(dev_burr_count, 0, nc, s));
+  const size_t spans = (3 * (size_t)h * w + 47 + 47) / 48;                   // the first span starts up to 47 bytes before the frame
+  hipLaunchKernelGGL(ts_overlay_kernel, dim3((unsigned)((spans + TS_THREADS - 1) / TS_THREADS), (unsigned)batch), dim3(TS_THREADS), 0, s, dev_frames,
+                     dev_cable, dev_tape, dev_burr, h, w, x1, y1, x2, y2, dev_table, dev_out, (unsigned long long*)dev_burr_count);
+  return launched(e);
+}
+
+int unetpp_rotate_u8(unetpp_engine* e, const uint8_t* dev_in, int batch, int h, int w, int channels, int code, uint8_t* dev_out, void* stream) {
+  REQUIRE_ROBUST(e, dev_in && dev_out);
+  if (!shape_ok(batch, h, w, MASK_SHAPE)) return fail(e, UNETPP_E_UNSUPPORTED, "rotate: shape %dx%dx%d outside 1 <= h, w <= 65535, h * w <= 2^30", batch, h, w);
+  if (channels != 1 && channels != 3) return fail(e, UNETPP_E_UNSUPPORTED, "rotate: %d channels, 1 or 3 are supported", channels);
+  if (code < UNETPP_ROTATE_90_CW || code > UNETPP_ROTATE_90_CCW) return fail(e, UNETPP_E_UNSUPPORTED, "rotate: unknown code %d", code);
+  const size_t n = (size_t)batch * h * w * channels;
+  if (overlaps(dev_in, n, dev_out, n)) return fail(e, UNETPP_E_UNSUPPORTED, "rotate: dev_out overlaps dev_in");
+  ENTER_DEVICE(e);
+  const int oh = code == UNETPP_ROTATE_180 ? h : w, ow = code == UNETPP_ROTATE_180 ? w : h;
+  const dim3 grid = tile_grid(ow, oh, TS_RT, TS_RT, batch);
+  if (channels == 3) hipLaunchKernelGGL(ts_rotate_kernel<3>, grid, dim3(TS_THREADS), 0, (hipStream_t)stream, dev_in, h, w, code, dev_out);
+  else hipLaunchKernelGGL(ts_rotate_kernel<1>, grid, dim3(TS_THREADS), 0, (hipStream_t)stream, dev_in, h, w, code, dev_out);
   return launched(e);
 }
 

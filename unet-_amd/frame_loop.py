@@ -16,8 +16,13 @@ infer_video_spatial.py, infer_video_fixed.py, infer_video_simple_v2.py and predi
 infer_video_simple_optimized.py and infer_video_simple_backup.py (simple_loops.py holds their steps and NumPy forms).
 `process_raw_frames` is `process_frames` from the camera's one-byte-per-pixel buffer (GigECameraHarvester.read,
 src/camera/gige_harvester.py:116-129): the demosaic of _to_bgr runs inside the resize launch (raw_frames.py).
+`process_frames_two_stage` is the whole body of the two-stage loop (infer_two_stage_burr.py:274-343): rotate, normalise, the
+model, the class masks with their sums, stage 2 and the overlay (two_stage.py); `process_raw_frames_two_stage` is the same from
+the camera's raw bytes.  stream.FrameStream runs any of these double-buffered.
 """
 from __future__ import annotations
+
+import collections
 
 import numpy as np
 
@@ -543,3 +548,78 @@ def process_frames_simple(model, frames_bgr_u8, variant="simple", input_size=256
     if num is not None:
         model._raise_num_overflow(num, k)                                     # the read-back, after the last launch
     return out, table, over
+
+
+# ---- the two-stage loop, end to end (infer_two_stage_burr.py:274-343) -----------------------------------------------------------------
+TwoStageResult = collections.namedtuple("TwoStageResult", "pred mask_cable mask_tape mask_burr result counts roi roi_area")
+_UNUSED_BURR_KEYS = ("band_out", "laplacian_threshold", "morph_kernel")      # in the reference's presets, never read by detect_burrs_on_cable
+
+
+def _two_stage_tail(model, gray, pred, target_wh, roi, want_overlay, frames_of, burr_config):
+    """:303-343 for the class map `pred`, the grey frames and (when an overlay is wanted) the BGR frames frames_of() gives."""
+    import torch
+    from . import two_stage as ts
+    fh, fw = int(gray.shape[1]), int(gray.shape[2])
+    if isinstance(roi, str):
+        if roi != "fixed":
+            raise ValueError(f"roi must be 'fixed', None or (x1, y1, x2, y2), got {roi!r}")
+        roi = map_roi_to_original((fw, fh), target_wh)
+    roi = (0, 0, fw, fh) if roi is None else tuple(int(v) for v in roi)
+    cfg = {k: v for k, v in burr_config.items() if k not in _UNUSED_BURR_KEYS}
+    cable, tape, counts = ts.class_masks(model, pred, (fw, fh), roi)
+    burr = model.detect_burrs(gray, cable, **cfg)
+    if want_overlay:
+        result, n_burr = ts.overlay(model, frames_of(), cable, tape, burr, roi)
+    else:
+        result, n_burr = None, model.count_nonzero(burr).to(torch.int64)
+    counts = torch.cat((counts, n_burr[:, None]), dim=1)
+    return TwoStageResult(pred, cable, tape, burr, result, counts, roi, ts.roi_area(roi))
+
+
+def process_frames_two_stage(model, frames_bgr_u8, *, target_size=(512, 512), roi="fixed", rotate=False, normalize_resolution=None,
+                             want_overlay=True, device=None, **burr_config):
+    """The body of the two-stage loop (infer_two_stage_burr.py:274-343) for B BGR frames of one size at once, every step on the
+    device (two_stage.py holds the new steps and their NumPy forms):
+      1. rotate=True: cv2.rotate(frame, ROTATE_90_COUNTERCLOCKWISE) (:276; two_stage.rotate)
+      2. normalize_resolution=(width, height): cv2.resize to it (:280; resize_frames)
+      3. preprocess_image and the model (:292-300; resize_frames to target_size = (width, height), segment)
+      4. the two class masks at frame size, clipped to the ROI, and their sums (:303-314, :333-334; two_stage.class_masks)
+      5. cv2.cvtColor(frame, COLOR_BGR2GRAY) (:317; bgr_to_gray)
+      6. detect_burrs_on_cable (:318; detect_burrs, which takes `burr_config`: min_area, max_area and its other keywords; the
+         keys of the reference's presets that its function never reads are dropped, so **edges.PRESETS[name] works)
+      7. want_overlay: the four blends of visualize_two_stage and the burr count (:132-153, :321; two_stage.overlay)
+    `roi`: "fixed" (map_roi_to_original of the frame size), None (the whole frame) or (x1, y1, x2, y2) in frame pixels.  Returns a
+    TwoStageResult: pred uint8 [B,th,tw], mask_cable, mask_tape, mask_burr uint8 0/1 [B,H,W], result uint8 [B,H,W,3] or None,
+    counts int64 [B,3] (cable, tape, burr pixels), all on the device, and roi, roi_area as Python numbers;
+    two_stage.ratios(counts.cpu(), roi_area) gives the percentages and the [BURR!] flag of :338-342.  Nothing is read back apart
+    from detect_burrs' own overflow check (check=False drops it).  The ROI box, the text and the contour outlines (:155-168,
+    :345-348) stay on the host."""
+    from . import two_stage as ts
+    x = _device_frames(model, frames_bgr_u8, device)
+    if x.dim() != 4 or int(x.shape[3]) != 3:
+        raise ValueError("frames must be uint8 [B,H,W,3]")
+    if rotate:
+        x = ts.rotate(model, x, ts.ROTATE_CODES["90_ccw"])
+    if normalize_resolution is not None:
+        nw, nh = int(normalize_resolution[0]), int(normalize_resolution[1])
+        if (int(x.shape[1]), int(x.shape[2])) != (nh, nw):
+            x = model.resize_frames(x, (nh, nw))
+    fh, fw = int(x.shape[1]), int(x.shape[2])
+    tw, th = int(target_size[0]), int(target_size[1])
+    pred = model.segment(x if (fh, fw) == (th, tw) else model.resize_frames(x, (th, tw)))
+    return _two_stage_tail(model, model.bgr_to_gray(x), pred, (tw, th), roi, want_overlay, lambda: x, burr_config)
+
+
+def process_raw_frames_two_stage(model, raw_u8, pixel_format, *, target_size=(512, 512), roi="fixed", want_overlay=True, device=None,
+                                 **burr_config):
+    """process_frames_two_stage from the camera's one-byte-per-pixel buffer, B raw frames uint8 [B,H,W] in `pixel_format`
+    (process_raw_frames): raw_frames.resize feeds the model, raw_frames.to_gray stage 2, and raw_frames.to_bgr runs only when an
+    overlay is wanted.  Returns what process_frames_two_stage(model, raw_frames.to_bgr(model, raw_u8, pixel_format), ...) returns,
+    bit for bit.  A Bayer mosaic cannot be rotated or resized before its demosaic, so there is no rotate or normalize_resolution."""
+    from . import raw_frames as rf
+    x = _device_frames(model, raw_u8, device)
+    pattern = rf.pattern_of(pixel_format)
+    tw, th = int(target_size[0]), int(target_size[1])
+    pred = model.segment(rf.resize(model, x, pattern, (th, tw)))
+    gray = rf.to_gray(model, x, pattern=pattern)
+    return _two_stage_tail(model, gray, pred, (tw, th), roi, want_overlay, lambda: rf.to_bgr(model, x, pattern=pattern), burr_config)

@@ -38,6 +38,12 @@ UNETPP_HIDDEN hipError_t allow_full_lds(const void* kernel, int device, int byte
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Hands out the byte offsets of a workspace's parts in order, each on a 256-byte boundary; `end` is the total so far.
+struct Carve {
+  size_t end = 0;
+  size_t take(size_t bytes) { const size_t at = end; end = align_up(end + bytes, 256); return at; }
+};
+
 // Every entry point runs with the engine's device current and puts the caller's device back on return, so that a
 // single-process multi-GPU program (torch, another engine) is not redirected by a call into this library.
 struct UNETPP_HIDDEN DeviceScope {

@@ -25,6 +25,7 @@
 #include <cstring>
 #include <string>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <tuple>
@@ -37,6 +38,7 @@
 #include "conv3x3_ws.h"
 #include "convt2x2_mfma.h"
 #include "tapmm_ws.h"
+#include "ws_dbg_host.h"
 
 using namespace unetpp;
 
@@ -67,7 +69,6 @@ struct ConvLayer {
   bool do_pool = false;
   int zt = -1;                  // tensor id of the fp32 accumulator start values (tapmm_ws.h): K = skip channels only
   int y_t = -1, low_t = -1;     // tapmm: fp32 Y tensor and the low-res input it is computed from
-  half_t* tapw = nullptr;       // tapmm: packed weights of the up channels
   bool c0f = false;             // conv0_0.conv2 computing conv0_0.conv1 itself from the caller's input (conv3x3_ws.h, C0F)
   bool upf = false;             // in2 is the LOW-resolution tensor: the loader does the bilinear x2 itself (no `up` tensor)
   bool ws = false;              // runs in the wave-specialised kernel (conv3x3_ws.h), else the lock-step one: fixes the weight layout too
@@ -75,9 +76,8 @@ struct ConvLayer {
   size_t w_off = 0, b_off = 0;  // float offsets inside the canonical blob payload
   int KC = 16, NW = 1, MW = 2, WAVES = 8;
   int nchunks = 1;
-  half_t* wpk = nullptr;
-  float* scale = nullptr;
-  float* mult = nullptr;
+  size_t wpk_bytes = 0;         // packed weights: Cout / BN channel tiles x nchunks slabs in the layout of the layer's kernel
+  size_t wpk_at = 0, scale_at = 0, mult_at = 0, tapw_at = 0;   // byte offsets inside the arena (unetpp_engine::at)
 };
 
 struct ConvTLayer {
@@ -85,9 +85,7 @@ struct ConvTLayer {
   int cin = 0, cout = 0, lvl = 0;   // lvl = level of the INPUT (the output is one level up)
   int in = -1, out = -1;
   size_t w_off = 0, b_off = 0;
-  half_t* wpk = nullptr;
-  float* scale = nullptr;
-  float* mult = nullptr;
+  size_t wpk_at = 0, scale_at = 0, mult_at = 0;   // byte offsets inside the arena
 };
 
 enum OpKind { OP_CONVERT, OP_CONV, OP_UP, OP_CONVT, OP_HEAD, OP_TAPMM, OP_UPSUM, OP_DS };
@@ -115,6 +113,7 @@ struct unetpp_engine : unetpp_engine_common {
   int num_cus = 256;
   char* arena = nullptr;
   size_t arena_bytes = 0;
+  template <class T> T* at(size_t byte_off) const { return (T*)(arena + byte_off); }
   float* blob = nullptr;  // canonical fp32 blob payload on device (weights + biases)
   size_t blob_floats = 0;
   bool weights_loaded = false;
@@ -286,31 +285,65 @@ hipError_t launch_ws_k(const LaunchCtx& cx, ConvArgs a, hipStream_t s, bool upro
   return hipGetLastError();
 }
 
-template <bool X8>
-hipError_t launch_ws_x(const LaunchCtx& cx, int P, const ConvArgs& a, bool pool, bool head, bool upf, bool c0f, bool uprows, hipStream_t s) {
-  if (P != 2 || (upf && (pool || head)) || (pool && head)) return hipErrorInvalidValue;
-  if (uprows) {      // planned in unetpp_create: Cout / 32 channel tiles per 16-row pixel tile, weights packed to match
-    if (X8 || !upf || c0f || (a.Cout != 32 && a.Cout != 64)) return hipErrorInvalidValue;
-    return launch_ws_k<2, false, false, true, false, 1, 4, X8>(cx, a, s, true);
+// The wave-specialised kernel of one launch, worked out once from the layer and the pass (ws_variant): the profile label is
+// printed from it, launch_ws instantiates from it, and unetpp_create asks it whether every EXACT8 layer has a kernel.
+struct WsVariant {
+  bool pool, head, upf, c0f;
+  bool cat2;        // two full-resolution sources
+  bool uprows;      // conv3x3_ws_uprows_kernel: Cout / 32 channel tiles per 16-row pixel tile, weights packed to match (unetpp_create)
+  int NW, MW;       // 1 x 4: 16-row tiles (Cout = 32, low rows); 2 x 2: 8-row tiles, two 32-channel blocks per consumer wave, Cout / 64 channel tiles
+  bool valid;       // conv3x3_ws.h has this combination
+};
+
+// `head`: the 1x1 head runs in this launch's epilogue.  debug_keep_intermediates keeps the plain fused-upsample kernel reachable
+// for conv0_4.conv1 (Cout = 32: one weight layout for both kernels), and for that layer only.
+WsVariant ws_variant(int P, bool x8, const ConvLayer& L, bool head, bool keep_all) {
+  const bool two = L.in2 >= 0, wide = L.cout >= 64 && L.cout % 64 == 0;
+  WsVariant v{L.do_pool, head, L.upf, L.c0f, two && !L.upf, L.uprows && !(keep_all && L.cout == 32), wide ? 2 : 1, wide ? 2 : 4, false};
+  if (P != 2 || (v.upf && (v.pool || head)) || (v.pool && head)) return v;
+  if (v.uprows) {
+    v.NW = 1; v.MW = 4;
+    v.valid = !x8 && v.upf && !v.c0f && (L.cout == 32 || L.cout == 64);
+  } else if (wide) {
+    v.valid = !head && !v.c0f && !(v.pool && v.cat2);
+  } else if (L.cout == 32 && !v.cat2) {
+    v.valid = !v.c0f || (v.pool && !head && !v.upf && L.nchunks == 2);
   }
-  if (a.Cout >= 64 && a.Cout % 64 == 0) {      // 8-row tiles, two 32-channel blocks per consumer wave, Cout / 64 channel tiles
-    if (head || c0f) return hipErrorInvalidValue;
-    if (upf) return launch_ws_k<2, false, false, true, false, 2, 2, X8>(cx, a, s);
-    if (pool) return a.in1 ? hipErrorInvalidValue : launch_ws_k<2, true, false, false, false, 2, 2, X8>(cx, a, s);
-    if (a.in1) return launch_ws_k<2, false, false, false, false, 2, 2, X8, true>(cx, a, s);      // two full-resolution sources
-    return launch_ws_k<2, false, false, false, false, 2, 2, X8>(cx, a, s);
-  }
-  if (a.in1 && !upf) return hipErrorInvalidValue;
-  if (a.Cout != 32) return hipErrorInvalidValue;
-  if (c0f) return (pool && !head && !upf && a.nchunks == 2) ? launch_ws_k<2, true, false, false, true, 1, 4, X8>(cx, a, s) : hipErrorInvalidValue;
-  if (upf) return launch_ws_k<2, false, false, true, false, 1, 4, X8>(cx, a, s);
-  if (head) return launch_ws_k<2, false, true, false, false, 1, 4, X8>(cx, a, s);
-  if (pool) return launch_ws_k<2, true, false, false, false, 1, 4, X8>(cx, a, s);
-  return launch_ws_k<2, false, false, false, false, 1, 4, X8>(cx, a, s);
+  return v;
 }
 
-hipError_t launch_ws(const LaunchCtx& cx, int P, bool x8, const ConvArgs& a, bool pool, bool head, bool upf, bool c0f, bool uprows, hipStream_t s) {
-  return x8 ? launch_ws_x<true>(cx, P, a, pool, head, upf, c0f, uprows, s) : launch_ws_x<false>(cx, P, a, pool, head, upf, c0f, uprows, s);
+// "<layer and what is fused into it>|<kernel and its full template argument list>", as rocprofv3 prints it (bench.py matches on
+// it).  A split-K launch (conv3x3_ws_splitk_kernel, chosen in launch_ws_k) keeps the label of the unsplit kernel it stands for.
+std::string ws_label(int P, bool x8, const ConvLayer& L, const WsVariant& v) {
+  char lbl[160];
+  auto tf = [](bool b) { return b ? "true" : "false"; };
+  if (v.uprows) snprintf(lbl, sizeof lbl, "%s+up|conv3x3_ws_uprows_kernel", L.name.c_str());
+  else snprintf(lbl, sizeof lbl, "%s%s%s%s|conv3x3_ws_kernel<%d, %s, %s, %s, %s, %d, %d, %s, %s>", v.c0f ? "input+conv0_0.conv1+" : "", L.name.c_str(),
+                v.upf ? "+up" : "", v.head ? "+final+argmax" : "", P, tf(v.pool), tf(v.head), tf(v.upf), tf(v.c0f), v.NW, v.MW, tf(x8), tf(v.cat2));
+  return lbl;
+}
+
+template <bool X8>
+hipError_t launch_ws_x(const LaunchCtx& cx, const WsVariant& v, const ConvArgs& a, hipStream_t s) {
+  if (!v.valid) return hipErrorInvalidValue;
+#define CASE(pool_, head_, upf_, c0f_, nw, cat2_) \
+  if (v.pool == pool_ && v.head == head_ && v.upf == upf_ && v.c0f == c0f_ && v.NW == nw && v.cat2 == cat2_) \
+    return launch_ws_k<2, pool_, head_, upf_, c0f_, nw, 4 / nw, X8, cat2_>(cx, a, s, v.uprows);
+  CASE(false, false, true, false, 2, false)
+  CASE(true, false, false, false, 2, false)
+  CASE(false, false, false, false, 2, true)
+  CASE(false, false, false, false, 2, false)
+  CASE(true, false, false, true, 1, false)
+  CASE(false, false, true, false, 1, false)      // and, with v.uprows, its low-row sibling
+  CASE(false, true, false, false, 1, false)
+  CASE(true, false, false, false, 1, false)
+  CASE(false, false, false, false, 1, false)
+#undef CASE
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_ws(const LaunchCtx& cx, bool x8, const WsVariant& v, const ConvArgs& a, hipStream_t s) {
+  return x8 ? launch_ws_x<true>(cx, v, a, s) : launch_ws_x<false>(cx, v, a, s);
 }
 
 template <int P, int KC, int NW, int MW, int WAVES>
@@ -371,6 +404,21 @@ void choose_cfg(int P, int cin_tensor, ConvLayer& L) {
     L.KC = 16;
     L.NW = (L.cout == 32) ? 1 : 2;
   }
+}
+
+// Bytes of one K-chunk's weight slab as the layer's kernel reads it (0: no such kernel)
+size_t slab_bytes(int P, bool x8, const ConvLayer& L) {
+  if (L.ws && x8) return L.NW == 1 ? WsCfg<2, false, false, 1, 4, true>::SLAB_BYTES : WsCfg<2, false, false, 2, 2, true>::SLAB_BYTES;
+  if (L.ws) return L.NW == 1 ? WsCfg<2, false, false, 1, 4>::SLAB_BYTES : WsCfg<2, false, false, 2, 2>::SLAB_BYTES;
+#define CASE(p, kc, nw) \
+  if (P == p && L.KC == kc && L.NW == nw) return ConvCfg<p, kc, nw, 2, 8>::SLAB_BYTES;
+  CASE(1, 16, 1)
+  CASE(1, 32, 2)
+  CASE(1, 16, 2)
+  CASE(1, 16, 4)
+  CASE(2, 16, 2)
+#undef CASE
+  return 0;
 }
 
 struct Launcher {
@@ -475,7 +523,36 @@ struct Builder {
   }
 };
 
-void build_nested(unetpp_engine* e, Builder& b) {
+// The plan switches of the environment (include/unetpp.h), read once per unetpp_create.
+struct PlanSwitches {
+  int plan_cus = 0;                 // UNETPP_PLAN_CUS=n: plan every launch for n compute units instead of the device's own count; 0 = unset
+  int ksplit_max = 16, ksplit_min_chunks = 4, ksplit_gate = 4;      // UNETPP_KSPLIT=max[,min chunks[,gate]]: split-K of small launches (unetpp_engine)
+  const char* tapmm = "23";         // UNETPP_TAPMM=levels whose up channels are multiplied at low resolution, e.g. "" (off) or "123"
+  const char* uprows = "01";        // UNETPP_UPROWS=levels of the low-row fused upsample, e.g. "0" (level 0 only) or "none"
+};
+
+int read_plan_switches(PlanSwitches* sw) {
+  if (const char* pc = getenv("UNETPP_PLAN_CUS")) {
+    char* end = nullptr;
+    errno = 0;
+    const long v = strtol(pc, &end, 10);
+    if (end == pc || *end != '\0' || errno != 0 || v < 1 || v > (1 << 20))
+      return fail(nullptr, UNETPP_E_INVALID, "UNETPP_PLAN_CUS='%s': a whole number of compute units >= 1 required", pc);
+    sw->plan_cus = (int)v;
+  }
+  if (const char* k = getenv("UNETPP_KSPLIT")) {
+    sw->ksplit_max = std::max(1, atoi(k));
+    if (const char* c = strchr(k, ',')) {
+      sw->ksplit_min_chunks = std::max(1, atoi(c + 1));
+      if (const char* g2 = strchr(c + 1, ',')) sw->ksplit_gate = std::max(1, atoi(g2 + 1));      // split when tiles * gate <= CUs
+    }
+  }
+  if (const char* tl = getenv("UNETPP_TAPMM")) sw->tapmm = tl;
+  if (const char* ul = getenv("UNETPP_UPROWS")) sw->uprows = ul;
+  return UNETPP_OK;
+}
+
+void build_nested(unetpp_engine* e, Builder& b, const PlanSwitches& sw) {
   // exact modes: the first ConvBlock runs as ONE launch from the caller's tensor (no input copy, no conv0_0.conv1 launch,
   // no x0_0a tensor): conv3x3_ws.h, C0F.
   const bool c0f = e->P == 2;
@@ -499,11 +576,10 @@ void build_nested(unetpp_engine* e, Builder& b) {
     snprintf(tn, sizeof tn, "x%d_%d", l, 4 - l);
     const int low = l == 3 ? x[4] : d[l + 1];
     // Levels 2-3 (exact modes): the up channels are multiplied at LOW resolution and interpolated afterwards
-    // (tapmm_ws.h: half the flops of the layer); UNETPP_TAPMM=levels overrides, e.g. "" (off) or "123".
-    const char* tl = getenv("UNETPP_TAPMM");
+    // (tapmm_ws.h: half the flops of the layer); UNETPP_TAPMM=levels overrides (PlanSwitches).
     // (the GEMM's 128-wide virtual-channel tiles need 9 * Cout % 128 == 0: levels 2 and 3; at level 1 the fp32
     // side tensors would be 0.9 GB per step and the path measured slower anyway)
-    const bool tapmm = e->P == 2 && l >= 1 && (9 * NB[l]) % TapmmCfg::TN == 0 && strchr(tl ? tl : "23", '0' + l) != nullptr;
+    const bool tapmm = e->P == 2 && l >= 1 && (9 * NB[l]) % TapmmCfg::TN == 0 && strchr(sw.tapmm, '0' + l) != nullptr;
     if (tapmm) {
       snprintf(nm, sizeof nm, "conv%d_%d", l, 4 - l);
       const int yt = b.tensor_raw(std::string(tn) + "y", (size_t)9 * NB[l] * 4, l + 1);
@@ -580,6 +656,278 @@ void build_simple(unetpp_engine* e, Builder& b) {
   b.head(prev, SB[0]);
 }
 
+// ---- forward: one function per op kind ----------------------------------------------------------
+// The engine's activation format as its kernels' template arguments: fast <1>, exact <2>, exact8 <2, true>; the heads count 1, 2, 3.
+struct Prec {
+  int P; bool x8;
+  template <class K> K pick(K fast, K exact, K exact8) const { return x8 ? exact8 : P == 2 ? exact : fast; }
+  const char* args() const { return pick("1", "2", "2, true"); }
+  const char* head_args() const { return pick("1", "2", "3"); }
+};
+
+// One pass's share of the caller's input: where frame b0 starts, and what a launch that reads it loads per pixel.
+struct InSlice { const char* raw; int format; double bytes_per_px; };
+InSlice in_slice(const void* dev_input, int in_format, int b0, size_t hw) {
+  const int bpp = in_format == UNETPP_IN_F32_NCHW ? 12 : 3;      // three fp32 planes, or one BGR byte triple
+  return {(const char*)dev_input + (size_t)b0 * hw * bpp, in_format, (double)bpp};
+}
+
+// One pass's share of one unetpp_outputs: its five pointers moved to frame b0 (NULL stays NULL), and what the launch that
+// writes them stores per pixel.  o == NULL: this output was not requested.
+struct OutSlice {
+  const unetpp_outputs* o = nullptr;      // rule and thresholds
+  float* logits = nullptr; float* probs = nullptr;
+  uint8_t* mask = nullptr; uint8_t* cable = nullptr; uint8_t* tape = nullptr;
+  double bytes_per_px = 0;
+};
+OutSlice out_slice(const unetpp_outputs* o, int b0, int C, size_t hw) {
+  OutSlice r;
+  if (!o) return r;
+  r.o = o;
+  if (o->dev_logits) r.logits = o->dev_logits + (size_t)b0 * C * hw;
+  if (o->dev_probs) r.probs = o->dev_probs + (size_t)b0 * C * hw;
+  if (o->dev_mask) r.mask = o->dev_mask + (size_t)b0 * hw;
+  if (o->dev_cable) r.cable = o->dev_cable + (size_t)b0 * hw;
+  if (o->dev_tape) r.tape = o->dev_tape + (size_t)b0 * hw;
+  r.bytes_per_px = (r.logits ? 4.0 * C : 0) + (r.probs ? 4.0 * C : 0) + (r.mask ? 1 : 0) + (r.cable ? 1 : 0) + (r.tape ? 1 : 0);
+  return r;
+}
+
+// One micro-batch pass of forward_impl: frames b0 .. b0 + nb of the caller's batch, on stream s, in activation slot `slot`.
+struct Pass {
+  unetpp_engine* e;
+  hipStream_t s;
+  Launcher& lx;
+  int nb, b0, h, w;
+  int slot;
+  size_t slot_off;
+  InSlice in;
+  OutSlice out[4];      // unetpp_forward_ds's outs[k]; out[0] is the final head's
+  bool head_done = false;      // the head ran in the last conv's epilogue
+#ifdef UNETPP_WS_DBG
+  WsDbgPass dbg;
+#endif
+  half_t* tp(int id) const { return (half_t*)(e->arena + slot_off + e->tensors[id].off); }
+};
+
+// EXACT8: layers whose chunk count is even pair the ninth taps of consecutive chunks (conv3x3_ws.h); the split-K plan then
+// only makes shares with an even number of chunks (launch_ws_k)
+bool x8_pair9(const unetpp_engine* e, const ConvLayer& L) { return e->x8 && L.nchunks % 2 == 0; }
+
+void run_convert(Pass& c) {
+  unetpp_engine* e = c.e;
+  const Prec prec{e->P, e->x8};
+  const size_t total = (size_t)c.nb * c.h * c.w;
+  const double bytes = (double)total * c.in.bytes_per_px + (double)total * e->P * 16;
+  c.lx.run(std::string("convert_input|convert_input_kernel<") + prec.args() + ">", 0, bytes, [&] {
+    hipLaunchKernelGGL(prec.pick(convert_input_kernel<1>, convert_input_kernel<2>, convert_input_kernel<2, true>), dim3((unsigned)((total + 255) / 256)),
+                       dim3(256), 0, c.s, (const void*)c.in.raw, c.in.format, c.nb, c.h, c.w, c.tp(e->t_in8), e->d_status);
+    return hipSuccess;
+  });
+}
+
+void run_conv(Pass& c, const Op& op) {
+  unetpp_engine* e = c.e;
+  const ConvLayer& L = e->convs[op.idx];
+  const int P = e->P, C = e->cfg.num_classes;
+  const bool head = op.fuse_head && !e->keep_all && L.cout == 32;
+  const OutSlice& o = c.out[0];
+  ConvArgs a{};
+  const int H = c.h >> L.lvl, W = c.w >> L.lvl;
+  const Tensor& t0 = e->tensors[L.in];
+  const int c1 = L.in2 >= 0 ? e->tensors[L.in2].C : 0;
+  a.in0 = c.tp(L.in); a.in1 = L.in2 >= 0 ? c.tp(L.in2) : nullptr; a.C0 = t0.C; a.C1 = c1;
+  a.wpk = e->at<half_t>(L.wpk_at); a.scale = e->at<float>(L.scale_at); a.bias = e->blob + L.b_off; a.out = c.tp(L.out);
+  a.pool_out = L.do_pool ? c.tp(L.pool) : nullptr;
+  a.N = c.nb; a.H = H; a.W = W; a.Cout = L.cout;
+  a.status = e->d_status;
+  a.zinit = L.zt >= 0 ? (const float*)c.tp(L.zt) : nullptr;
+  if (e->t_kpart >= 0) { a.kpart = (float*)c.tp(e->t_kpart); a.kcnt = (unsigned*)c.tp(e->t_kcnt); }
+  a.ksplit = 1;
+  a.pair9 = x8_pair9(e, L) ? 1 : 0;
+  if (L.c0f) {     // the first block reads the caller's tensor itself
+    const ConvLayer& L1 = e->convs[e->c0f_conv1];
+    a.raw_in = c.in.raw;
+    a.raw_fmt = c.in.format == UNETPP_IN_F32_NCHW ? 0 : 1;
+    a.c1w = e->c1w; a.c1_scale = e->at<float>(L1.scale_at); a.c1_bias = e->blob + L1.b_off;
+  }
+  const int mw = small_grid_rows(L, e->num_cus, c.nb, H, W, head);
+  const int TH = L.WAVES * mw;
+  a.tiles_x = (W + 31) / 32; a.tiles_y = (H + TH - 1) / TH;
+  a.nct = L.cout / (32 * L.NW); a.nchunks = L.nchunks;
+  double px = (double)c.nb * H * W;
+  double flops = 2.0 * px * L.cout * (L.zt >= 0 ? t0.C : L.cin_real) * 9;
+  double bytes = px * P * 2.0 * (t0.C + (L.upf ? c1 / 4.0 : c1) + (head ? 0 : L.cout)) + (L.do_pool ? px / 4 * P * 2.0 * L.cout : 0.0) + (double)L.cout * L.cin_real * 9 * 2.0 * P;
+  if (L.zt >= 0) bytes += px * L.cout * 4.0 - (double)L.cout * (L.cin_real - t0.C) * 9 * 2.0 * P;
+  if (L.c0f) {     // conv0_0.conv1 rides along: its flops, the raw input instead of x0_0a
+    flops += 2.0 * px * 32 * 3 * 9;
+    bytes += px * c.in.bytes_per_px - px * P * 2.0 * t0.C;
+  }
+  if (head) {
+    a.head_w = e->blob + e->head_w_off; a.head_b = e->blob + e->head_b_off; a.head_C = C;
+    a.logits = o.logits; a.mask = o.mask; a.cable = o.cable; a.tape = o.tape;
+    a.probs = o.probs; a.rule = o.o->rule;
+    a.t_cable = o.o->t_cable; a.t_tape = o.o->t_tape; a.bg_margin = o.o->bg_margin; a.ct_margin = o.o->ct_margin;
+    flops += 2.0 * px * 32 * C;
+    bytes += px * o.bytes_per_px;
+    c.head_done = true;
+  }
+  const WsVariant v = ws_variant(P, e->x8, L, head, e->keep_all);
+  std::string lbl;
+  if (L.ws) {
+    lbl = ws_label(P, e->x8, L, v);
+  } else {
+    char buf[160];
+    auto tf = [](bool b) { return b ? "true" : "false"; };
+    snprintf(buf, sizeof buf, "%s%s%s|conv3x3_bias_relu_kernel<%d, %d, %d, %d, %d, %s, %s, %s>", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "",
+             P, L.KC, L.NW, mw, L.WAVES, tf(L.do_pool), tf(head), tf(L.upf));
+    lbl = buf;
+  }
+#ifdef UNETPP_WS_DBG
+  ws_dbg_before_launch(c.dbg, a, L.name, c.s);
+#endif
+  c.lx.run(lbl, flops, bytes, [&] {
+    return L.ws ? launch_ws(LaunchCtx{e->cfg.device, e->num_cus, e->ksplit_max, e->ksplit_min_chunks, e->ksplit_gate, c.lx.plan}, e->x8, v, a, c.s)
+                : launch_conv(LaunchCtx{e->cfg.device, e->num_cus, 1, 4, 4, c.lx.plan}, P, L, mw, a, head, c.s);
+  });
+#ifdef UNETPP_WS_DBG
+  ws_dbg_after_launch(c.dbg, a, L.name, L.ws, c.s);
+#endif
+}
+
+void run_tapmm(Pass& c, const Op& op) {
+  unetpp_engine* e = c.e;
+  const ConvLayer& L = e->convs[op.idx];
+  const int P = e->P, H = c.h >> L.lvl, W = c.w >> L.lvl;
+  const int cup = L.cin_real - e->tensors[L.in].C;
+  TapmmArgs t{};
+  t.low = c.tp(L.low_t); t.wpk = e->at<half_t>(L.tapw_at); t.y = (float*)c.tp(L.y_t);
+  t.N = c.nb; t.hw = (H >> 1) * (W >> 1); t.K = cup; t.Nv = 9 * L.cout;
+#ifdef UNETPP_WS_DBG
+  { const char* d = getenv("UNETPP_TAPMM_DBG"); t.dbg = d ? atoi(d) : 0; }
+#endif
+  const int tiles = c.nb * ((t.hw + TapmmCfg::TM - 1) / TapmmCfg::TM) * (t.Nv / TapmmCfg::TN);
+  const double M = (double)c.nb * t.hw;
+  char lbl[96];
+  snprintf(lbl, sizeof lbl, "%s.up-gemm|tapmm_ws_kernel<%s>", L.name.c_str(), e->x8 ? "true" : "false");
+  c.lx.run(lbl, 2.0 * M * cup * t.Nv, M * cup * 2.0 * P + M * t.Nv * 4.0 + (double)t.Nv * cup * 2.0 * P, [&] {
+    auto k = e->x8 ? tapmm_ws_kernel<true> : tapmm_ws_kernel<false>;
+    hipError_t st = allow_full_lds((const void*)k, e->cfg.device);
+    if (st != hipSuccess) return st;
+    const int grid = std::min(tiles, e->num_cus);
+    if (c.lx.plan) { c.lx.plan[0] = grid; c.lx.plan[1] = tiles; c.lx.plan[2] = 1; c.lx.plan[3] = 0; }      // (a GEMM tile has no rows per wave)
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(TapmmCfg::NT), TapmmCfg::LDS_BYTES, c.s, t);
+    return hipSuccess;
+  });
+}
+
+void run_upsum(Pass& c, const Op& op) {
+  unetpp_engine* e = c.e;
+  const ConvLayer& L = e->convs[op.idx];
+  const int H = c.h >> L.lvl, W = c.w >> L.lvl;
+  UpsumArgs u{};
+  u.y = (const float*)c.tp(L.y_t); u.z = (float*)c.tp(L.zt); u.N = c.nb; u.H = H; u.W = W; u.Cout = L.cout;
+  unsigned blocks = (unsigned)(((W + UpsumCfg::TW - 1) / UpsumCfg::TW) * ((H + UpsumCfg::TH - 1) / UpsumCfg::TH) * (L.cout / 32) * c.nb);
+  const double px = (double)c.nb * H * W;
+  char lbl[96];
+  const bool small = blocks <= (unsigned)e->num_cus;      // too few 16-row tiles for the chip: 4-row tiles
+  if (small) blocks = (unsigned)(((W + 31) / 32) * ((H + 3) / 4) * (L.cout / 32) * c.nb);
+  snprintf(lbl, sizeof lbl, "%s.up-sum|upsum_kernel<1, %d>", L.name.c_str(), small ? 4 : 16);
+  c.lx.run(lbl, px * L.cout * 9 * 8.0, px / 4 * 9 * L.cout * 4.0 + px * L.cout * 4.0, [&] {
+    if (small) hipLaunchKernelGGL((upsum_kernel<1, 4>), dim3(blocks), dim3(256), UpsumCfgT<4>::LDS_BYTES, c.s, u);
+    else hipLaunchKernelGGL((upsum_kernel<1, 16>), dim3(blocks), dim3(256), UpsumCfg::LDS_BYTES, c.s, u);
+    return hipSuccess;
+  });
+}
+
+// fast only: the exact modes interpolate in the decoder conv's loader (UPF)
+void run_up(Pass& c, const Op& op) {
+  unetpp_engine* e = c.e;
+  const Tensor& low = e->tensors[op.idx];
+  const Tensor& dst = e->tensors[op.out];
+  const int P = e->P, H = c.h >> dst.lvl, W = c.w >> dst.lvl;
+  double px = (double)c.nb * H * W;
+  double bytes = px * P * 2.0 * low.C + px / 4 * P * 2.0 * low.C;
+  const int nseg = (W + UP_SEG - 1) / UP_SEG;
+  const int seg_w = std::min(W, UP_SEG);
+  const size_t up_lds = (size_t)3 * (seg_w / 2 + 2) * P * 32;      // staged low-res rows of one segment
+  const int up_threads = seg_w * 2 * P >= 1024 ? 512 : (seg_w * 2 * P >= 256 ? 256 : 128);   // one item = both rows of a piece
+  char nm[64];
+  snprintf(nm, sizeof nm, "up%d|upsample2x_kernel<1>", dst.lvl);
+  c.lx.run(nm, px * low.C * 8, bytes, [&] {
+    if (P != 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(upsample2x_kernel<1>, dim3((unsigned)((H / 2) * nseg), (unsigned)(c.nb * (low.C / 16))), dim3(up_threads), up_lds, c.s, c.tp(op.idx), H, W, c.tp(op.out));
+    return hipSuccess;
+  });
+}
+
+void run_convt(Pass& c, const Op& op) {
+  unetpp_engine* e = c.e;
+  const ConvTLayer& T = e->convts[op.idx];
+  const Prec prec{e->P, e->x8};
+  const int P = e->P, H = c.h >> T.lvl, W = c.w >> T.lvl;
+  ConvTArgs a{};
+  a.in = c.tp(T.in); a.wpk = e->at<half_t>(T.wpk_at); a.scale = e->at<float>(T.scale_at); a.bias = e->blob + T.b_off; a.out = c.tp(T.out);
+  a.N = c.nb; a.H = H; a.W = W; a.Cin = T.cin; a.Cout = T.cout;
+  a.status = e->d_status;
+  double px = (double)c.nb * H * W;
+  double flops = 2.0 * px * T.cin * T.cout * 4;
+  double bytes = px * P * 2.0 * (T.cin + 4.0 * T.cout) + 4.0 * T.cin * T.cout * 2.0 * P;
+  dim3 grid((unsigned)(((H * W + 511) / 512) * (4 * T.cout / 64) * c.nb));
+  c.lx.run(T.name + "|convt2x2_kernel<" + prec.args() + ">", flops, bytes, [&] {
+    hipLaunchKernelGGL(prec.pick(convt2x2_kernel<1>, convt2x2_kernel<2>, convt2x2_kernel<2, true>), grid, dim3(256), 0, c.s, a);
+    return hipSuccess;
+  });
+}
+
+// unetpp_forward_ds: output k of this node, when requested
+void run_ds(Pass& c, const Op& op) {
+  unetpp_engine* e = c.e;
+  const Prec prec{e->P, e->x8};
+  const int k = op.idx, C = e->cfg.num_classes, P = e->P, h = c.h, w = c.w;
+  const OutSlice& o = c.out[k];
+  if (!o.o) return;
+  const int cx = e->tensors[op.out].C, hk = h >> k, wk = w >> k;
+  const double lowpx = (double)c.nb * hk * wk, px = (double)c.nb * h * w;
+  const float* dsw = e->ds_w + e->ds_w_off[k];
+  const char* nm = k == 3 ? "ds3_1" : k == 2 ? "ds2_2" : "ds1_3";
+  // 1. the 1x1 conv at the node's resolution, fp32 logits only, into the slot's scratch
+  float* low = e->ds_scratch[c.slot] + e->ds_scr_off[k];
+  const dim3 hgrid((unsigned)((hk * wk + 255) / 256), (unsigned)c.nb);
+  const size_t lds = (size_t)(C * cx + C) * sizeof(float);
+  c.lx.run(std::string(nm) + "|head_generic_kernel<" + prec.head_args() + ">", 2.0 * lowpx * cx * C, lowpx * (P * 2.0 * cx + 4.0 * C), [&] {
+    uint8_t* none = nullptr;
+    hipLaunchKernelGGL(prec.pick(head_generic_kernel<1>, head_generic_kernel<2>, head_generic_kernel<3>), hgrid, dim3(256), lds, c.s, c.tp(op.out), cx, dsw,
+                       dsw + (size_t)C * cx, C, hk, wk, low, (float*)nullptr, none, none, none, 0, 0.f, 0.f, 0.f, 0.f);
+    return hipSuccess;
+  });
+  // 2. one bilinear step to (h, w) + the head epilogue; ATen's scale, float(in - 1) / float(out - 1)
+  const float sy = (float)(hk - 1) / (float)(h - 1), sx = (float)(wk - 1) / (float)(w - 1);
+  const size_t items = (size_t)c.nb * h * (w / 4);
+  c.lx.run(std::string(nm) + "+up|ds_upsample_kernel", px * C * 9.0, lowpx * 4.0 * C + px * o.bytes_per_px, [&] {
+    hipLaunchKernelGGL(ds_upsample_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, c.s, (const float*)low, C, hk, wk, c.nb, h, w, sy, sx,
+                       o.logits, o.probs, o.mask, o.cable, o.tape, o.o->rule, o.o->t_cable, o.o->t_tape, o.o->bg_margin, o.o->ct_margin);
+    return hipSuccess;
+  });
+}
+
+void run_head(Pass& c, const Op& op) {
+  if (c.head_done) return;     // ran in the last conv's epilogue
+  unetpp_engine* e = c.e;
+  const Prec prec{e->P, e->x8};
+  const OutSlice& o = c.out[0];
+  const int cx = e->head_cx, C = e->cfg.num_classes;
+  const size_t hw = (size_t)c.h * c.w, total = c.nb * hw;
+  const dim3 grid((unsigned)((hw + 255) / 256), (unsigned)c.nb);
+  const size_t lds = (size_t)(C * cx + C) * sizeof(float);
+  c.lx.run(std::string("final+argmax|head_generic_kernel<") + prec.head_args() + ">", 2.0 * total * cx * C, (double)total * (e->P * 2.0 * cx + o.bytes_per_px), [&] {
+    hipLaunchKernelGGL(prec.pick(head_generic_kernel<1>, head_generic_kernel<2>, head_generic_kernel<3>), grid, dim3(256), lds, c.s, c.tp(op.out), cx,
+                       e->blob + e->head_w_off, e->blob + e->head_b_off, C, c.h, c.w, o.logits, o.probs, o.mask, o.cable, o.tape, o.o->rule, o.o->t_cable,
+                       o.o->t_tape, o.o->bg_margin, o.o->ct_margin);
+    return hipSuccess;
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -623,16 +971,8 @@ int unetpp_create(const unetpp_config* cfg, unetpp_engine** out) {
   // full-resolution tensor has 64 channels x (1 or 2) fp16 planes
   if ((double)cfg->max_h * cfg->max_w * 64 * 2 * (cfg->precision == UNETPP_PREC_FAST ? 1 : 2) >= 2147483648.0)
     return fail(nullptr, UNETPP_E_UNSUPPORTED, "max shape %dx%d too large for 32-bit tensor offsets", cfg->max_h, cfg->max_w);
-  // UNETPP_PLAN_CUS=n: plan every launch for n compute units instead of the device's own count (include/unetpp.h)
-  int plan_cus = 0;
-  if (const char* pc = getenv("UNETPP_PLAN_CUS")) {
-    char* end = nullptr;
-    errno = 0;
-    const long v = strtol(pc, &end, 10);
-    if (end == pc || *end != '\0' || errno != 0 || v < 1 || v > (1 << 20))
-      return fail(nullptr, UNETPP_E_INVALID, "UNETPP_PLAN_CUS='%s': a whole number of compute units >= 1 required", pc);
-    plan_cus = (int)v;
-  }
+  PlanSwitches sw;
+  if (const int rc = read_plan_switches(&sw)) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(nullptr, UNETPP_E_HIP, "no HIP device available: this engine has no CPU fallback");
@@ -640,20 +980,21 @@ int unetpp_create(const unetpp_config* cfg, unetpp_engine** out) {
   DeviceScope dev_scope(cfg->device);
   if (dev_scope.st != hipSuccess) return fail(nullptr, UNETPP_E_HIP, "hipSetDevice(%d): %s", cfg->device, hipGetErrorString(dev_scope.st));
 
-  unetpp_engine* e = new unetpp_engine();
+  // the one owner of the engine until it is handed to the caller: every early return below frees whatever exists by then
+  struct Destroy { void operator()(unetpp_engine* p) const { unetpp_destroy(p); } };
+  std::unique_ptr<unetpp_engine, Destroy> owner(new unetpp_engine());
+  unetpp_engine* e = owner.get();
+  e->cfg = *cfg;
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) e->num_cus = prop.multiProcessorCount;
   }
-  if (plan_cus > 0) {      // only ever smaller launches than the device's own plan: never a grid that is not resident at once
-    if (plan_cus > e->num_cus) {
-      const int have = e->num_cus;
-      delete e;
-      return fail(nullptr, UNETPP_E_INVALID, "UNETPP_PLAN_CUS=%d exceeds the device's %d compute units", plan_cus, have);
-    }
-    e->num_cus = plan_cus;
+  if (sw.plan_cus > 0) {      // only ever smaller launches than the device's own plan: never a grid that is not resident at once
+    if (sw.plan_cus > e->num_cus)
+      return fail(nullptr, UNETPP_E_INVALID, "UNETPP_PLAN_CUS=%d exceeds the device's %d compute units", sw.plan_cus, e->num_cus);
+    e->num_cus = sw.plan_cus;
   }
-  e->cfg = *cfg;
+  e->ksplit_max = sw.ksplit_max; e->ksplit_min_chunks = sw.ksplit_min_chunks; e->ksplit_gate = sw.ksplit_gate;
   e->P = cfg->precision == UNETPP_PREC_FAST ? 1 : 2;
   e->x8 = cfg->precision == UNETPP_PREC_EXACT8;
   e->mb = (cfg->micro_batch > 0 && cfg->micro_batch < cfg->max_batch) ? cfg->micro_batch : cfg->max_batch;
@@ -661,15 +1002,8 @@ int unetpp_create(const unetpp_config* cfg, unetpp_engine** out) {
   if (e->mb >= cfg->max_batch) e->nstreams = 1;      // a single pass has nothing to overlap with
   const int P = e->P;
 
-  if (const char* k = getenv("UNETPP_KSPLIT")) {
-    e->ksplit_max = std::max(1, atoi(k));
-    if (const char* c = strchr(k, ',')) {
-      e->ksplit_min_chunks = std::max(1, atoi(c + 1));
-      if (const char* g2 = strchr(c + 1, ',')) e->ksplit_gate = std::max(1, atoi(g2 + 1));      // split when tiles * gate <= CUs
-    }
-  }
   Builder b{e};
-  if (cfg->arch == UNETPP_ARCH_NESTED) build_nested(e, b); else build_simple(e, b);
+  if (cfg->arch == UNETPP_ARCH_NESTED) build_nested(e, b, sw); else build_simple(e, b);
   // The kernel of every conv, fixed here for the engine's lifetime (it also decides the weight layout, see repack): in the
   // exact modes the wave-specialised one, except SimpleUNet's two-source decoder convs in exact, which stay on the
   // lock-step kernel (same speed, and results that do not depend on a split-K plan: DESIGN.md 5.6); fast: lock-step.
@@ -677,25 +1011,18 @@ int unetpp_create(const unetpp_config* cfg, unetpp_engine** out) {
   // `exact`, fused upsample with at least two skip chunks, Cout = 32 or 64 (conv0_4.conv1, conv1_3.conv1): the kernel that multiplies
   // the up chunks on low-resolution rows, 32 output channels per workgroup -- Cout = 64 runs as two channel tiles per pixel tile, so
   // its weights are packed in 32-channel slabs (NW = 1; L.MW x L.WAVES stays the 16-row tile).  Cout >= 128 would repeat halo and
-  // interpolation four to eight times per pixel tile and stays on the 2 x 2 kernel.  UNETPP_UPROWS=levels overrides, e.g. "0"
-  // (level 0 only) or "none".
-  {
-    const char* ul = getenv("UNETPP_UPROWS");
-    for (ConvLayer& L : e->convs) {
-      if (!L.ws || !L.upf || P != 2 || e->x8 || (L.cout != 32 && L.cout != 64) || L.lvl > 9) continue;
-      const int c0 = e->tensors[L.in].C, c1 = e->tensors[L.in2].C;
-      if (c0 < 32 || c0 % 16 || c1 < 16 || c1 % 16 || strchr(ul ? ul : "01", '0' + L.lvl) == nullptr) continue;
-      L.uprows = true;
-      L.NW = 1;
-    }
+  // interpolation four to eight times per pixel tile and stays on the 2 x 2 kernel.  UNETPP_UPROWS=levels overrides (PlanSwitches).
+  for (ConvLayer& L : e->convs) {
+    if (!L.ws || !L.upf || P != 2 || e->x8 || (L.cout != 32 && L.cout != 64) || L.lvl > 9) continue;
+    const int c0 = e->tensors[L.in].C, c1 = e->tensors[L.in2].C;
+    if (c0 < 32 || c0 % 16 || c1 < 16 || c1 % 16 || strchr(sw.uprows, '0' + L.lvl) == nullptr) continue;
+    L.uprows = true;
+    L.NW = 1;
   }
-  if (e->x8)      // EXACT8 exists in the wave-specialised kernel only: every conv must have a variant there (launch_ws_x)
+  if (e->x8)      // EXACT8 exists in the wave-specialised kernel only: every conv must have a variant there (ws_variant)
     for (const ConvLayer& L : e->convs)
-      if (!L.ws || (L.cout != 32 && L.cout % 64) || (L.in2 >= 0 && (L.do_pool || (!L.upf && L.cout % 64)))) {
-        const std::string name = L.name;
-        delete e;
-        return fail(nullptr, UNETPP_E_UNSUPPORTED, "internal: %s has no EXACT8 kernel", name.c_str());
-      }
+      if (!L.ws || !ws_variant(P, true, L, false, false).valid)
+        return fail(nullptr, UNETPP_E_UNSUPPORTED, "internal: %s has no EXACT8 kernel", L.name.c_str());
   if (P == 2 && e->ksplit_max > 1) {
     // at most num_cus workgroups take part in a split launch, each with 4 consumer waves x 16 KB of raw accumulators
     e->t_kpart = (int)e->tensors.size();
@@ -704,68 +1031,39 @@ int unetpp_create(const unetpp_config* cfg, unetpp_engine** out) {
     { Tensor t; t.name = "ksplit.counters"; t.off = b.act; e->tensors.push_back(t); b.act += align_up((size_t)e->num_cus * 4 * sizeof(unsigned), 256); }
   }
   e->blob_floats = b.off;
-  if (b.off != blob_payload_floats(cfg->arch, cfg->num_classes, 3, &e->n_blob_layers)) {
-    delete e;
+  if (b.off != blob_payload_floats(cfg->arch, cfg->num_classes, 3, &e->n_blob_layers))
     return fail(nullptr, UNETPP_E_STATE, "internal: blob size mismatch");
-  }
   e->act_bytes = align_up(b.act, 4096);
-  size_t total = e->act_bytes * e->nstreams;
 
-  // ---- blob + packed weights + scales in the same arena
-  size_t blob_off = total; total += align_up(b.off * sizeof(float), 256);
-  std::vector<size_t> wpk_off(e->convs.size()), sc_off(e->convs.size()), mu_off(e->convs.size());
-  for (size_t i = 0; i < e->convs.size(); ++i) {
-    ConvLayer& L = e->convs[i];
-    size_t wb = (size_t)(L.cout / (32 * L.NW)) * L.nchunks * P * 9 * L.KC * (32 * L.NW) * sizeof(half_t);
-    if (e->x8) wb = (size_t)(L.cout / (32 * L.NW)) * L.nchunks * 38 * (32 * L.NW) * 16;      // WsCfg::SLAB_BYTES with X8
-    wpk_off[i] = total; total += align_up(wb, 256);
-    sc_off[i] = total; total += align_up(L.cout * sizeof(float), 256);
-    mu_off[i] = total; total += align_up(L.cout * sizeof(float), 256);
+  // ---- behind the activation slots, in the same arena: blob, packed weights and scales, each offset kept with its layer
+  Carve arena{e->act_bytes * e->nstreams};
+  const size_t blob_at = arena.take(b.off * sizeof(float));
+  for (ConvLayer& L : e->convs) {
+    L.wpk_bytes = (size_t)(L.cout / (32 * L.NW)) * L.nchunks * slab_bytes(P, e->x8, L);
+    L.wpk_at = arena.take(L.wpk_bytes);
+    L.scale_at = arena.take(L.cout * sizeof(float));
+    L.mult_at = arena.take(L.cout * sizeof(float));
   }
-  std::vector<size_t> tapw_off(e->convs.size(), 0);
-  for (size_t i = 0; i < e->convs.size(); ++i) {
-    ConvLayer& L = e->convs[i];
-    if (L.zt < 0) continue;
-    const int cup = L.cin_real - e->tensors[L.in].C;
-    tapw_off[i] = total; total += align_up((size_t)9 * L.cout * cup * P * sizeof(half_t), 256);
+  for (ConvLayer& L : e->convs)
+    if (L.zt >= 0) L.tapw_at = arena.take((size_t)9 * L.cout * (L.cin_real - e->tensors[L.in].C) * P * sizeof(half_t));
+  for (ConvTLayer& T : e->convts) {
+    T.wpk_at = arena.take((size_t)4 * T.cout * T.cin * P * sizeof(half_t));
+    T.scale_at = arena.take(T.cout * sizeof(float));
+    T.mult_at = arena.take(T.cout * sizeof(float));
   }
-  std::vector<size_t> twpk(e->convts.size()), tsc(e->convts.size()), tmu(e->convts.size());
-  for (size_t i = 0; i < e->convts.size(); ++i) {
-    ConvTLayer& T = e->convts[i];
-    twpk[i] = total; total += align_up((size_t)4 * T.cout * T.cin * P * sizeof(half_t), 256);
-    tsc[i] = total; total += align_up(T.cout * sizeof(float), 256);
-    tmu[i] = total; total += align_up(T.cout * sizeof(float), 256);
-  }
-  const size_t c1w_off = total; total += 4096;
-  const size_t status_off = total; total += 256;
+  const size_t c1w_at = arena.take(4096);
+  const size_t status_at = arena.take(256);
+  const size_t total = arena.end;
   hipError_t st = hipMalloc((void**)&e->arena, total);
-  if (st == hipSuccess) {
-    st = hipMemset(e->arena + status_off, 0, 256);
-    if (st != hipSuccess) { (void)hipFree(e->arena); e->arena = nullptr; }
-  }
-  if (st != hipSuccess) {
-    std::string m = hipGetErrorString(st);
-    delete e;
-    return fail(nullptr, UNETPP_E_HIP, "hipMalloc(%zu bytes): %s", total, m.c_str());
-  }
+  if (st == hipSuccess) st = hipMemset(e->arena + status_at, 0, 256);
+  if (st != hipSuccess) return fail(nullptr, UNETPP_E_HIP, "hipMalloc(%zu bytes): %s", total, hipGetErrorString(st));
   e->arena_bytes = total;
   if (e->t_kcnt >= 0)
     for (int i = 0; i < e->nstreams; ++i)
       (void)hipMemset(e->arena + (size_t)i * e->act_bytes + e->tensors[e->t_kcnt].off, 0, (size_t)e->num_cus * 4 * sizeof(unsigned));
-  e->d_status = (unsigned*)(e->arena + status_off);
-  e->c1w = (half_t*)(e->arena + c1w_off);
-  e->blob = (float*)(e->arena + blob_off);
-  for (size_t i = 0; i < e->convs.size(); ++i) {
-    e->convs[i].wpk = (half_t*)(e->arena + wpk_off[i]);
-    e->convs[i].scale = (float*)(e->arena + sc_off[i]);
-    e->convs[i].mult = (float*)(e->arena + mu_off[i]);
-    if (e->convs[i].zt >= 0) e->convs[i].tapw = (half_t*)(e->arena + tapw_off[i]);
-  }
-  for (size_t i = 0; i < e->convts.size(); ++i) {
-    e->convts[i].wpk = (half_t*)(e->arena + twpk[i]);
-    e->convts[i].scale = (float*)(e->arena + tsc[i]);
-    e->convts[i].mult = (float*)(e->arena + tmu[i]);
-  }
+  e->d_status = e->at<unsigned>(status_at);
+  e->c1w = e->at<half_t>(c1w_at);
+  e->blob = e->at<float>(blob_at);
   if (e->nstreams > 1) {
     hipError_t se = hipSuccess;
     for (int i = 0; i < e->nstreams && se == hipSuccess; ++i) {
@@ -773,13 +1071,9 @@ int unetpp_create(const unetpp_config* cfg, unetpp_engine** out) {
       if (se == hipSuccess) se = hipEventCreateWithFlags(&e->ev_done[i], hipEventDisableTiming);
     }
     if (se == hipSuccess) se = hipEventCreateWithFlags(&e->ev_start, hipEventDisableTiming);
-    if (se != hipSuccess) {
-      std::string m = hipGetErrorString(se);
-      unetpp_destroy(e);                       // frees the arena and whatever streams/events exist
-      return fail(nullptr, UNETPP_E_HIP, "stream/event creation: %s", m.c_str());
-    }
+    if (se != hipSuccess) return fail(nullptr, UNETPP_E_HIP, "stream/event creation: %s", hipGetErrorString(se));
   }
-  *out = e;
+  *out = owner.release();
   return UNETPP_OK;
 }
 
@@ -798,48 +1092,41 @@ void unetpp_destroy(unetpp_engine* e) {
 
 size_t unetpp_workspace_bytes(const unetpp_engine* e) { return e ? e->arena_bytes : 0; }
 
-#ifdef UNETPP_WS_DBG
-static unsigned long long* unetpp_dbg_stamp_buf = nullptr;     // measurement build: in-kernel stamps (scripts/ws_stamps.sh)
-#endif
-
-// EXACT8: layers whose chunk count is even pair the ninth taps of consecutive chunks (conv3x3_ws.h); the split-K plan then
-// only makes shares with an even number of chunks (launch_ws_k)
-static bool x8_pair9(const unetpp_engine* e, const ConvLayer& L) { return e->x8 && L.nchunks % 2 == 0; }
-
 static int repack(unetpp_engine* e, hipStream_t s) {
   const int P = e->P;
   for (auto& L : e->convs) {
     const float* w = e->blob + L.w_off;
-    hipLaunchKernelGGL(weight_scale_kernel, dim3(L.cout), dim3(256), 0, s, w, L.cin_real * 9, e->blob + L.b_off, L.mult, L.scale, e->d_status);
+    float* mult = e->at<float>(L.mult_at);
+    hipLaunchKernelGGL(weight_scale_kernel, dim3(L.cout), dim3(256), 0, s, w, L.cin_real * 9, e->blob + L.b_off, mult, e->at<float>(L.scale_at), e->d_status);
     const int BN = 32 * L.NW;
+    const long long units = (long long)(L.wpk_bytes / 16);      // one thread per 16 bytes of packed weights
     if (e->x8) {
       if ((int)(&L - &e->convs[0]) == e->c0f_conv1) continue;      // conv0_0.conv1 runs in the producers (conv0_pack_kernel below)
-      const long long units = (long long)(L.cout / BN) * L.nchunks * 38 * BN;
-      hipLaunchKernelGGL(weight_pack_x8_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, w, L.mult, L.cin_real, L.cout, BN,
-                         L.nchunks, (char*)L.wpk, units, x8_pair9(e, L) ? 1 : 0);
+      hipLaunchKernelGGL(weight_pack_x8_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, w, mult, L.cin_real, L.cout, BN,
+                         L.nchunks, e->at<char>(L.wpk_at), units, x8_pair9(e, L) ? 1 : 0);
       continue;
     }
-    long long units = (long long)(L.cout / BN) * L.nchunks * P * 9 * (L.KC / 8) * BN;
-    hipLaunchKernelGGL(weight_pack_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, w, L.mult, L.cin_real,
-                       L.cout, P, L.KC, BN, L.nchunks, L.wpk, units, L.ws ? 1 : 0);
+    hipLaunchKernelGGL(weight_pack_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, w, mult, L.cin_real,
+                       L.cout, P, L.KC, BN, L.nchunks, e->at<half_t>(L.wpk_at), units, L.ws ? 1 : 0);
   }
   for (auto& L : e->convs) {
     if (L.zt < 0) continue;
     const int cs = e->tensors[L.in].C, cup = L.cin_real - cs;
     const long long units = (long long)9 * L.cout * cup * P / 8;
-    hipLaunchKernelGGL(tapw_pack_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, e->blob + L.w_off, L.mult, L.cout, cs,
-                       cup, L.tapw, units, e->x8 ? 1 : 0);
+    hipLaunchKernelGGL(tapw_pack_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, e->blob + L.w_off, e->at<float>(L.mult_at), L.cout, cs,
+                       cup, e->at<half_t>(L.tapw_at), units, e->x8 ? 1 : 0);
   }
   if (e->c0f_conv1 >= 0) {
     const ConvLayer& L1 = e->convs[e->c0f_conv1];
-    hipLaunchKernelGGL(conv0_pack_kernel, dim3(1), dim3(256), 0, s, e->blob + L1.w_off, L1.mult, e->c1w);
+    hipLaunchKernelGGL(conv0_pack_kernel, dim3(1), dim3(256), 0, s, e->blob + L1.w_off, e->at<float>(L1.mult_at), e->c1w);
   }
   for (auto& T : e->convts) {
     const float* w = e->blob + T.w_off;
-    hipLaunchKernelGGL(convt_scale_kernel, dim3(T.cout), dim3(256), 0, s, w, T.cin, T.cout, e->blob + T.b_off, T.mult, T.scale, e->d_status);
+    float* mult = e->at<float>(T.mult_at);
+    hipLaunchKernelGGL(convt_scale_kernel, dim3(T.cout), dim3(256), 0, s, w, T.cin, T.cout, e->blob + T.b_off, mult, e->at<float>(T.scale_at), e->d_status);
     long long units = (long long)(4 * T.cout / 32) * (T.cin / 16) * P * 64;
-    hipLaunchKernelGGL(convt_pack_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, w, T.mult, T.cin, T.cout, P,
-                       T.wpk, units);
+    hipLaunchKernelGGL(convt_pack_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, w, mult, T.cin, T.cout, P,
+                       e->at<half_t>(T.wpk_at), units);
   }
   HIP_TRY(e, hipGetLastError());
   e->weights_loaded = true;
@@ -907,10 +1194,7 @@ static int check_rule(unetpp_engine* e, const unetpp_outputs* o) {
 // last requested OP_DS (the shallowest requested level), so deeper decoder levels never run.
 static int forward_impl(unetpp_engine* e, const void* dev_input, int in_format, int batch, int h, int w,
                         const unetpp_outputs* const outs[4], void* stream) {
-  static const unetpp_outputs no_outputs{};
-  const unetpp_outputs* outp = outs[0] ? outs[0] : &no_outputs;
-  float* dev_logits = outp->dev_logits; float* dev_probs = outp->dev_probs;
-  uint8_t* dev_mask = outp->dev_mask; uint8_t* dev_cable = outp->dev_cable; uint8_t* dev_tape = outp->dev_tape;
+  static const unetpp_outputs no_outputs{};      // out[0] of a pass that was asked for deep-supervision outputs only
   size_t n_ops = e->ops.size();
   if (!outs[0])
     for (size_t i = 0; i < e->ops.size(); ++i)
@@ -925,8 +1209,6 @@ static int forward_impl(unetpp_engine* e, const void* dev_input, int in_format, 
   if (h > e->cfg.max_h || w > e->cfg.max_w) return fail(e, UNETPP_E_INVALID, "shape %dx%d exceeds engine maximum %dx%d", h, w, e->cfg.max_h, e->cfg.max_w);
   ENTER_DEVICE(e);
   hipStream_t user_stream = (hipStream_t)stream;
-  hipStream_t s = user_stream;
-  const int P = e->P, C = e->cfg.num_classes;
   const bool multi = e->nstreams > 1 && batch > e->mb;
   // join: the caller's stream continues after every internal stream has drained.  It runs on EVERY exit after the
   // fork, failures included: the caller may free or reuse its output buffers on its stream right after an error
@@ -959,302 +1241,34 @@ static int forward_impl(unetpp_engine* e, const void* dev_input, int in_format, 
       HIP_TRY(e, hipMemsetAsync(e->arena + (size_t)i * e->act_bytes + e->tensors[e->t_kcnt].off, 0, (size_t)e->num_cus * 4 * sizeof(unsigned),
                                 multi ? e->streams[i] : user_stream));
   e->kcnt_dirty = true;
-  Launcher Lx{e, s};
+  Launcher Lx{e, user_stream};
   int pass = 0;
   e->prof_prev_ev = -1;     // other work may sit between two forwards: start a fresh event chain
   const size_t hw = (size_t)h * w;
 
   for (int b0 = 0; b0 < batch; b0 += e->mb, ++pass) {
-    const int nb = std::min(e->mb, batch - b0);
     const int slot = multi ? pass % e->nstreams : 0;
-    if (multi) { s = e->streams[slot]; Lx.s = s; }
-    const size_t slot_off = (size_t)slot * e->act_bytes;
-    e->last_slot_off = slot_off;
-    auto tp = [&](int id) { return (half_t*)(e->arena + slot_off + e->tensors[id].off); };
-    float* lg = dev_logits ? dev_logits + (size_t)b0 * C * hw : nullptr;
-    uint8_t* mk = dev_mask ? dev_mask + (size_t)b0 * hw : nullptr;
-    uint8_t* cb = dev_cable ? dev_cable + (size_t)b0 * hw : nullptr;
-    uint8_t* tpe = dev_tape ? dev_tape + (size_t)b0 * hw : nullptr;
-    float* pr = dev_probs ? dev_probs + (size_t)b0 * C * hw : nullptr;
-    bool head_done = false;
-#ifdef UNETPP_WS_DBG
-    std::vector<std::string> dbg_timeline;                   // UNETPP_WS_STAMPS=all: the wave-specialised launches of this pass, in order
-#endif
-
+    if (multi) Lx.s = e->streams[slot];
+    Pass c{e, Lx.s, Lx, std::min(e->mb, batch - b0), b0, h, w, slot, (size_t)slot * e->act_bytes, in_slice(dev_input, in_format, b0, hw)};
+    c.out[0] = out_slice(outs[0] ? outs[0] : &no_outputs, b0, e->cfg.num_classes, hw);
+    for (int k = 1; k < 4; ++k) c.out[k] = out_slice(outs[k], b0, e->cfg.num_classes, hw);
+    e->last_slot_off = c.slot_off;
     for (size_t oi = 0; oi < n_ops; ++oi) {
       const Op& op = e->ops[oi];
-      if (op.kind == OP_CONVERT) {
-        const char* src = (const char*)dev_input + (in_format == UNETPP_IN_F32_NCHW ? (size_t)b0 * 3 * hw * 4 : (size_t)b0 * hw * 3);
-        size_t total = (size_t)nb * hw;
-        double bytes = (double)total * (in_format == UNETPP_IN_F32_NCHW ? 12 : 3) + (double)total * P * 16;
-        Lx.run(e->x8 ? "convert_input|convert_input_kernel<2, true>" : P == 2 ? "convert_input|convert_input_kernel<2>" : "convert_input|convert_input_kernel<1>", 0, bytes, [&] {
-          if (e->x8) hipLaunchKernelGGL((convert_input_kernel<2, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const void*)src, in_format, nb, h, w, tp(e->t_in8), e->d_status);
-          else if (P == 2) hipLaunchKernelGGL(convert_input_kernel<2>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const void*)src, in_format, nb, h, w, tp(e->t_in8), e->d_status);
-          else hipLaunchKernelGGL(convert_input_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const void*)src, in_format, nb, h, w, tp(e->t_in8), e->d_status);
-          return hipSuccess;
-        });
-      } else if (op.kind == OP_CONV) {
-        ConvLayer& L = e->convs[op.idx];
-        const bool head = op.fuse_head && !e->keep_all && L.cout == 32;
-        ConvArgs a{};
-        const int H = h >> L.lvl, W = w >> L.lvl;
-        const Tensor& t0 = e->tensors[L.in];
-        const int c1 = L.in2 >= 0 ? e->tensors[L.in2].C : 0;
-        a.in0 = tp(L.in); a.in1 = L.in2 >= 0 ? tp(L.in2) : nullptr; a.C0 = t0.C; a.C1 = c1;
-        a.wpk = L.wpk; a.scale = L.scale; a.bias = e->blob + L.b_off; a.out = tp(L.out);
-        a.pool_out = L.do_pool ? tp(L.pool) : nullptr;
-        a.N = nb; a.H = H; a.W = W; a.Cout = L.cout;
-        a.status = e->d_status;
-        a.zinit = L.zt >= 0 ? (const float*)tp(L.zt) : nullptr;
-        if (e->t_kpart >= 0) { a.kpart = (float*)tp(e->t_kpart); a.kcnt = (unsigned*)tp(e->t_kcnt); }
-        a.ksplit = 1;
-        a.pair9 = x8_pair9(e, L) ? 1 : 0;
-        if (L.c0f) {     // the first block reads the caller's tensor itself
-          const ConvLayer& L1 = e->convs[e->c0f_conv1];
-          a.raw_in = (const char*)dev_input + (in_format == UNETPP_IN_F32_NCHW ? (size_t)b0 * 3 * hw * 4 : (size_t)b0 * hw * 3);
-          a.raw_fmt = in_format == UNETPP_IN_F32_NCHW ? 0 : 1;
-          a.c1w = e->c1w; a.c1_scale = L1.scale; a.c1_bias = e->blob + L1.b_off;
-        }
-#ifdef UNETPP_WS_DBG
-        { const char* d = getenv("UNETPP_WS_DBG"); a.dbg = d ? atoi(d) : 0; }
-        // UNETPP_WS_DBG_ONLY=layer: the ablation applies to that launch alone -- its inputs stay genuine (a layer fed with the
-        // zeros an ablated predecessor leaves behind runs at a different clock)
-        { const char* only = getenv("UNETPP_WS_DBG_ONLY"); if (only && L.name != only) a.dbg = 0; }
-        unsigned long long*& stamp_buf = unetpp_dbg_stamp_buf;
-        const char* stamp_layer = getenv("UNETPP_WS_STAMPS");      // layer name: print that launch's in-kernel phase times
-        const bool stamp_all = stamp_layer && !strcmp(stamp_layer, "all");      // "all": one wall-clock timeline of the forward
-        const bool stamp_this = stamp_layer && L.name == stamp_layer;
-        if (stamp_this || stamp_all) {
-          if (!stamp_buf) { (void)hipMalloc((void**)&stamp_buf, (size_t)32 * 1024 * 32 * 8); (void)hipMemset(stamp_buf, 0, (size_t)32 * 1024 * 32 * 8); }
-          if (stamp_this) (void)hipMemsetAsync(stamp_buf, 0, 1024 * 32 * 8 * 5, s);
-          a.stamps = stamp_buf + (stamp_all ? (size_t)(1 + dbg_timeline.size()) * 1024 * 32 : 0);
-          if (stamp_all) dbg_timeline.push_back(L.name);
-        }
-#endif
-        const int mw = small_grid_rows(L, e->num_cus, nb, H, W, head);
-        const int TH = L.WAVES * mw;
-        a.tiles_x = (W + 31) / 32; a.tiles_y = (H + TH - 1) / TH;
-        a.nct = L.cout / (32 * L.NW); a.nchunks = L.nchunks;
-        double px = (double)nb * H * W;
-        double flops = 2.0 * px * L.cout * (L.zt >= 0 ? t0.C : L.cin_real) * 9;
-        double bytes = px * P * 2.0 * (t0.C + (L.upf ? c1 / 4.0 : c1) + (head ? 0 : L.cout)) + (L.do_pool ? px / 4 * P * 2.0 * L.cout : 0.0) + (double)L.cout * L.cin_real * 9 * 2.0 * P;
-        if (L.zt >= 0) bytes += px * L.cout * 4.0 - (double)L.cout * (L.cin_real - t0.C) * 9 * 2.0 * P;
-        if (L.c0f) {     // conv0_0.conv1 rides along: its flops, the raw input instead of x0_0a
-          flops += 2.0 * px * 32 * 3 * 9;
-          bytes += px * (in_format == UNETPP_IN_F32_NCHW ? 12.0 : 3.0) - px * P * 2.0 * t0.C;
-        }
-        if (head) {
-          a.head_w = e->blob + e->head_w_off; a.head_b = e->blob + e->head_b_off; a.head_C = C;
-          a.logits = lg; a.mask = mk; a.cable = cb; a.tape = tpe;
-          a.probs = pr; a.rule = outp->rule;
-          a.t_cable = outp->t_cable; a.t_tape = outp->t_tape; a.bg_margin = outp->bg_margin; a.ct_margin = outp->ct_margin;
-          flops += 2.0 * px * 32 * C;
-          bytes += px * ((lg ? 4.0 * C : 0) + (pr ? 4.0 * C : 0) + (mk ? 1 : 0) + (cb ? 1 : 0) + (tpe ? 1 : 0));
-          head_done = true;
-        }
-        char lbl[160];
-        // labels end in the kernel's full template argument list, as rocprofv3 prints it (bench.py matches on it)
-        auto tf = [](bool v) { return v ? "true" : "false"; };
-        // the layers planned for the low-row kernel (unetpp_create); debug_keep_intermediates keeps the plain fused-upsample kernel
-        // reachable for conv0_4.conv1 (Cout = 32: one weight layout for both kernels), and for that layer only
-        const bool uprows = L.uprows && !(e->keep_all && L.cout == 32);
-        if (uprows) snprintf(lbl, sizeof lbl, "%s+up|conv3x3_ws_uprows_kernel", L.name.c_str());
-        else if (L.ws) snprintf(lbl, sizeof lbl, "%s%s%s%s|conv3x3_ws_kernel<%d, %s, %s, %s, %s, %d, %d, %s, %s>", L.c0f ? "input+conv0_0.conv1+" : "", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "", P, tf(L.do_pool), tf(head), tf(L.upf), tf(L.c0f), L.cout == 32 ? 1 : 2, L.cout == 32 ? 4 : 2, tf(e->x8), tf(L.in2 >= 0 && !L.upf));
-        else snprintf(lbl, sizeof lbl, "%s%s%s|conv3x3_bias_relu_kernel<%d, %d, %d, %d, %d, %s, %s, %s>", L.name.c_str(), L.upf ? "+up" : "", head ? "+final+argmax" : "", P, L.KC, L.NW, mw, L.WAVES, tf(L.do_pool), tf(head), tf(L.upf));
-        Lx.run(lbl, flops, bytes, [&] {
-          return L.ws ? launch_ws(LaunchCtx{e->cfg.device, e->num_cus, e->ksplit_max, e->ksplit_min_chunks, e->ksplit_gate, Lx.plan}, P, e->x8, a, L.do_pool, head, L.upf, L.c0f, uprows, s)
-                    : launch_conv(LaunchCtx{e->cfg.device, e->num_cus, 1, 4, 4, Lx.plan}, P, L, mw, a, head, s);
-        });
-#ifdef UNETPP_WS_DBG
-        if (stamp_this && L.ws) {
-          static int printed = 0;
-          std::vector<unsigned long long> hs(1024 * 32 * 5);
-          (void)hipStreamSynchronize(s);
-          (void)hipMemcpy(hs.data(), stamp_buf, hs.size() * 8, hipMemcpyDeviceToHost);
-          if (printed++ == 3) {      // a warm launch
-            double sum[32] = {0};
-            int nwg = 0;
-            for (int b = 0; b < 1024; ++b) { if (!hs[b * 32 + 1] && !hs[b * 32 + 16]) continue; ++nwg; for (int i = 0; i < 32; ++i) sum[i] += (double)hs[b * 32 + i]; }
-            fprintf(stderr, "[stamps %s] %d workgroups, mean cycles per workgroup:\n  consumer: barrier %.0f  chunks %.0f  epilogue %.0f  init %.0f\n"
-                            "  producer: skip issue %.0f wait %.0f barrier %.0f | up issue %.0f interp %.0f (reads %.0f arithmetic %.0f split+stores %.0f) wait %.0f barrier %.0f | setup %.0f\n", L.name.c_str(), nwg,
-                    sum[0] / nwg, sum[1] / nwg, sum[2] / nwg, sum[3] / nwg, sum[16] / nwg, sum[17] / nwg, sum[18] / nwg, sum[19] / nwg, sum[20] / nwg, sum[24] / nwg, sum[25] / nwg, sum[26] / nwg, sum[21] / nwg, sum[22] / nwg, sum[23] / nwg);
-            // wall-clock (100 MHz) begin / end of consumer wave 0 of every workgroup, relative to the earliest begin
-            std::vector<double> bg, en;
-            unsigned long long t0 = ~0ull;
-            std::vector<double> cb, pe;
-            for (int b = 0; b < 1024; ++b) if (hs[b * 32 + 6]) t0 = std::min(t0, hs[b * 32 + 6]);
-            for (int b = 0; b < 1024; ++b) if (hs[b * 32 + 6]) {
-              bg.push_back((hs[b * 32 + 6] - t0) * 0.01); en.push_back((hs[b * 32 + 5] - t0) * 0.01);
-              cb.push_back((hs[b * 32 + 4] - t0) * 0.01); pe.push_back((hs[b * 32 + 16 + 12] - t0) * 0.01);
-            }
-            std::sort(bg.begin(), bg.end()); std::sort(en.begin(), en.end()); std::sort(cb.begin(), cb.end()); std::sort(pe.begin(), pe.end());
-            if (!bg.empty()) fprintf(stderr, "  consumer loop begins p50 %.2f max %.2f | producer wave 0 ends p50 %.2f max %.2f\n", cb[cb.size() / 2], cb.back(), pe[pe.size() / 2], pe.back());
-            if (a.dbg & 131072)
-              for (int b : {0, 1, 100, 200}) {      // event logs of consumer wave 0 and producer wave 0 (phase:us after the earliest kernel entry)
-                for (int role = 0; role < 2; ++role) {
-                  fprintf(stderr, "  wg %3d %s:", b, role ? "producer" : "consumer");
-                  const unsigned long long* ev = hs.data() + 1024 * 32 + ((size_t)b * 2 + role) * 64;
-                  for (int i = 0; i < 60 && ev[i]; ++i) fprintf(stderr, " %d:%.2f", (int)(ev[i] >> 56), (double)((ev[i] & 0xffffffffffffffull) - t0) * 0.01);
-                  fprintf(stderr, "\n");
-                }
-              }
-            if (!bg.empty())
-              fprintf(stderr, "  wall clock (us after the first workgroup's kernel entry): entry p50 %.2f p90 %.2f max %.2f | end min %.2f p50 %.2f p90 %.2f max %.2f\n",
-                      bg[bg.size() / 2], bg[bg.size() * 9 / 10], bg.back(), en.front(), en[en.size() / 2], en[en.size() * 9 / 10], en.back());
-          }
-        }
-#endif
-      } else if (op.kind == OP_TAPMM || op.kind == OP_UPSUM) {
-        const ConvLayer& L = e->convs[op.idx];
-        const int H = h >> L.lvl, W = w >> L.lvl;
-        const int cs = e->tensors[L.in].C, cup = L.cin_real - cs;
-        if (op.kind == OP_TAPMM) {
-          TapmmArgs t{};
-          t.low = tp(L.low_t); t.wpk = L.tapw; t.y = (float*)tp(L.y_t);
-          t.N = nb; t.hw = (H >> 1) * (W >> 1); t.K = cup; t.Nv = 9 * L.cout;
-#ifdef UNETPP_WS_DBG
-          { const char* d = getenv("UNETPP_TAPMM_DBG"); t.dbg = d ? atoi(d) : 0; }
-#endif
-          const int tiles = nb * ((t.hw + TapmmCfg::TM - 1) / TapmmCfg::TM) * (t.Nv / TapmmCfg::TN);
-          const double M = (double)nb * t.hw;
-          char lbl[96];
-          snprintf(lbl, sizeof lbl, "%s.up-gemm|tapmm_ws_kernel<%s>", L.name.c_str(), e->x8 ? "true" : "false");
-          Lx.run(lbl, 2.0 * M * cup * t.Nv, M * cup * 2.0 * P + M * t.Nv * 4.0 + (double)t.Nv * cup * 2.0 * P, [&] {
-            auto k = e->x8 ? tapmm_ws_kernel<true> : tapmm_ws_kernel<false>;
-            hipError_t st = allow_full_lds((const void*)k, e->cfg.device);
-            if (st != hipSuccess) return st;
-            const int grid = std::min(tiles, e->num_cus);
-            if (Lx.plan) { Lx.plan[0] = grid; Lx.plan[1] = tiles; Lx.plan[2] = 1; Lx.plan[3] = 0; }      // (a GEMM tile has no rows per wave)
-            hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(TapmmCfg::NT), TapmmCfg::LDS_BYTES, s, t);
-            return hipSuccess;
-          });
-        } else {
-          UpsumArgs u{};
-          u.y = (const float*)tp(L.y_t); u.z = (float*)tp(L.zt); u.N = nb; u.H = H; u.W = W; u.Cout = L.cout;
-          unsigned blocks = (unsigned)(((W + UpsumCfg::TW - 1) / UpsumCfg::TW) * ((H + UpsumCfg::TH - 1) / UpsumCfg::TH) * (L.cout / 32) * nb);
-          const double px = (double)nb * H * W;
-          char lbl[96];
-          const bool small = blocks <= (unsigned)e->num_cus;      // too few 16-row tiles for the chip: 4-row tiles
-          if (small) blocks = (unsigned)(((W + 31) / 32) * ((H + 3) / 4) * (L.cout / 32) * nb);
-          snprintf(lbl, sizeof lbl, "%s.up-sum|upsum_kernel<1, %d>", L.name.c_str(), small ? 4 : 16);
-          Lx.run(lbl, px * L.cout * 9 * 8.0, px / 4 * 9 * L.cout * 4.0 + px * L.cout * 4.0, [&] {
-            if (small) hipLaunchKernelGGL((upsum_kernel<1, 4>), dim3(blocks), dim3(256), UpsumCfgT<4>::LDS_BYTES, s, u);
-            else hipLaunchKernelGGL((upsum_kernel<1, 16>), dim3(blocks), dim3(256), UpsumCfg::LDS_BYTES, s, u);
-            return hipSuccess;
-          });
-        }
-      } else if (op.kind == OP_UP) {      // fast only: the exact modes interpolate in the decoder conv's loader (UPF)
-        const Tensor& low = e->tensors[op.idx];
-        const Tensor& dst = e->tensors[op.out];
-        const int H = h >> dst.lvl, W = w >> dst.lvl;
-        double px = (double)nb * H * W;
-        double bytes = px * P * 2.0 * low.C + px / 4 * P * 2.0 * low.C;
-        const int nseg = (W + UP_SEG - 1) / UP_SEG;
-        const int seg_w = std::min(W, UP_SEG);
-        const size_t up_lds = (size_t)3 * (seg_w / 2 + 2) * P * 32;      // staged low-res rows of one segment
-        const int up_threads = seg_w * 2 * P >= 1024 ? 512 : (seg_w * 2 * P >= 256 ? 256 : 128);   // one item = both rows of a piece
-        char nm[64];
-        snprintf(nm, sizeof nm, "up%d|upsample2x_kernel<1>", dst.lvl);
-        Lx.run(nm, px * low.C * 8, bytes, [&] {
-          if (P != 1) return hipErrorInvalidValue;
-          hipLaunchKernelGGL(upsample2x_kernel<1>, dim3((unsigned)((H / 2) * nseg), (unsigned)(nb * (low.C / 16))), dim3(up_threads), up_lds, s, tp(op.idx), H, W, tp(op.out));
-          return hipSuccess;
-        });
-      } else if (op.kind == OP_CONVT) {
-        ConvTLayer& T = e->convts[op.idx];
-        ConvTArgs a{};
-        const int H = h >> T.lvl, W = w >> T.lvl;
-        a.in = tp(T.in); a.wpk = T.wpk; a.scale = T.scale; a.bias = e->blob + T.b_off; a.out = tp(T.out);
-        a.N = nb; a.H = H; a.W = W; a.Cin = T.cin; a.Cout = T.cout;
-        a.status = e->d_status;
-        double px = (double)nb * H * W;
-        double flops = 2.0 * px * T.cin * T.cout * 4;
-        double bytes = px * P * 2.0 * (T.cin + 4.0 * T.cout) + 4.0 * T.cin * T.cout * 2.0 * P;
-        dim3 grid((unsigned)(((H * W + 511) / 512) * (4 * T.cout / 64) * nb));
-        char lbl[96];
-        if (e->x8) snprintf(lbl, sizeof lbl, "%s|convt2x2_kernel<2, true>", T.name.c_str());
-        else snprintf(lbl, sizeof lbl, "%s|convt2x2_kernel<%d>", T.name.c_str(), P);
-        Lx.run(lbl, flops, bytes, [&] {
-          if (e->x8) hipLaunchKernelGGL((convt2x2_kernel<2, true>), grid, dim3(256), 0, s, a);
-          else if (P == 2) hipLaunchKernelGGL(convt2x2_kernel<2>, grid, dim3(256), 0, s, a);
-          else hipLaunchKernelGGL(convt2x2_kernel<1>, grid, dim3(256), 0, s, a);
-          return hipSuccess;
-        });
-      } else if (op.kind == OP_DS) {      // unetpp_forward_ds: output k of this node, when requested
-        const int k = op.idx;
-        const unetpp_outputs* dk = outs[k];
-        if (!dk) continue;
-        const int cx = e->tensors[op.out].C, hk = h >> k, wk = w >> k;
-        const double lowpx = (double)nb * hk * wk, px = (double)nb * hw;
-        float* low = e->ds_scratch[slot] + e->ds_scr_off[k];
-        const float* dsw = e->ds_w + e->ds_w_off[k];
-        const float* dsb = dsw + (size_t)C * cx;
-        const char* nm = k == 3 ? "ds3_1" : k == 2 ? "ds2_2" : "ds1_3";
-        char lbl[96];
-        // 1. the 1x1 conv at the node's resolution, fp32 logits only, into the slot's scratch
-        snprintf(lbl, sizeof lbl, "%s|head_generic_kernel<%d>", nm, e->x8 ? 3 : P);
-        const dim3 hgrid((unsigned)((hk * wk + 255) / 256), (unsigned)nb);
-        const size_t lds = (size_t)(C * cx + C) * sizeof(float);
-        Lx.run(lbl, 2.0 * lowpx * cx * C, lowpx * (P * 2.0 * cx + 4.0 * C), [&] {
-          uint8_t* none = nullptr;
-          if (e->x8) hipLaunchKernelGGL(head_generic_kernel<3>, hgrid, dim3(256), lds, s, tp(op.out), cx, dsw, dsb, C, hk, wk, low, (float*)nullptr, none, none, none, 0, 0.f, 0.f, 0.f, 0.f);
-          else if (P == 2) hipLaunchKernelGGL(head_generic_kernel<2>, hgrid, dim3(256), lds, s, tp(op.out), cx, dsw, dsb, C, hk, wk, low, (float*)nullptr, none, none, none, 0, 0.f, 0.f, 0.f, 0.f);
-          else hipLaunchKernelGGL(head_generic_kernel<1>, hgrid, dim3(256), lds, s, tp(op.out), cx, dsw, dsb, C, hk, wk, low, (float*)nullptr, none, none, none, 0, 0.f, 0.f, 0.f, 0.f);
-          return hipSuccess;
-        });
-        // 2. one bilinear step to (h, w) + the head epilogue; ATen's scale, float(in - 1) / float(out - 1)
-        float* dl = dk->dev_logits ? dk->dev_logits + (size_t)b0 * C * hw : nullptr;
-        float* dp = dk->dev_probs ? dk->dev_probs + (size_t)b0 * C * hw : nullptr;
-        uint8_t* dm = dk->dev_mask ? dk->dev_mask + (size_t)b0 * hw : nullptr;
-        uint8_t* dc = dk->dev_cable ? dk->dev_cable + (size_t)b0 * hw : nullptr;
-        uint8_t* dt = dk->dev_tape ? dk->dev_tape + (size_t)b0 * hw : nullptr;
-        const float sy = (float)(hk - 1) / (float)(h - 1), sx = (float)(wk - 1) / (float)(w - 1);
-        const size_t items = (size_t)nb * h * (w / 4);
-        snprintf(lbl, sizeof lbl, "%s+up|ds_upsample_kernel", nm);
-        Lx.run(lbl, px * C * 9.0, lowpx * 4.0 * C + px * ((dl ? 4.0 * C : 0) + (dp ? 4.0 * C : 0) + (dm ? 1 : 0) + (dc ? 1 : 0) + (dt ? 1 : 0)), [&] {
-          hipLaunchKernelGGL(ds_upsample_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const float*)low, C, hk, wk, nb, h, w, sy, sx,
-                             dl, dp, dm, dc, dt, dk->rule, dk->t_cable, dk->t_tape, dk->bg_margin, dk->ct_margin);
-          return hipSuccess;
-        });
-      } else if (op.kind == OP_HEAD) {
-        if (head_done) continue;     // ran in the last conv's epilogue
-        const int cx = e->head_cx;
-        size_t total = (size_t)nb * hw;
-        double bytes = (double)total * (P * 2.0 * cx + (lg ? 4.0 * C : 0) + (pr ? 4.0 * C : 0) + (mk ? 1 : 0) + (cb ? 1 : 0) + (tpe ? 1 : 0));
-        dim3 grid((unsigned)((hw + 255) / 256), (unsigned)nb);
-        const size_t lds = (size_t)(C * cx + C) * sizeof(float);
-        Lx.run(e->x8 ? "final+argmax|head_generic_kernel<3>" : P == 2 ? "final+argmax|head_generic_kernel<2>" : "final+argmax|head_generic_kernel<1>", 2.0 * total * cx * C, bytes, [&] {
-          if (e->x8) hipLaunchKernelGGL(head_generic_kernel<3>, grid, dim3(256), lds, s, tp(op.out), cx, e->blob + e->head_w_off, e->blob + e->head_b_off, C, h, w, lg, pr, mk, cb, tpe, outp->rule, outp->t_cable, outp->t_tape, outp->bg_margin, outp->ct_margin);
-          else if (P == 2) hipLaunchKernelGGL(head_generic_kernel<2>, grid, dim3(256), lds, s, tp(op.out), cx, e->blob + e->head_w_off, e->blob + e->head_b_off, C, h, w, lg, pr, mk, cb, tpe, outp->rule, outp->t_cable, outp->t_tape, outp->bg_margin, outp->ct_margin);
-          else hipLaunchKernelGGL(head_generic_kernel<1>, grid, dim3(256), lds, s, tp(op.out), cx, e->blob + e->head_w_off, e->blob + e->head_b_off, C, h, w, lg, pr, mk, cb, tpe, outp->rule, outp->t_cable, outp->t_tape, outp->bg_margin, outp->ct_margin);
-          return hipSuccess;
-        });
+      switch (op.kind) {
+        case OP_CONVERT: run_convert(c); break;
+        case OP_CONV: run_conv(c, op); break;
+        case OP_TAPMM: run_tapmm(c, op); break;
+        case OP_UPSUM: run_upsum(c, op); break;
+        case OP_UP: run_up(c, op); break;
+        case OP_CONVT: run_convt(c, op); break;
+        case OP_DS: run_ds(c, op); break;
+        case OP_HEAD: run_head(c, op); break;
       }
     }
     if (Lx.rc) return Lx.rc;
 #ifdef UNETPP_WS_DBG
-    if (!dbg_timeline.empty()) {
-      // wall-clock (100 MHz, chip-wide) entry of the first workgroup and end of the last consumer-0 / producer-0 wave of every
-      // wave-specialised launch, relative to the first launch's entry: what lies between the launches
-      static int pass = 0;
-      if (++pass == 6) {
-        (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> hs((size_t)(1 + dbg_timeline.size()) * 1024 * 32);
-        (void)hipMemcpy(hs.data(), unetpp_dbg_stamp_buf, hs.size() * 8, hipMemcpyDeviceToHost);
-        unsigned long long T0 = ~0ull;
-        double prev_end = 0;
-        for (size_t li = 0; li < dbg_timeline.size(); ++li) {
-          const unsigned long long* r = hs.data() + (1 + li) * 1024 * 32;
-          unsigned long long first = ~0ull, last = 0; int nwg = 0;
-          for (int b = 0; b < 1024; ++b) if (r[b * 32 + 6]) { ++nwg; first = std::min(first, r[b * 32 + 6]); last = std::max(last, std::max(r[b * 32 + 5], r[b * 32 + 16 + 12])); }
-          if (!nwg) continue;
-          if (T0 == ~0ull) T0 = first;
-          const double b0 = (first - T0) * 0.01, e0 = (last - T0) * 0.01;
-          fprintf(stderr, "[timeline] %-16s %4d wg  entry %8.2f  end %8.2f  inside %6.2f  since previous end %6.2f\n", dbg_timeline[li].c_str(), nwg, b0, e0, e0 - b0, b0 - prev_end);
-          prev_end = e0;
-        }
-      }
-    }
+    ws_dbg_end_of_pass(c.dbg, c.s);
 #endif
   }
   HIP_TRY(e, join.run());

@@ -80,12 +80,6 @@ dim3 tile_grid(int w, int h, int tw, int th, int batch) {
   return dim3((unsigned)((w + tw - 1) / tw), (unsigned)((h + th - 1) / th), (unsigned)batch);
 }
 
-// Hands out the byte offsets of a workspace's parts in order, each on a 256-byte boundary; `end` is the total so far.
-struct Carve {
-  size_t end = 0;
-  size_t take(size_t bytes) { const size_t at = end; end = align_up(end + bytes, 256); return at; }
-};
-
 }  // namespace
 
 // One C block to the end of the file: the entry points, and next to each family its own checks and layouts (static).

@@ -1,13 +1,10 @@
 #!/bin/bash
 # Phase ablations of conv3x3_ws_kernel: builds the library with -DUNETPP_WS_DBG, runs the per-layer
 # profile once per UNETPP_WS_DBG value given on the command line, then rebuilds the product library.
-#   bits: 1 no interpolation, 2 no halo / low-res DMA, 4 no MFMAs, 8 no slab DMA, 16 no consumer work at all,
-#         32 corner reads of the interpolation in the old (2-way conflicting) order, 64 interpolation without split + stores,
-#         128 no DMA wait, 256 no epilogue, 512 interpolation without corner reads; bits 10-11 producer s_setprio,
-#         12-13 consumer s_setprio; 16384 halo DMA with a pixel's units on neighbouring lanes; 262144 epilogue without its global stores; 32768 stamps inside the
-#         interpolation (scripts/ws_stamps.sh).  Results are garbage -- and so are the operands of later layers: the
-#         chip's clock depends on the data, compare a layer only with itself.
-# usage (on the GPU box, from the repo root): [PREC=exact8] [BATCH=1] [LAYERS='conv1_3\|conv0_4'] scripts/ws_ablate.sh 0 1 4 256 ...
+#   The values are sums of the bits of enum WsDbgBit in unet-_amd/csrc/ws_dbg_dev.h, the one table of them.  Results are
+#   garbage -- and so are the operands of later layers: the chip's clock depends on the data, compare a layer only with
+#   itself.
+# usage (on the GPU box, from the repo root): [PREC=exact8] [BATCH=1] [LAYERS='conv1_3\|conv0_4'] scripts/ws_ablate.sh <value> ...
 set -e
 cd "$(dirname "$0")/.."
 python -c 'from unet_amd import _lib; _lib.build(defines=["UNETPP_WS_DBG=1"])'

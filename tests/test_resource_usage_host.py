@@ -28,10 +28,15 @@ FLAGSHIP = [
 
 
 @pytest.fixture(scope="module")
-def kernels():
+def ru():
     spec = importlib.util.spec_from_file_location("resource_usage", os.path.join(ROOT, "scripts", "resource_usage.py"))
     ru = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(ru)
+    return ru
+
+
+@pytest.fixture(scope="module")
+def kernels(ru):
     table = ru.parse_remarks(ru.compile_remarks())
     print(ru.table(table, ["conv3x3_ws", "tapmm_ws_kernel"]))
     return table
@@ -57,3 +62,10 @@ def test_no_wave_specialised_kernel_uses_scratch_or_loses_occupancy(kernels):
     assert len(ws) >= 18
     for n, k in ws.items():
         assert k["vgpr_spill"] == 0 and k["scratch"] == 0 and k["occupancy"] == 2, (n, k)
+
+
+def test_measurement_build_compiles_the_same_kernels(ru, kernels):
+    """-DUNETPP_WS_DBG=1 (csrc/ws_dbg_dev.h, ws_dbg_host.h; scripts/ws_ablate.sh) is built by hand and rarely: it must go on
+    compiling, into the kernels of the product build.  Its registers are its own business (the stamps cost some)."""
+    dbg = ru.parse_remarks(ru.compile_remarks(defines=["UNETPP_WS_DBG=1"]))      # raises if the compile fails
+    assert set(dbg) == set(kernels)

@@ -14,7 +14,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunetpp_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["unetpp_abi.hip", "unetpp_postproc.hip"]      # the engine; the post-processing entry points
-HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "ws_dbg_host.h", "convt2x2_mfma.h", "aux_kernels.h", "frame_kernels.h", "components.h", "distance.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "nlmeans.h", "evaluation.h", "probmap.h", "multiclass.h", "geometry.h", "tiling.h", "roi_loop.h", "loss.h", "contours.h", "simple_loops.h", "raw_frames.h", "two_stage.h", os.path.join("..", "..", "include", "unetpp.h"),
+HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "ws_dbg_dev.h", "ws_dbg_host.h", "convt2x2_mfma.h", "aux_kernels.h",
+           "frame_kernels.h", "components.h", "distance.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "nlmeans.h", "evaluation.h",
+           "probmap.h", "multiclass.h", "geometry.h", "tiling.h", "roi_loop.h", "loss.h", "contours.h", "simple_loops.h", "raw_frames.h",
+           "two_stage.h", os.path.join("..", "..", "include", "unetpp.h"),
            os.path.join("..", "..", "include", "unetpp_roi.h"), os.path.join("..", "..", "include", "unetpp_loss.h"),
            os.path.join("..", "..", "include", "unetpp_contours.h"), os.path.join("..", "..", "include", "unetpp_simple_loops.h"),
            os.path.join("..", "..", "include", "unetpp_raw.h"), os.path.join("..", "..", "include", "unetpp_two_stage.h")]

@@ -35,6 +35,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ws_dbg_dev.h"
+
+// Build-time tunable (scripts/dev/ab_flag.sh passes -D): steps of a chunk over which the narrow tiles (NW == 1) issue the next
+// chunk's loads -- such a chunk takes ~3.4k cycles, less than a loaded HBM round trip, so its loads go out in the first steps
+#ifndef UNETPP_SPREAD_NW1
+#define UNETPP_SPREAD_NW1 3
+#endif
+
 namespace unetpp {
 
 typedef _Float16 half_t;
@@ -125,6 +133,15 @@ __device__ __forceinline__ void apply_rule(int rule, float p0, float p1, float p
     tape = cand_t && p2 >= p1 + ctm;
     if (cable && tape) { cable = p1 >= p2; tape = !cable; }
   }
+}
+
+// The dynamic LDS tail behind a conv kernel's fixed regions (its Cfg::LDS_BYTES), for the kernels and their launch sites.  Byte
+// offsets from the tail's start: the (scale, bias) table of all Cout channels at 0, the fused head's [C][32] weights and [C]
+// biases at `head` (head_C = 0: no head), `extra_bytes` more at `extra` (conv3x3_ws.h: the up-rows edge buffer); `bytes` in all.
+struct LdsTail { int head, extra, bytes; };
+__host__ __device__ constexpr LdsTail lds_tail(int Cout, int head_C, int extra_bytes = 0) {
+  const int head = Cout * 8, extra = head + ((head_C * 33 * 4 + 15) / 16) * 16;
+  return {head, extra, extra + extra_bytes};
 }
 
 template <int P, int KC, int NW, int MW, int WAVES, bool UPF = false>
@@ -351,9 +368,11 @@ __device__ __forceinline__ void pack_store_octets(const float (&v)[16], half_t* 
 
 // The same for accumulators of weights packed with rows8 (weight_pack_kernel): registers 0..7 are channels 8 h .. 8 h + 7
 // of the tile's first record, registers 8..15 the same eight of the second -- the stores of pack_store_octets without
-// its exchange between the half-waves.
+// its exchange between the half-waves.  dbg_nostore, dbg_coalesced: WS_EPI_NO_STORE, WS_EPI_COALESCED of a measurement build
+// (ws_dbg_dev.h); constant false, and their branches dead, everywhere else.
 template <int P, bool X8 = false>
-__device__ __forceinline__ void pack_store_rows8(const float (&v)[16], half_t* dst, size_t blk_stride, bool ok, int h, bool dbg_nostore = false, bool dbg_coalesced = false) {
+__device__ __forceinline__ void pack_store_rows8(const float (&v)[16], half_t* dst, size_t blk_stride, bool ok, int h,
+                                                 bool dbg_nostore = false, bool dbg_coalesced = false) {
 #pragma unroll
   for (int pi = 0; pi < 2; ++pi) {
     unsigned wh[4], wl[4];
@@ -371,7 +390,6 @@ __device__ __forceinline__ void pack_store_rows8(const float (&v)[16], half_t* d
         wh[i] = __builtin_bit_cast(unsigned, ph);
       }
     }
-#ifdef UNETPP_WS_DBG
     if (dbg_nostore) {      // timing experiment: the whole epilogue except its global stores
       asm volatile("" :: "v"(wh[0]), "v"(wh[1]), "v"(wh[2]), "v"(wh[3]));
       if (P == 2) asm volatile("" :: "v"(wl[0]), "v"(wl[1]), "v"(wl[2]), "v"(wl[3]));
@@ -386,7 +404,6 @@ __device__ __forceinline__ void pack_store_rows8(const float (&v)[16], half_t* d
       }
       continue;
     }
-#endif
     if (ok) {
       // (streaming `nt` stores here: one frame per call 2 % sooner in the layer table, nothing in bench.py's median, batch 16 0.6-1 %
       // later -- also as a per-launch switch for small launches; not kept.  profiles/r03_halo_nt_ab.txt)
@@ -653,9 +670,10 @@ void conv3x3_bias_relu_kernel(ConvArgs a) {
 
   // per-channel (scale, bias) of the whole layer staged once per workgroup: the epilogue then reads them
   // from LDS (broadcast reads) instead of exposing a global-load latency per tile
-  float2* sb_lds = (float2*)(smem + C::LDS_BYTES);
+  char* const tail = smem + C::LDS_BYTES;
+  float2* sb_lds = (float2*)tail;
   for (int i = tid; i < a.Cout; i += NT) sb_lds[i] = make_float2(a.scale[i], a.bias[i]);
-  float* head_lds = (float*)(smem + C::LDS_BYTES + a.Cout * 8);   // HEAD only: [C][32] weights then [C] biases
+  float* head_lds = (float*)(tail + lds_tail(a.Cout, 0).head);   // HEAD only: [C][32] weights then [C] biases
   if (HEAD) {
     static_assert(!HEAD || (NW == 1 && !POOL), "the fused head needs all 32 channels of x0_4 in one tile");
     for (int i = tid; i < a.head_C * 32; i += NT) head_lds[i] = a.head_w[i];
@@ -713,11 +731,8 @@ void conv3x3_bias_relu_kernel(ConvArgs a) {
       const char* halo = cur;
       const char* slab = cur + C::HALO_BYTES;
       constexpr int NSTEPS = 9 * (KC / 16);
-#ifndef UNETPP_SPREAD_NW1
-#define UNETPP_SPREAD_NW1 3
-#endif
-      // narrow tiles (NW == 1) finish a chunk in ~3.4k cycles, less than a loaded HBM round trip: their
-      // loads go out in the first steps; wide tiles spread them over the whole chunk
+      // narrow tiles send their loads out in the first steps (UNETPP_SPREAD_NW1, top of the file); wide tiles spread them
+      // over the whole chunk
       constexpr int SPREAD = (NW == 1) ? UNETPP_SPREAD_NW1 : NSTEPS - 1;
       constexpr int HPS = (ITERS + SPREAD - 1) / SPREAD;          // halo items issued per step
       constexpr int DPS = (DMA_PER_WAVE + SPREAD - 1) / SPREAD;   // DMA pieces issued per step

@@ -31,7 +31,16 @@
 // the consumers through LDS; a layer of two chunks and one channel tile keeps its weight slabs in LDS; the first tap
 // of a tile starts from the MFMA's zero operand; C0F -- the producers compute conv0_0.conv1 themselves (below).
 // Built with -fno-slp-vectorize (unet-_amd/_lib.py): packed fp32 VALU instructions are 5-10x slower beside the
-// consumers' MFMA stream.  Measurement builds (-DUNETPP_WS_DBG): phase ablations and in-kernel phase stamps.
+// consumers' MFMA stream.  Measurement builds (-DUNETPP_WS_DBG): phase ablations and in-kernel phase stamps, behind the
+// WS_* hooks of ws_dbg_dev.h.
+//
+// LDS map (WsCfg states every offset once; a launch asks for LDS_BYTES + tail().bytes):
+//   0          stage buffer 0: halo image (HALO_BYTES; a piece's lo plane LO_PLANE behind its hi plane), then at SLAB_OFF the
+//              weight slab (SLAB_BYTES; its lo plane, or the X8 pair weights, SLAB_MAIN further on)
+//   BUF_BYTES  stage buffer 1, the same
+//   LS_OFF     UPF: two low-res staging buffers (LS_BYTES each)           PATCH_OFF  C0F: two input patches (PATCH_BYTES each)
+//   STG_OFF    HANDOFF: one accumulator pair per consumer wave (STG_WAVE each)
+//   LDS_BYTES  the dynamic tail (tail()): (scale, bias) of all Cout channels | HEAD: head weights and biases | UR: edge buffer
 //
 // EXACT8 (template parameter X8; include/unetpp.h UNETPP_PREC_EXACT8): the split product  x w = hi wh + lo wh + x wl  with
 // the main term in fp16 (one v_mfma_f32_32x32x16_f16 per tap and 16 channels) and BOTH cross terms of TWO taps in one
@@ -46,6 +55,14 @@
 // consumers' epilogue.
 #pragma once
 #include "conv3x3_mfma.h"
+
+// Build-time tunables of the fused first block's producers (C0F; scripts/dev/ab_flag.sh passes -D):
+#ifndef UNETPP_C0_PRIO      // their s_setprio level (0: none).  The matrix pipe serves the older (consumer) wave first: without a
+#define UNETPP_C0_PRIO 1    // higher priority the producers' few MFMAs wait until the consumers stall
+#endif
+#ifndef UNETPP_C0_GB        // 16-pixel groups per batch: all operand reads of a batch first, then its MFMAs, then its epilogues
+#define UNETPP_C0_GB 2
+#endif
 
 namespace unetpp {
 
@@ -81,7 +98,16 @@ struct WsCfg {
   // the consumers already multiply the next tile -- two waves per SIMD issue the epilogue's VALU work instead of one.
   static constexpr bool HANDOFF = !UPF && !C0F;
   static constexpr int STG_WAVE = 2 * 16 * 64 * 4, STG_BYTES = HANDOFF ? NCONS * STG_WAVE : 0;
-  static constexpr int LDS_BYTES = 2 * BUF_BYTES + 2 * LS_BYTES + 2 * PATCH_BYTES + STG_BYTES;
+  // the LDS map (file header): stage s at s * BUF_BYTES, its slab at SLAB_OFF; the region pairs; LDS_BYTES = the fixed part
+  static constexpr int SLAB_OFF = HALO_BYTES, LS_OFF = 2 * BUF_BYTES, PATCH_OFF = LS_OFF + 2 * LS_BYTES;
+  static constexpr int STG_OFF = PATCH_OFF + 2 * PATCH_BYTES, LDS_BYTES = STG_OFF + STG_BYTES;
+  static constexpr int LO_PLANE = KG * PPP * 16;      // halo image: from a unit's hi plane to its lo plane, within a piece
+  // the dynamic tail behind LDS_BYTES (lds_tail, conv3x3_mfma.h); its `extra` is the up-rows edge buffer: four accumulators,
+  // (k0 - 1; dy -1, 0) from waves 0, 1, (k0 + 8; dy 0, +1) from waves 2, 3
+  static constexpr int UR_EDGE_BYTES = 4 * 4096;
+  __host__ __device__ static constexpr LdsTail tail(int Cout, int head_C, bool uprows) {
+    return lds_tail(Cout, head_C, uprows ? UR_EDGE_BYTES : 0);
+  }
   // interpolation items: 2x2 halo blocks x channel quads
   static constexpr int BLK_Y = (TH + 2) / 2, BLK_X = HALO_W / 2, UP_ITEMS = BLK_Y * BLK_X * 4;
   static constexpr int UP_ROUNDS = (UP_ITEMS + NPROD * 64 - 1) / (NPROD * 64);
@@ -90,6 +116,8 @@ struct WsCfg {
 
 typedef int int4v __attribute__((ext_vector_type(4)));
 typedef int int8v __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 // Workgroup barrier that orders LDS traffic only: unlike __syncthreads() it does not wait for this wave's global
 // stores (vmcnt), so a consumer's epilogue stores keep draining while it already multiplies the next tile.
@@ -145,11 +173,7 @@ __device__ __forceinline__ void ws_epilogue(KernArgs<ConvArgs> a, const float16v
       const bool ok = gy < H && gx < W;
       const size_t blk = (size_t)H * W * P * 16;
       half_t* dst = a->out + ((size_t)n * nbo + (cbase >> 4)) * blk + ((size_t)gy * W + gx) * P * 16;
-#ifdef UNETPP_WS_DBG
-      pack_store_rows8<P, X8>(v[m], dst, blk, ok, h, (a->dbg & 262144) != 0, (a->dbg & 524288) != 0);
-#else
-      pack_store_rows8<P, X8>(v[m], dst, blk, ok, h);
-#endif
+      pack_store_rows8<P, X8>(v[m], dst, blk, ok, h, WS_OFF(a->dbg, WS_EPI_NO_STORE), WS_OFF(a->dbg, WS_EPI_COALESCED));
     }
   } else {
     // logits[c] = b[c] + sum_co x0_4[co] * Wf[c][co] in fp32: a lane holds 16 of a pixel's 32 channels, lane ^ 32 the
@@ -233,11 +257,7 @@ __device__ __forceinline__ void ws_epilogue(KernArgs<ConvArgs> a, const float16v
       const bool ok = ((lane & 1) == 0) && py < Hp && px < Wp;
       const size_t blk = (size_t)Hp * Wp * P * 16;
       half_t* dst = a->pool_out + ((size_t)n * nbo + (cbase >> 4)) * blk + ((size_t)py * Wp + px) * P * 16;
-#ifdef UNETPP_WS_DBG
-      pack_store_rows8<P, X8>(pv, dst, blk, ok, h, (a->dbg & 262144) != 0);
-#else
-      pack_store_rows8<P, X8>(pv, dst, blk, ok, h);
-#endif
+      pack_store_rows8<P, X8>(pv, dst, blk, ok, h, WS_OFF(a->dbg, WS_EPI_NO_STORE));
     }
   }
 }
@@ -286,7 +306,6 @@ __host__ __device__ constexpr int ur_row(int m, int dy) { return (m + dy + 1) / 
 // exchange slots (one accumulator, 4 KB each) of the boundary between waves b and b + 1: 0, 1 = (k0 + 2 b + 1; dy -1, 0) going up
 // to wave b + 1, 2, 3 = (k0 + 2 b + 2; dy 0, +1) going down to wave b
 __host__ __device__ constexpr int ur_slot(int boundary, int i) { return boundary * 4 + i; }
-constexpr int UR_EDGE_BYTES = 4 * 4096;      // LDS behind the scale / bias table: (k0 - 1; dy -1, 0) from waves 0, 1, (k0 + 8; dy 0, +1) from waves 2, 3
 
 // fraction of the bilinear x2 upsample (align_corners=True) at destination index `dst` whose lower source index is `i0`
 __device__ __forceinline__ float up_frac(float scale, int dst, int i0) {
@@ -306,9 +325,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
   static_assert(!(POOL && HEAD) && !(UPF && (POOL || HEAD)), "one fused extra per kernel");
   static_assert(!CAT2 || (!UPF && !C0F && !POOL && !HEAD), "two full-resolution sources: the plain kernel only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef UNETPP_WS_DBG
-  const unsigned long long rt_entry = __builtin_amdgcn_s_memrealtime();
-#endif
+  WS_WALLCLOCK(rt_entry)
   touch_kernarg_lines<ConvArgs>();                      // (conv3x3_mfma.h: nine serialised scalar-cache misses otherwise)
 
   const int tid = threadIdx.x;
@@ -327,8 +344,9 @@ __device__ __forceinline__ void conv3x3_ws_body() {
   // (by the CONSUMER waves only, which have nothing else to do until the first chunk has landed: the producers go straight
   // to their first DMA instead of waiting for these loads; the first chunk's barrier publishes the table -- a launch of one
   // tile per CU, i.e. a small batch, is a chain of such latencies)
-  float2* sb_lds = (float2*)(smem + C::LDS_BYTES);
-  float* head_lds = (float*)(smem + C::LDS_BYTES + a->Cout * 8);
+  char* const tail_lds = smem + C::LDS_BYTES;      // the dynamic tail: its offsets from WsCfg::tail
+  float2* sb_lds = (float2*)tail_lds;
+  float* head_lds = (float*)(tail_lds + C::tail(a->Cout, 0, UR).head);
   if (wave < C::NCONS) {
     for (int i = tid; i < a->Cout; i += C::NCONS * 64) sb_lds[i] = make_float2(a->scale[i], a->bias[i]);
     if (HEAD) {
@@ -337,9 +355,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
     }
   }
 
-#ifdef UNETPP_WS_DBG
-  const unsigned long long rt_staged = __builtin_amdgcn_s_memrealtime();
-#endif
+  WS_WALLCLOCK(rt_staged)
   // tile order as in conv3x3_bias_relu_kernel: an XCD (workgroups b, b+8, ...) walks a contiguous run of tiles
   const int G = (int)gridDim.x;
   const int slot = (G % 8 == 0) ? ((int)blockIdx.x % 8) * (G / 8) + (int)blockIdx.x / 8 : (int)blockIdx.x;
@@ -420,10 +436,8 @@ __device__ __forceinline__ void conv3x3_ws_body() {
   auto handoff_on = [&]() { KernArgs<ConvArgs> p = kernargs_again(a); return C::HANDOFF && p->nchunks >= 2 && (!SPLITK || p->ksplit == 1); };
 
   // ---- C0F: patch loader (producer lanes) and the once-per-launch part of the producers' work
-  typedef __attribute__((ext_vector_type(4))) float float4v;
   const int plane_id = tid - C::NCONS * 64;              // 0..255 among the producer lanes (negative: a consumer lane)
   constexpr int PATCH_ELEMS = C::PATCH_FLOATS, PATCH_LOADS = C0F ? (PATCH_ELEMS + C::NPROD * 64 - 1) / (C::NPROD * 64) : 1;
-  const int patch_base = 2 * C::BUF_BYTES + 2 * C::LS_BYTES;
   // patch element e of this lane (e = plane_id + 256 i): which image sample it is (row, col, ch relative to the patch
   // origin) and where it goes in the LDS image [row][col][RGB]; fixed for the whole launch.
   //   float32 NCHW: lanes walk a plane's rows (coalesced);  uint8 NHWC BGR: lanes walk the bytes of a row, RGB = BGR reversed
@@ -476,7 +490,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
   // LDS image [row][col][RGB], one word per sample: fp16 hi in the low half, fp16 lo (= sample - hi) in the high half --
   // split once per tile here instead of once per use (every sample is an operand of up to nine pixels, in two chunks)
   auto patch_store = [&](int buf, const float (&val)[PATCH_LOADS]) {
-    unsigned* pd = (unsigned*)(smem + patch_base + buf * C::PATCH_BYTES);
+    unsigned* pd = (unsigned*)(smem + C::PATCH_OFF + buf * C::PATCH_BYTES);
 #pragma unroll
     for (int i = 0; i < PATCH_LOADS; ++i)
       if (pe_idx[i] >= 0) {
@@ -494,12 +508,12 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       if (piece < 2 * C::SLAB_PIECES) {
         const int c = piece / C::SLAB_PIECES, pc = piece - c * C::SLAB_PIECES;
         glds16((const char*)a->wpk + (size_t)c * C::SLAB_BYTES + pc * 1024, lane * 16,
-               lds_base + c * C::BUF_BYTES + C::HALO_BYTES + pc * 1024);
+               lds_base + c * C::BUF_BYTES + C::SLAB_OFF + pc * 1024);
       }
     }
     // the zero words behind each patch (operand slots 27..31 of a pixel read them) and the first tile's patch
     if (plane_id < 32) {
-      *(float*)(smem + patch_base + PATCH_ELEMS * 4 + (plane_id & 15) * 4 + (plane_id >> 4) * C::PATCH_BYTES) = 0.f;
+      *(float*)(smem + C::PATCH_OFF + PATCH_ELEMS * 4 + (plane_id & 15) * 4 + (plane_id >> 4) * C::PATCH_BYTES) = 0.f;
     }
     int n0, y00, x00;
     decode(slot, n0, y00, x00);
@@ -510,37 +524,11 @@ __device__ __forceinline__ void conv3x3_ws_body() {
   }
   if (C0F) __syncthreads();                              // C0F: slabs, zero words and the first patch visible to all producer waves
 
-#ifdef UNETPP_WS_DBG
-#define WS_STAMP(i) { const unsigned long long now_ = __builtin_readcyclecounter(); st_sum[i] += now_ - st_t; st_t = now_; \
-                      if (ev_ptr && ev_ptr < ev_end) *ev_ptr++ = ((unsigned long long)(i) << 56) | __builtin_amdgcn_s_memrealtime(); }
-// event log of one wave per role (dbg bit 131072, single-layer stamps only): (phase << 56 | 100 MHz wall clock) after every phase, 60 events
-#define WS_EVLOG(role) unsigned long long* ev_ptr = (a->stamps && (a->dbg & 131072) && lane == 0 && blockIdx.x < 1024) ? a->stamps + (size_t)1024 * 32 + ((size_t)blockIdx.x * 2 + (role)) * 64 : nullptr; \
-                       unsigned long long* const ev_end = ev_ptr + 60; if (ev_ptr) *ev_ptr++ = (63ull << 56) | rt_entry;
-#define WS_STAMP_IN(i) if (a->dbg & 32768) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); WS_STAMP(i) __builtin_amdgcn_sched_barrier(0); }
-#define WS_EVT(i) { if (ev_ptr && ev_ptr < ev_end) *ev_ptr++ = ((unsigned long long)(i) << 56) | __builtin_amdgcn_s_memrealtime(); }
-#else
-#define WS_STAMP(i) {}
-#define WS_STAMP_IN(i) {}
-#define WS_EVT(i) {}
-#endif
   if (C0F && wave >= C::NCONS) {
     // =============================================================== producers, fused first block
     const int pw = wave - C::NCONS;
-#ifdef UNETPP_WS_DBG
-    // stamps: [0] patch prefetch issue, [1] conv1 groups, [2] patch store, [3] barrier
-    unsigned long long st_sum[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long st_t = __builtin_readcyclecounter();
-    WS_EVLOG(1)
-    if (pw != 0) ev_ptr = nullptr;
-#endif
-#ifndef UNETPP_C0_PRIO
-#define UNETPP_C0_PRIO 1
-#endif
-    // the matrix pipe serves the older (consumer) wave first: without a higher priority the producers' few MFMAs wait
-    // until the consumers stall
+    WS_ROLE_BEGIN(1, pw == 0, WS_CYCLES, 0)      // stamps: [0] patch prefetch issue, [1] conv1 groups, [2] patch store, [3] barrier
     if (UNETPP_C0_PRIO) __builtin_amdgcn_s_setprio(UNETPP_C0_PRIO);
-    typedef __attribute__((ext_vector_type(4))) float f32x4;
-    typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
     const int pxl = lane & 15, kq = lane >> 4;
     // packed conv1 weights: A fragments of this lane (row = output channel pxl of the half, k = 8 kq .. 8 kq + 7)
     half8 wa_h[2], wa_l[2];
@@ -568,7 +556,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       int n, y0, x0;
       decode(tile, n, y0, x0);
       const int tbuf = (g >> 1) & 1;                                     // patch buffer of this tile (two chunks per tile)
-      const char* patch = smem + patch_base + tbuf * C::PATCH_BYTES;
+      const char* patch = smem + C::PATCH_OFF + tbuf * C::PATCH_BYTES;
       const int zero_off = PATCH_ELEMS * 4;
 #pragma unroll
       for (int c = 0; c < 2; ++c, ++g) {                 // unrolled: c indexes register arrays
@@ -587,9 +575,6 @@ __device__ __forceinline__ void conv3x3_ws_body() {
         // groups in batches of GB: all operand reads of a batch first, then its MFMAs, then its epilogues, so that the
         // LDS latency and the three dependent MFMAs of one group hide behind the other groups' work (patch reads and
         // halo-image writes go through the same LDS pointer: the compiler would not reorder them by itself)
-#ifndef UNETPP_C0_GB
-#define UNETPP_C0_GB 2
-#endif
         constexpr int GB = UNETPP_C0_GB;
         static_assert(C::C0_ITERS % GB == 0, "group batches");
         // this lane's pixel of group pw + 4 it: hp = 16 (pw + 4 it) + pxl, advanced by 64 halo pixels per group; in the
@@ -655,7 +640,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
               if (valid) {
                 char* dst = himg + gi * 1024 + dst_lane;
                 *(u32x2*)dst = (u32x2){oh0, oh1};
-                *(u32x2*)(dst + KG * PPP * 16) = (u32x2){ol0, ol1};
+                *(u32x2*)(dst + C::LO_PLANE) = (u32x2){ol0, ol1};
               }
             }
           }
@@ -670,37 +655,26 @@ __device__ __forceinline__ void conv3x3_ws_body() {
         WS_STAMP(3)
       }
     }
-#ifdef UNETPP_WS_DBG
-    if (a->stamps && pw == 0 && lane == 0)
-#pragma unroll
-      for (int i = 0; i < 11; ++i) a->stamps[((size_t)blockIdx.x * 2 + 1) * 16 + i] = st_sum[i];
-    if (a->stamps && pw == 0 && lane == 0) a->stamps[((size_t)blockIdx.x * 2 + 1) * 16 + 12] = __builtin_amdgcn_s_memrealtime();
-#endif
+    WS_ROLE_END(1, pw == 0, 11, 12, )
     return;
   }
 
   if (wave >= C::NCONS) {
     // =============================================================== producers
     const int pw = wave - C::NCONS;
-#ifdef UNETPP_WS_DBG
-    const unsigned long long rt_prod = __builtin_amdgcn_s_memrealtime();
-    { const int pr = (a->dbg >> 10) & 3; if (pr == 1) __builtin_amdgcn_s_setprio(1); else if (pr == 2) __builtin_amdgcn_s_setprio(2); else if (pr == 3) __builtin_amdgcn_s_setprio(3); }
-#endif
+    WS_WALLCLOCK(rt_prod)
+    WS_PRIO(WS_PRIO_PROD)
     constexpr unsigned OOB = 0x80000000u;                // beyond num_records: the buffer load returns zeros
     constexpr int ITERS = C::HALO_ITERS;
     // tile-invariant: halo pixel / unit of this lane in each of its DMA pieces (as in conv3x3_bias_relu_kernel)
     int my_u = lane / PPP;
-#ifdef UNETPP_WS_DBG
-    if (a->dbg & 16384) my_u = lane % C::U;               // timing experiment: a pixel's units on neighbouring lanes (results garbage)
-#endif
+    if (WS_OFF(a->dbg, WS_UNITS_ON_LANES)) my_u = lane % C::U;
     const int my_pl = my_u / KG, my_k8 = (my_u % KG) * 8;
     int hyx[ITERS];
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
       int hp = (pw + it * C::NPROD) * PPP + lane % PPP;
-#ifdef UNETPP_WS_DBG
-      if (a->dbg & 16384) hp = (pw + it * C::NPROD) * PPP + lane / C::U;
-#endif
+      if (WS_OFF(a->dbg, WS_UNITS_ON_LANES)) hp = (pw + it * C::NPROD) * PPP + lane / C::U;
       const int hy = hp / HALO_W, hx = hp - hy * HALO_W;
       hyx[it] = (hp < C::NHALO) ? ((hy << 8) | hx) : -1;
     }
@@ -738,9 +712,10 @@ __device__ __forceinline__ void conv3x3_ws_body() {
     // blocks 4..7 -- all 64 banks once, instead of every bank twice; two separate ds_read_b64 (2 LDS cycles each)
     // also replace the ds_read2_b64 the compiler forms from a fixed +32 offset (8 cycles, banked modulo 32).
     int rd_swap = (P == 2 && !X8 && (lane & 16)) ? 32 : 0;      // (X8: hi and the 8-bit planes are not interchangeable)
-#ifdef UNETPP_WS_DBG
-    if (a->dbg & 32) rd_swap = 0;
-#endif
+    if (WS_OFF(a->dbg, WS_NO_RD_SWAP)) rd_swap = 0;
+    // HALO ADDRESS, written out at five sites (as a function or a lambda it changes the registers of every kernel here): byte
+    // offset of unit u (plane * KG + k-group) of halo pixel hp in a halo image = (hp / PPP) * 1024 + (u * PPP + hp % PPP) * 16 --
+    // 1 KB pieces of [unit][PPP pixels][16 bytes] (conv3x3_mfma.h).  A channel quad q is half a unit: u = q >> 1, + (q & 1) * 8.
     if (UR) {
       // item = (row of T, column block, channel quad): the block's two pixels of that row, [0], [1] (q >= 2: in the opposite order)
 #pragma unroll
@@ -762,8 +737,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
         const int q = i & 3, blk = i >> 2;
         const int by = blk / C::BLK_X, bx = blk - by * C::BLK_X;
         const int hp0 = (2 * by) * HALO_W + 2 * bx;       // first pixel of the block; right neighbour hp0 + 1, the row below hp0 + HALO_W
-        // byte offset of channel quad q of halo pixel hp, plane 0: (hp / PPP) * 1024 + ((q >> 1) * PPP + hp % PPP) * 16 + (q & 1) * 8.
-        // Lanes of the second channel octet (q >= 2) take the block's two columns in the opposite order (see setup_tile).
+        // (HALO ADDRESS, above.)  Lanes of the second channel octet (q >= 2) take the block's two columns in the opposite order (see setup_tile).
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
           const int hp = hp0 + (px >> 1) * HALO_W + ((px & 1) ^ ((q >> 1) & 1));
@@ -789,7 +763,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
     // the low-res records of up chunk j (channel block j of in1) into staging buffer j & 1; inside an M0 run
     auto ur_ls_dma = [&](__amdgpu_buffer_rsrc_t rs, const unsigned (&vo)[LSR], int j) {
       const int soffL = j * (int)plane_bytes1;
-      const unsigned dstL = opaque(lds_base + 2 * C::BUF_BYTES + (j & 1) * C::LS_BYTES + pw * 1024);
+      const unsigned dstL = opaque(lds_base + C::LS_OFF + (j & 1) * C::LS_BYTES + pw * 1024);
 #pragma unroll
       for (int it = 0; it < LSR; ++it) {
         const int piece = pw + it * C::NPROD;
@@ -894,23 +868,17 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       }
     };
 
-#ifdef UNETPP_WS_DBG
-    // stamps (macros near the top of the kernel): [0] skip-chunk issue, [1] skip-chunk wait, [2] skip-chunk barrier, [3] up-chunk issue, [4] interpolation,
-    // [5] up-chunk wait, [6] up-chunk barrier, [7] tile setup; with dbg bit 32768 the interpolation is cut into
+    // stamps: [0] skip-chunk issue, [1] skip-chunk wait, [2] skip-chunk barrier, [3] up-chunk issue, [4] interpolation,
+    // [5] up-chunk wait, [6] up-chunk barrier, [7] tile setup; with WS_STAMP_INNER the interpolation is cut into
     // [8] corner reads issued and landed, [9] arithmetic, [10] stores issued and retired (instead of [4])
-    unsigned long long st_sum[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long st_t = 0;
-    WS_EVLOG(1)
-    if (pw != 0) ev_ptr = nullptr;
-    if (ev_ptr) { *ev_ptr++ = (48ull << 56) | rt_staged; *ev_ptr++ = (49ull << 56) | rt_prod; }
+    WS_ROLE_BEGIN(1, pw == 0, 0, 0)
+    WS_EVT_AT2(48, rt_staged, 49, rt_prod)
     WS_EVT(50)
-#endif
     // all interpolation items of this lane for up-chunk c: staging buffer (c & 1) -> halo image.  Straight-line code
     // for all rounds (the LDS reads of every round are issued before the first value is needed; a lane without an
     // item in the last round computes on clamped addresses and skips only the stores).
     auto up_rounds = [&](int c, int halo_off) {
-      typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-      const char* ls = smem + 2 * C::BUF_BYTES + (c & 1) * C::LS_BYTES;
+      const char* ls = smem + C::LS_OFF + (c & 1) * C::LS_BYTES;
       u32x2 hq[UPR][4], lq[UPR][4];                      // corners (ra,ca), (ra,cb), (rb,ca), (rb,cb): 4 channels each
 #pragma unroll
       for (int r = 0; r < UPR; ++r) {
@@ -918,9 +886,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
         const int off[4] = {up_o00[r], up_o01[r], up_o10[r], o11};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-#ifdef UNETPP_WS_DBG
-          if (a->dbg & 512) { hq[r][k] = (u32x2){0x3c003c00u, 0x3c003c00u}; lq[r][k] = (u32x2){0u, 0u}; continue; }
-#endif
+          if (WS_OFF(a->dbg, WS_NO_CORNER_READ)) { hq[r][k] = (u32x2){0x3c003c00u, 0x3c003c00u}; lq[r][k] = (u32x2){0u, 0u}; continue; }
           hq[r][k] = *(const u32x2*)(ls + off[k]);
           if (P == 2) lq[r][k] = *(const u32x2*)(ls + (off[k] ^ 32));
         }
@@ -964,9 +930,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
           }
         }
         WS_STAMP_IN(9)
-#ifdef UNETPP_WS_DBG
-        if (a->dbg & 64) { if (v[0][0] == 12345.f && v[3][3] == 7.f && v[1][2] == 3.f && v[2][1] == 9.f) a->status[1] = 1; continue; }
-#endif
+        if (WS_OFF(a->dbg, WS_NO_UP_STORE)) { if (v[0][0] == 12345.f && v[3][3] == 7.f && v[1][2] == 3.f && v[2][1] == 9.f) a->status[1] = 1; continue; }
         if (up_st[r][0] >= 0) {
 #pragma unroll
           for (int ky = 0; ky < 2; ++ky)
@@ -986,7 +950,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
               const u32x2 oh = {h0, h1}, ol = {l0, l1};
               char* dst = smem + halo_off + up_st[r][px];
               *(u32x2*)dst = oh;
-              if (P == 2) *(u32x2*)(dst + KG * PPP * 16) = ol;
+              if (P == 2) *(u32x2*)(dst + C::LO_PLANE) = ol;
             }
         }
         WS_STAMP_IN(10)
@@ -995,8 +959,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
 
     // UR: the same for the image T of up chunk j -- x-interpolation only, two corners and two pixels per item
     auto up_rows_rounds = [&](int j, int halo_off) {
-      typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-      const char* ls = smem + 2 * C::BUF_BYTES + (j & 1) * C::LS_BYTES;
+      const char* ls = smem + C::LS_OFF + (j & 1) * C::LS_BYTES;
       u32x2 hq[UPR][2], lq[UPR][2];                      // corners (r, ca), (r, cb): 4 channels each
 #pragma unroll
       for (int r = 0; r < UPR; ++r) {
@@ -1032,7 +995,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
             split_pack2(v[kx][2], v[kx][3], h1, l1);
             char* dst = smem + halo_off + up_st[r][kx];
             *(u32x2*)dst = (u32x2){h0, h1};
-            *(u32x2*)(dst + KG * PPP * 16) = (u32x2){l0, l1};
+            *(u32x2*)(dst + C::LO_PLANE) = (u32x2){l0, l1};
           }
         }
         WS_STAMP_IN(10)
@@ -1040,16 +1003,14 @@ __device__ __forceinline__ void conv3x3_ws_body() {
     };
 
     // HANDOFF: the epilogue of the accumulator pair consumer wave `pw` left in LDS for the previous tile
-    const int stg_base = 2 * C::BUF_BYTES + 2 * C::LS_BYTES + 2 * C::PATCH_BYTES;
     int hn = -1, hty = 0, htx = 0, hct = 0;            // the cursor's digits of that tile (not y0, x0 as well); hn < 0: none yet
     auto handoff_epilogue = [&]() {
-      const char* st = smem + stg_base + pw * C::STG_WAVE + lane * 16;
+      const char* st = smem + C::STG_OFF + pw * C::STG_WAVE + lane * 16;
       float16v pair[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          typedef __attribute__((ext_vector_type(4))) float f32x4;
           const f32x4 v4 = *(const f32x4*)(st + (i * 4 + q) * 1024);
           pair[i][4 * q] = v4[0]; pair[i][4 * q + 1] = v4[1]; pair[i][4 * q + 2] = v4[2]; pair[i][4 * q + 3] = v4[3];
         }
@@ -1059,9 +1020,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       ws_epilogue<P, 2, POOL, HEAD, X8>(kernargs_again(a), pair, sb_lds, head_lds, hn, gy0, htx * TW, cbase, lane);
     };
     int g = 0;                                           // global chunk counter: chunk g -> stage buffer g & 1
-#ifdef UNETPP_WS_DBG
-    st_t = __builtin_readcyclecounter();
-#endif
+    WS_RESTART
     WS_EVT(51)
     decode_first(slot);
     // UR: the low-res records of a tile's first up chunk, for the tile the cursor stands on (an M0 run of its own)
@@ -1104,38 +1063,34 @@ __device__ __forceinline__ void conv3x3_ws_body() {
         // addresses per stage) and spills them into vector lanes, to be read back in front of each DMA instruction.
         const unsigned dst0 = opaque(lds_base + buf + pw * 1024);
         const unsigned m0_keep = m0_run_begin();         // one save / restore of M0 for all DMA pieces of the chunk
-#ifdef UNETPP_WS_DBG
-        if (!(a->dbg & 2))
-#endif
-        if (c < nch0) {
-          const int soff = c * (int)plane_bytes0;
+        if (!WS_OFF(a->dbg, WS_NO_HALO_DMA)) {
+          if (c < nch0) {
+            const int soff = c * (int)plane_bytes0;
 #pragma unroll
-          for (int it = 0; it < ITERS; ++it) {
-            const int piece = pw + it * C::NPROD;
-            if (it + 1 < ITERS || C::HALO_PIECES % C::NPROD == 0 || piece < C::HALO_PIECES)      // (only a wave's last piece can be missing)
-              blds16_run<true>(rsrc0, voff0[it], soff, dst0 + it * (C::NPROD * 1024));
-          }
-        } else if (CAT2) {                               // chunk of the second full-resolution source
-          const int soff = (c - nch0) * (int)plane_bytes0;
+            for (int it = 0; it < ITERS; ++it) {
+              const int piece = pw + it * C::NPROD;
+              if (it + 1 < ITERS || C::HALO_PIECES % C::NPROD == 0 || piece < C::HALO_PIECES)      // (only a wave's last piece can be missing)
+                blds16_run<true>(rsrc0, voff0[it], soff, dst0 + it * (C::NPROD * 1024));
+            }
+          } else if (CAT2) {                               // chunk of the second full-resolution source
+            const int soff = (c - nch0) * (int)plane_bytes0;
 #pragma unroll
-          for (int it = 0; it < ITERS; ++it) {
-            const int piece = pw + it * C::NPROD;
-            if (it + 1 < ITERS || C::HALO_PIECES % C::NPROD == 0 || piece < C::HALO_PIECES)      // (only a wave's last piece can be missing)
-              blds16_run<true>(rsrc1, voff0[it], soff, dst0 + it * (C::NPROD * 1024));
+            for (int it = 0; it < ITERS; ++it) {
+              const int piece = pw + it * C::NPROD;
+              if (it + 1 < ITERS || C::HALO_PIECES % C::NPROD == 0 || piece < C::HALO_PIECES)
+                blds16_run<true>(rsrc1, voff0[it], soff, dst0 + it * (C::NPROD * 1024));
+            }
           }
         }
         // A layer of two chunks and one channel tile keeps its weights: chunk c of every tile lands in stage c, so the
         // slabs this workgroup loaded for its first tile are still there (a third of the bytes and DMA pieces saved).
-#ifdef UNETPP_WS_DBG
-        if (!(a->dbg & 8))
-#endif
-        if (!(slabs_stay && g >= 2)) {
+        if (!WS_OFF(a->dbg, WS_NO_SLAB_DMA) && !(slabs_stay && g >= 2)) {
           const char* wchunk = opaque(wsrc + (size_t)c * C::SLAB_BYTES + pw * 1024);
 #pragma unroll
           for (int it = 0; it < C::SLAB_ITERS; ++it) {
             const int piece = pw + it * C::NPROD;
             if (it + 1 < C::SLAB_ITERS || C::SLAB_PIECES % C::NPROD == 0 || piece < C::SLAB_PIECES)
-              glds16_run(wchunk + it * (C::NPROD * 1024), lane * 16, dst0 + C::HALO_BYTES + it * (C::NPROD * 1024));
+              glds16_run(wchunk + it * (C::NPROD * 1024), lane * 16, dst0 + C::SLAB_OFF + it * (C::NPROD * 1024));
           }
         }
         if (!UPF) { m0_run_end(m0_keep); WS_STAMP(0) }
@@ -1152,12 +1107,9 @@ __device__ __forceinline__ void conv3x3_ws_body() {
           if (cj < nup) up_rows_rounds(cj, buf);
           if (c >= nch0) { WS_STAMP(4) } else { WS_STAMP(0) }
         } else if (UPF) {
-#ifdef UNETPP_WS_DBG
-          if (!(a->dbg & 2))
-#endif
-          if (c + 1 < nchunks && c + 1 >= nch0) {      // low-res records of the NEXT chunk, one iteration ahead
-            const int soffL = (c + 1 - nch0) * (int)plane_bytes1;
-            const unsigned dstL = opaque(lds_base + 2 * C::BUF_BYTES + ((c + 1) & 1) * C::LS_BYTES + pw * 1024);
+          if (!WS_OFF(a->dbg, WS_NO_HALO_DMA) && c + 1 < nchunks && c + 1 >= nch0) {      // low-res records of the NEXT chunk, one iteration ahead
+            const int soffL = (c + 1 - nch0) * (int)plane_bytes1;      // (ur_ls_dma's loop; called from here it changes two kernels)
+            const unsigned dstL = opaque(lds_base + C::LS_OFF + ((c + 1) & 1) * C::LS_BYTES + pw * 1024);
 #pragma unroll
             for (int it = 0; it < LSR; ++it) {
               const int piece = pw + it * C::NPROD;
@@ -1167,16 +1119,10 @@ __device__ __forceinline__ void conv3x3_ws_body() {
           }
           m0_run_end(m0_keep);
           if (c >= nch0) { WS_STAMP(3) } else { WS_STAMP(0) }
-#ifdef UNETPP_WS_DBG
-          if (!(a->dbg & 1))
-#endif
-          if (c >= nch0) up_rounds(c, buf);              // this chunk's halo image from the records that landed last iteration
+          if (!WS_OFF(a->dbg, WS_NO_INTERP) && c >= nch0) up_rounds(c, buf);              // this chunk's halo image from the records that landed last iteration
           if (c >= nch0) { WS_STAMP(4) } else { WS_STAMP(0) }
         }
-#ifdef UNETPP_WS_DBG
-        if (!(a->dbg & 128))
-#endif
-        if (c == handoff_c) handoff_epilogue();     // previous tile's pair: published by the barrier behind chunk 0
+        if (!WS_OFF(a->dbg, WS_NO_HANDOFF_EPI) && c == handoff_c) handoff_epilogue();     // previous tile's pair: published by the barrier behind chunk 0
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA pieces have landed
         if (UPF && c >= nch0) { WS_STAMP(5) } else { WS_STAMP(1) }
         lds_barrier();                                    // chunk g published; the consumers have left buffer (g+1) & 1
@@ -1188,20 +1134,13 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       lds_barrier();                                      // the consumers' last pair is in LDS
       if (hn >= 0) handoff_epilogue();
     }
-#ifdef UNETPP_WS_DBG
-    if (a->stamps && pw == 0 && lane == 0)
-#pragma unroll
-      for (int i = 0; i < 11; ++i) a->stamps[((size_t)blockIdx.x * 2 + 1) * 16 + i] = st_sum[i];
-    if (a->stamps && pw == 0 && lane == 0) a->stamps[((size_t)blockIdx.x * 2 + 1) * 16 + 12] = __builtin_amdgcn_s_memrealtime();
-#endif
+    WS_ROLE_END(1, pw == 0, 11, 12, )
     return;
   }
 
   // ================================================================= consumers
   const int cw = wave;
-#ifdef UNETPP_WS_DBG
-  { const int pr = (a->dbg >> 12) & 3; if (pr == 1) __builtin_amdgcn_s_setprio(1); else if (pr == 2) __builtin_amdgcn_s_setprio(2); else if (pr == 3) __builtin_amdgcn_s_setprio(3); }
-#endif
+  WS_PRIO(WS_PRIO_CONS)
   // lane-constant LDS read offsets: pixel fragment of halo row r (0 .. MW+1 of this wave) shifted by dx
   int a_off[MW + 2][3];
 #pragma unroll
@@ -1209,7 +1148,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
       const int hp = (cw * MW + r) * HALO_W + (lane & 31) + dx;
-      a_off[r][dx] = (hp / PPP) * 1024 + ((lane >> 5) * PPP + hp % PPP) * 16;
+      a_off[r][dx] = (hp / PPP) * 1024 + ((lane >> 5) * PPP + hp % PPP) * 16;      // (HALO ADDRESS, in the producers)
     }
   const int b_lane_off = ((lane >> 5) * BN + (lane & 31)) * 16;
   struct AFrag { half8 h[MW + 2], l[MW + 2]; };
@@ -1219,7 +1158,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
     for (int r = 0; r < MW + 2; ++r) {
       const char* p = halo + a_off[r][dx];
       f.h[r] = *(const half8*)p;
-      if (P == 2) f.l[r] = *(const half8*)(p + KG * PPP * 16);
+      if (P == 2) f.l[r] = *(const half8*)(p + C::LO_PLANE);
     }
   };
   auto load_a_part = [&](AFrag& f, const char* halo, int dx, int r0, int r1) {
@@ -1228,7 +1167,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       if (r >= r0 && r < r1) {
         const char* p = halo + a_off[r][dx];
         f.h[r] = *(const half8*)p;
-        if (P == 2) f.l[r] = *(const half8*)(p + KG * PPP * 16);
+        if (P == 2) f.l[r] = *(const half8*)(p + C::LO_PLANE);
       }
   };
   auto load_b = [&](BFrag& f, const char* slab, int tap) {
@@ -1236,7 +1175,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
     for (int j = 0; j < NW; ++j) {
       const int off = b_lane_off + (tap * KG * BN + j * 32) * 16;
       f.h[j] = *(const half8*)(slab + off);
-      if (P == 2) f.l[j] = *(const half8*)(slab + off + 9 * KC * BN * 2);
+      if (P == 2) f.l[j] = *(const half8*)(slab + off + C::SLAB_MAIN);
     }
   };
   float16v acc[MW][NW];
@@ -1281,7 +1220,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       for (int dx = 0; dx < 3; ++dx) {
         const int tr = r < 2 ? 2 * cw + 1 + r : (2 * cw < C::NCONS ? 0 : C::LSH - 1);
         const int hp = tr * HALO_W + (lane & 31) + dx;
-        t_off[r][dx] = (hp / PPP) * 1024 + ((lane >> 5) * PPP + hp % PPP) * 16;
+        t_off[r][dx] = (hp / PPP) * 1024 + ((lane >> 5) * PPP + hp % PPP) * 16;      // (HALO ADDRESS)
       }
   }
   struct TFrag { half8 h[TR], l[TR]; };
@@ -1294,14 +1233,8 @@ __device__ __forceinline__ void conv3x3_ws_body() {
   };
 
   int g = 0;
-#ifdef UNETPP_WS_DBG
-  unsigned long long st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // [0] barrier, [1] chunk, [2] epilogue, [3] accumulator init (UR: and the fold)
-  unsigned long long st_t = __builtin_readcyclecounter();
-  const unsigned long long rt_begin = __builtin_amdgcn_s_memrealtime();     // 100 MHz, one clock for the whole chip
-  WS_EVLOG(0)
-  if (cw != 0) ev_ptr = nullptr;
-  if (ev_ptr) *ev_ptr++ = (62ull << 56) | rt_begin;
-#endif
+  WS_ROLE_BEGIN(0, cw == 0, WS_CYCLES, WS_WALL)      // stamps: [0] barrier, [1] chunk, [2] epilogue, [3] accumulator init (UR: and the fold)
+  WS_EVT_AT(62, rt_role)
   decode_first(slot);
   if constexpr (UR) lds_barrier();                          // the producers' barrier behind the first tile's low-res records
   for (int tile = slot; tile < tiles_end(); tile += tile_step(), decode_next()) {
@@ -1314,7 +1247,6 @@ __device__ __forceinline__ void conv3x3_ws_body() {
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
         if (!UR && a->zinit && ks == 0) {    // accumulators start from the low-resolution half of the layer (tapmm_ws.h); uniform branch
-          typedef __attribute__((ext_vector_type(4))) float f32x4;
           const int gy = y0 + cw * MW + m, gx = x0 + (lane & 31);
           const bool in = gy < H && gx < W;
           const float* zp = a->zinit + (((size_t)n * (a->Cout >> 5) + ((ct * BN + j * 32) >> 5)) * ((size_t)H * W) + (size_t)gy * W + gx) * 32 + 8 * (lane >> 5);
@@ -1346,10 +1278,8 @@ __device__ __forceinline__ void conv3x3_ws_body() {
         lds_barrier();                                    // chunk g is in stage buffer g & 1
         WS_STAMP(0)
         const char* halo = smem + (g & 1) * C::BUF_BYTES;
-        const char* slab = halo + C::HALO_BYTES;
-#ifdef UNETPP_WS_DBG
-        if (a->dbg & 16) return;
-#endif
+        const char* slab = halo + C::SLAB_OFF;
+        if (WS_OFF(a->dbg, WS_NO_CHUNK)) return;
         // ---- up chunk: 1x3 products on the wave's rows of T into the Y accumulators.  dx-major as below; a step is one tap:
         // one weight fragment against the two (three) row fragments of its column shift, the next step's fragments read first.
         TFrag ft0, ft1;
@@ -1360,7 +1290,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
             if (r >= r0 && r < r1) {
               const char* p = halo + t_off[r][dx];
               f.h[r] = *(const half8*)p;
-              f.l[r] = *(const half8*)(p + KG * PPP * 16);
+              f.l[r] = *(const half8*)(p + C::LO_PLANE);
             }
         };
         load_t(ft0, 0, 0, TR);
@@ -1377,10 +1307,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
             if (step + 1 < 9) load_b(fbn, slab, ((step + 1) % 3) * 3 + (step + 1) / 3);
             if (dx < 2) load_t(ftn, dx + 1, dy, dy + 1);
             __builtin_amdgcn_sched_barrier(0);
-#ifdef UNETPP_WS_DBG
-            if (!(a->dbg & 4))
-#endif
-            {
+            if (!WS_OFF(a->dbg, WS_NO_MFMA)) {
               const bool Z0 = FIRST && dx == 0;           // (a constant once the loops are unrolled)
               ur_mfma(yo[0][dy], fb, ft, 0, Z0);
               ur_mfma(yo[1][dy], fb, ft, 1, Z0);
@@ -1398,11 +1325,10 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       // left the last up chunk's stage buffer, and the producers do not refill it before the second barrier further down.
       lds_barrier();
       WS_STAMP(0)
-      typedef __attribute__((ext_vector_type(4))) float f32x4;
       // slots 0 .. 11 (ur_slot) lie over the stage buffer, the four edge slots behind the scale / bias table (UR_EDGE_BYTES more LDS)
       constexpr int UR_EDGE = 12;
       char* xb0 = smem + ((g - 1) & 1) * C::BUF_BYTES + lane * 16;
-      char* xe = smem + C::LDS_BYTES + a->Cout * 8 - UR_EDGE * 4096 + lane * 16;      // (the table holds all Cout channels, nct tiles of 32)
+      char* xe = tail_lds + C::tail(a->Cout, 0, UR).extra - UR_EDGE * 4096 + lane * 16;
       auto put = [&](int slot, const float16v& v) {
         char* xb = slot >= UR_EDGE ? xe : xb0;
 #pragma unroll
@@ -1465,7 +1391,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) {
           const int hp = (cw * MW + r) * HALO_W + (ln & 31) + dx;
-          a_off[r][dx] = (hp / PPP) * 1024 + ((ln >> 5) * PPP + hp % PPP) * 16;
+          a_off[r][dx] = (hp / PPP) * 1024 + ((ln >> 5) * PPP + hp % PPP) * 16;      // (HALO ADDRESS)
         }
       WS_STAMP(3)
     }
@@ -1473,12 +1399,10 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       if (!(UR && c == ur_nup)) lds_barrier();            // chunk g is in stage buffer g & 1 (UR: the fold has met the first skip chunk's)
       WS_STAMP(0)
       const char* halo = smem + (g & 1) * C::BUF_BYTES;
-      const char* slab = halo + C::HALO_BYTES;
+      const char* slab = halo + C::SLAB_OFF;
       // dx-major walk: the six halo rows of one column shift serve its three taps.  Fragments of the next tap
       // (and, spread over the three taps, the next column shift) are read before this tap's MFMAs.
-#ifdef UNETPP_WS_DBG
-      if (a->dbg & 16) continue;
-#endif
+      if (WS_OFF(a->dbg, WS_NO_CHUNK)) continue;
       if constexpr (X8) {
         // ---- EXACT8 chunk: 9 main-term steps (fp16 hi planes, one 32-cycle MFMA per product) and 5 cross-term steps (one
         // 64-cycle K = 64 MFMA per product and tap PAIR).  Order: column 0, column 1, pairs 0-2 (the taps of columns 0 and 1
@@ -1496,8 +1420,8 @@ __device__ __forceinline__ void conv3x3_ws_body() {
         };
         // 8-bit operand of one pixel row for a tap pair: bytes 0-15 from halo row ra shifted by dxa, bytes 16-31 from (rb, dxb)
         auto load_x = [&](int dxa, int ra, int dxb, int rb) {
-          const int4v lo = *(const int4v*)(halo + a_off[ra][dxa] + KG * PPP * 16);
-          const int4v hi = *(const int4v*)(halo + a_off[rb][dxb] + KG * PPP * 16);
+          const int4v lo = *(const int4v*)(halo + a_off[ra][dxa] + C::LO_PLANE);
+          const int4v hi = *(const int4v*)(halo + a_off[rb][dxb] + C::LO_PLANE);
           return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
         };
         auto load_bm = [&](BM& f, int tap) {
@@ -1513,9 +1437,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
           }
         };
         auto main_step = [&](const BM& b, const half8 (&hf)[R], int dy, bool first) {
-#ifdef UNETPP_WS_DBG
-          if (a->dbg & 4) return;
-#endif
+          if (WS_OFF(a->dbg, WS_NO_MFMA)) return;
           const float16v zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int m = 0; m < MW; ++m)
@@ -1524,9 +1446,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
               acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b.w[j], hf[m + dy], first ? zero : acc[m][j], 0, 0, 0);
         };
         auto cross_step = [&](const BX& b, const int8v (&x)[R], int r0) {
-#ifdef UNETPP_WS_DBG
-          if (a->dbg & (4 | 65536)) return;      // 65536: the cross terms only (how much of a chunk they are)
-#endif
+          if (WS_OFF(a->dbg, WS_NO_MFMA | WS_NO_CROSS)) return;
 #pragma unroll
           for (int m = 0; m < MW; ++m)
 #pragma unroll
@@ -1595,7 +1515,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
         load_bx(bx0, 4);
         int4v cur[MW];
 #pragma unroll
-        for (int m = 0; m < MW; ++m) cur[m] = *(const int4v*)(halo + a_off[m + 2][2] + KG * PPP * 16);
+        for (int m = 0; m < MW; ++m) cur[m] = *(const int4v*)(halo + a_off[m + 2][2] + C::LO_PLANE);
         __builtin_amdgcn_sched_barrier(0);
         cross_step(bx1, xa, 0);      // pair 3: taps (0, 2) + (1, 2)
         __builtin_amdgcn_sched_barrier(0);
@@ -1630,10 +1550,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
           }
           if (dx < 2) load_a_part(fan, halo, dx + 1, 2 * dy, 2 * dy + 2);
           __builtin_amdgcn_sched_barrier(0);
-#ifdef UNETPP_WS_DBG
-          if (!(a->dbg & 4))
-#endif
-          {
+          if (!WS_OFF(a->dbg, WS_NO_MFMA)) {
             if (step == 0 && c == c_begin && from_zero) run_mfma_first(fa, fb);
             else run_mfma(fa, fb, dy);
           }
@@ -1643,9 +1560,7 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       WS_STAMP(1)
     }
     // ---- epilogue from registers, two row pairs; the producers are already filling the next tile's first chunk
-#ifdef UNETPP_WS_DBG
-    if (a->dbg & 256) { if (acc[0][0][0] == 12345.f && acc[MW - 1][NW - 1][5] == 7.f) a->status[1] = 1; continue; }
-#endif
+    if (WS_OFF(a->dbg, WS_NO_EPILOGUE)) { if (acc[0][0][0] == 12345.f && acc[MW - 1][NW - 1][5] == 7.f) a->status[1] = 1; continue; }
     // ---- split-K (a->ksplit > 1; small batches, where a layer has fewer tiles than the chip has CUs): this wave's raw
     // accumulators go to its slot of the partial buffer; a counter per (tile, wave) tells the wave whose partial arrives
     // LAST, and that wave adds all KS partials in the fixed order 0 .. KS-1 (its own included, read back like the others:
@@ -1655,7 +1570,6 @@ __device__ __forceinline__ void conv3x3_ws_body() {
     // last wave reads every partial with sc1 loads.  No release / acquire fence (an agent-scope release writes back the whole
     // L2: measured +30 us per split launch).
     if (KS > 1) {
-      typedef __attribute__((ext_vector_type(4))) float f32x4;
       const int tile_id = tile / KS;                                     // (n, ty, tx, ct): the same for the KS workgroups of a tile
       const int ntile = total_tiles / KS;
       constexpr int WAVE_BYTES = MW * NW * 16 * 64 * 4;
@@ -1714,12 +1628,11 @@ __device__ __forceinline__ void conv3x3_ws_body() {
       for (int j = 0; j < NW; ++j) {
         const bool give = handoff && (MW == 4 ? m2 == 1 : j == 1);      // this pair goes to producer wave cw
         if (give) {
-          char* st = smem + (2 * C::BUF_BYTES + 2 * C::LS_BYTES + 2 * C::PATCH_BYTES) + cw * C::STG_WAVE + lane * 16;
+          char* st = smem + C::STG_OFF + cw * C::STG_WAVE + lane * 16;
 #pragma unroll
           for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-              typedef __attribute__((ext_vector_type(4))) float f32x4;
               const float16v& v = acc[2 * m2 + i][j];
               *(f32x4*)(st + (i * 4 + q) * 1024) = (f32x4){v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
             }
@@ -1731,18 +1644,8 @@ __device__ __forceinline__ void conv3x3_ws_body() {
     WS_STAMP(2)
   }
   if (handoff_on()) lds_barrier();        // the last handed-over pair is in LDS
-#ifdef UNETPP_WS_DBG
-  if (a->stamps && cw == 0 && lane == 0)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a->stamps[((size_t)blockIdx.x * 2) * 16 + i] = st_sum[i];
-  if (a->stamps && cw == 0 && lane == 0) {
-    a->stamps[((size_t)blockIdx.x * 2) * 16 + 4] = rt_begin;
-    a->stamps[((size_t)blockIdx.x * 2) * 16 + 6] = rt_entry;
-    a->stamps[((size_t)blockIdx.x * 2) * 16 + 5] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
+  WS_ROLE_END(0, cw == 0, 4, 5, WS_PUT(0, 4, rt_role) WS_PUT(0, 6, rt_entry))
 }
-#undef WS_STAMP
 
 template <int P, bool POOL, bool HEAD, bool UPF, bool C0F = false, int NW = 1, int MWP = 4, bool X8 = false, bool CAT2 = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(ConvArgs) {

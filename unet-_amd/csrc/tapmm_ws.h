@@ -31,7 +31,7 @@ struct TapmmArgs {
   float* y;              // [N][Nv/32][h*w][32] fp32 raw accumulators
   int N, hw, K, Nv;      // low-res pixels per image, input channels, virtual channels (9 * Cout)
 #ifdef UNETPP_WS_DBG
-  int dbg;               // measurement builds: 1 no DMA, 2 no MFMA, 4 no Y stores
+  int dbg;               // measurement builds: TapmmDbgBit (ws_dbg_dev.h); part of the argument layout, so declared here
 #endif
 };
 
@@ -83,8 +83,11 @@ __global__ __launch_bounds__(512, 2) void tapmm_ws_kernel(TapmmArgs a) {
     int in_, iq0, ivt;
     decode(it_tile, in_, iq0, ivt);
     auto issue = [&](int ring) {
-#ifdef UNETPP_WS_DBG
-      if (a.dbg & 1) { if (++it_s == nst) { it_s = 0; it_tile += G; if (it_tile < total_tiles) decode(it_tile, in_, iq0, ivt); } return; }
+#ifdef UNETPP_WS_DBG      // (not a WS_OFF test: its dead body changes the order of the lambda's captures, and with it two kernels' registers)
+      if (a.dbg & TAPMM_NO_DMA) {      // the cursor's step alone
+        if (++it_s == nst) { it_s = 0; it_tile += G; if (it_tile < total_tiles) decode(it_tile, in_, iq0, ivt); }
+        return;
+      }
 #endif
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
           (void*)(a.low + (size_t)in_ * (a.K / 16) * a.hw * 32), 0, (int)((a.K / 16) * blk_bytes), 0x00020000);
@@ -144,9 +147,7 @@ __global__ __launch_bounds__(512, 2) void tapmm_ws_kernel(TapmmArgs a) {
   };
   float16v acc[C::MT][C::NTL];
   auto run_mfma = [&](const Frag& f) {
-#ifdef UNETPP_WS_DBG
-    if (a.dbg & 2) return;
-#endif
+    if (WS_OFF(a.dbg, TAPMM_NO_MFMA)) return;
 #pragma unroll
     for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
@@ -247,9 +248,7 @@ __global__ __launch_bounds__(512, 2) void tapmm_ws_kernel(TapmmArgs a) {
       __builtin_amdgcn_sched_barrier(0);
       ++g;
     }
-#ifdef UNETPP_WS_DBG
-    if (a.dbg & 4) { if (acc[0][0][0] == 12345.f) a.y[0] = 1.f; continue; }
-#endif
+    if (WS_OFF(a.dbg, TAPMM_NO_STORE)) { if (acc[0][0][0] == 12345.f) a.y[0] = 1.f; continue; }
     // ---- store the raw accumulators: Y[n][v/32][q][32], lane = pixel, registers 4q'..4q'+3 = channels 8q' + 4h + (0..3)
     const int h = lane >> 5;
 #pragma unroll
@@ -262,7 +261,6 @@ __global__ __launch_bounds__(512, 2) void tapmm_ws_kernel(TapmmArgs a) {
         if (q < a.hw) {
 #pragma unroll
           for (int qq = 0; qq < 4; ++qq) {
-            typedef __attribute__((ext_vector_type(4))) float f32x4;
             *(f32x4*)(dst + 8 * qq) = (f32x4){acc[mt][nt][4 * qq], acc[mt][nt][4 * qq + 1], acc[mt][nt][4 * qq + 2], acc[mt][nt][4 * qq + 3]};
           }
         }
@@ -344,7 +342,6 @@ typedef UpsumCfgT<16> UpsumCfg;
 template <int TB, int TH_ = 16>
 __global__ __launch_bounds__(256, TB == 1 ? 4 : 1) void upsum_kernel(UpsumArgs a) {
   using C = UpsumCfgT<TH_>;
-  typedef __attribute__((ext_vector_type(4))) float f32x4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int H = a.H, W = a.W, h = H >> 1, w = W >> 1;
   const int tid = threadIdx.x, lane = tid & 63;

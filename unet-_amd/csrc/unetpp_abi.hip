@@ -227,7 +227,7 @@ struct LaunchCtx {      // per engine: one process may drive engines on several 
 template <int P, int KC, int NW, int MW, int WAVES, bool POOL, bool HEAD, bool UPF = false>
 hipError_t launch_conv_k(const LaunchCtx& cx, const ConvArgs& a, hipStream_t s) {
   using C = ConvCfg<P, KC, NW, MW, WAVES, UPF>;
-  const int lds = C::LDS_BYTES + a.Cout * 8 + (HEAD ? ((a.head_C * 33 * 4 + 15) / 16) * 16 : 0);
+  const int lds = C::LDS_BYTES + lds_tail(a.Cout, HEAD ? a.head_C : 0).bytes;
   // persistent workgroups: as many as are resident at once, each walks tiles blockIdx, +grid, ...
   const int total = a.N * a.tiles_x * a.tiles_y * a.nct;
   const int per_cu = std::max(1, std::min(2, (160 * 1024) / lds));
@@ -245,7 +245,7 @@ template <int P, bool POOL, bool HEAD, bool UPF, bool C0F = false, int NW = 1, i
 hipError_t launch_ws_k(const LaunchCtx& cx, ConvArgs a, hipStream_t s, bool uprows = false) {
   using C = WsCfg<P, UPF, C0F, NW, MW, X8>;
   a.tiles_x = (a.W + C::TW - 1) / C::TW; a.tiles_y = (a.H + C::TH - 1) / C::TH; a.nct = a.Cout / C::BN;
-  const int lds = C::LDS_BYTES + a.Cout * 8 + (HEAD ? ((a.head_C * 33 * 4 + 15) / 16) * 16 : 0) + (uprows ? UR_EDGE_BYTES : 0);
+  const int lds = C::LDS_BYTES + C::tail(a.Cout, HEAD ? a.head_C : 0, uprows).bytes;
   // Split-K plan (small batches): a layer with fewer tiles than a quarter of the CUs shares each tile's K-chunks among
   // `ksplit` workgroups -- the largest divisor of the chunk count that still leaves every workgroup four chunks and fits
   // the chip (measured at batch 1, 512x512: levels 3-4 gain 10-35 us per layer; two-way splits and two-chunk shares gain nothing:

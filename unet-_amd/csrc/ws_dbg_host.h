@@ -59,8 +59,10 @@ inline void ws_dbg_after_launch(const WsDbgPass& d, const ConvArgs& a, const std
   int nwg = 0;
   for (int b = 0; b < 1024; ++b) { if (!hs[b * 32 + 1] && !hs[b * 32 + 16]) continue; ++nwg; for (int i = 0; i < 32; ++i) sum[i] += (double)hs[b * 32 + i]; }
   fprintf(stderr, "[stamps %s] %d workgroups, mean cycles per workgroup:\n  consumer: barrier %.0f  chunks %.0f  epilogue %.0f  init %.0f\n"
-                  "  producer: skip issue %.0f wait %.0f barrier %.0f | up issue %.0f interp %.0f (reads %.0f arithmetic %.0f split+stores %.0f) wait %.0f barrier %.0f | setup %.0f\n", layer.c_str(), nwg,
-          sum[0] / nwg, sum[1] / nwg, sum[2] / nwg, sum[3] / nwg, sum[16] / nwg, sum[17] / nwg, sum[18] / nwg, sum[19] / nwg, sum[20] / nwg, sum[24] / nwg, sum[25] / nwg, sum[26] / nwg, sum[21] / nwg, sum[22] / nwg, sum[23] / nwg);
+                  "  producer: skip issue %.0f wait %.0f barrier %.0f | up issue %.0f interp %.0f (reads %.0f arithmetic %.0f split+stores %.0f)"
+                  " wait %.0f barrier %.0f | setup %.0f\n", layer.c_str(), nwg,
+          sum[0] / nwg, sum[1] / nwg, sum[2] / nwg, sum[3] / nwg, sum[16] / nwg, sum[17] / nwg, sum[18] / nwg, sum[19] / nwg, sum[20] / nwg,
+          sum[24] / nwg, sum[25] / nwg, sum[26] / nwg, sum[21] / nwg, sum[22] / nwg, sum[23] / nwg);
   // wall-clock (100 MHz) begin / end of consumer wave 0 of every workgroup, relative to the earliest begin
   std::vector<double> bg, en;
   unsigned long long t0 = ~0ull;
@@ -72,7 +74,7 @@ inline void ws_dbg_after_launch(const WsDbgPass& d, const ConvArgs& a, const std
   }
   std::sort(bg.begin(), bg.end()); std::sort(en.begin(), en.end()); std::sort(cb.begin(), cb.end()); std::sort(pe.begin(), pe.end());
   if (!bg.empty()) fprintf(stderr, "  consumer loop begins p50 %.2f max %.2f | producer wave 0 ends p50 %.2f max %.2f\n", cb[cb.size() / 2], cb.back(), pe[pe.size() / 2], pe.back());
-  if (a.dbg & 131072)
+  if (a.dbg & WS_EVENT_LOG)
     for (int b : {0, 1, 100, 200}) {      // event logs of consumer wave 0 and producer wave 0 (phase:us after the earliest kernel entry)
       for (int role = 0; role < 2; ++role) {
         fprintf(stderr, "  wg %3d %s:", b, role ? "producer" : "consumer");

@@ -1,0 +1,362 @@
+"""The NumPy form of the loss gradients (unet_amd/loss_grad.py) against the reference's own autograd
+(tests/golden/loss_grad_scenes.npz, scripts/make_golden_loss_grad.py), against calculus, and the eighth binding table and its
+header.  No GPU.
+
+The bar: per scene and combination loss_grad_np lies no further from the reference's float64 gradient than the reference's
+own float32 gradient does (e32 = max |g32 - g64| / max |g64| over all positions), with no margin; asserted here at the stored
+positions and on the plane sums.
+
+FINDING (tests/golden/README_loss_grad.txt has both numbers of every pair).  Over all positions the bar holds
+for 23 of the 40 pairs and is missed by the 17 of loss_grad.KNOWN_MISSES: a gradient element is one pixel's float32 chain and
+lands AT the reference's own float32 noise, not inside it as the summed losses do.  The bar is not loosened.  test_bar asserts
+it for the 23 pairs; for the 17 it asserts the record instead: the pair is listed in the module, the fixture and the README
+with both numbers, and at the stored positions it is no further off than its recorded all-positions figure.  A pair that
+changes sides in either direction fails here and in the generator."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, load_golden
+from unet_amd import _lib
+from unet_amd import loss as ls
+from unet_amd import loss_grad as lg
+
+HEADER = os.path.join(ROOT, "include", "unetpp_loss_grad.h")
+README = os.path.join(ROOT, "tests", "golden", "README_loss_grad.txt")
+U = 2.0 ** -24                                                   # float32 unit roundoff
+
+
+@pytest.fixture(scope="module")
+def golden():
+    g = load_golden("loss_grad_scenes")
+    return {k: g[k] for k in g.files}
+
+
+@pytest.fixture(scope="module")
+def facts(golden):
+    return lg.fixture_facts(golden)
+
+
+# ---- the fixture --------------------------------------------------------------------------------------------------------------------
+def test_fixture_covers_the_scenes_and_combinations(golden, facts):
+    special = {s[0] for s in ls.LOSS_SCENES if s[6] in ls.SPECIAL or s[7] in ls.SPECIAL}
+    assert set(lg.GRAD_SCENES) == {s[0] for s in ls.LOSS_SCENES} - special and {"absent3", "background3", "absent7_single"} <= set(lg.GRAD_SCENES)
+    assert lg.GRAD_COMBOS == (("combined", "default_w"), ("combined", "3class"), ("advanced", "default"), ("advanced", "3class_w"))
+    assert len(facts) == len(lg.GRAD_SCENES) * 4 == 40
+    for name in lg.GRAD_SCENES:
+        C = next(s[2] for s in ls.LOSS_SCENES if s[0] == name)
+        for criterion, params in lg.GRAD_COMBOS:
+            assert golden[f"{name}_{criterion}_{params}_g64"].shape == (len(golden[f"{name}_pos"]), C)
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "loss_grad_scenes.npz")) < 512 * 1024
+
+
+@pytest.mark.parametrize("criterion,params", lg.GRAD_COMBOS)
+@pytest.mark.parametrize("name", lg.GRAD_SCENES)
+def test_bar(facts, golden, name, criterion, params):
+    """form <= e32 with no margin, at the stored positions, for every pair that meets it over all positions; the plane sums
+    within their own bound (loss_grad.fixture_facts derives it) for every pair; the recorded misses are exactly KNOWN_MISSES."""
+    at, sums, e32, form = facts[(name, criterion, params)]
+    print(f"{name} {criterion} {params}: at the positions {at:.3e}, plane sums / their bound {sums:.3f}, e32 {e32:.3e}, form over all positions {form:.3e}")
+    assert at <= form * (1 + 1e-9)                               # the stored positions are some of all positions
+    assert sums <= 1
+    missed = (name, criterion, params) in lg.KNOWN_MISSES
+    assert missed == (form > e32) == (f"{name}_{criterion}_{params}" in set(golden["misses"].tolist()))
+    if not missed:
+        assert at <= e32
+
+
+def test_the_recorded_misses():
+    """17 pairs, each in the README with both numbers; both criteria are among them (cross-entropy + Dice alone misses too, so
+    the finding is not a property of Focal or Tversky)."""
+    assert len(lg.KNOWN_MISSES) == 17 and lg.KNOWN_MISSES <= {(n, c, p) for n in lg.GRAD_SCENES for c, p in lg.GRAD_COMBOS}
+    assert {c for _, c, _ in lg.KNOWN_MISSES} == {"combined", "advanced"}
+    g = load_golden("loss_grad_scenes")
+    with open(README) as f:
+        text = f.read()
+    for name, criterion, params in lg.KNOWN_MISSES:
+        _, e32, form = g[f"{name}_{criterion}_{params}_stats"]
+        assert f"  MISSES: {name} {criterion} {params}: form {form:.3e} > e32 {e32:.3e}" in text
+    assert text.count("  MISSES: ") == 17 and "holds for 23 of 40" in text
+
+
+def test_readme_records_the_fixture(golden):
+    with open(README) as f:
+        text = f.read()
+    for name in lg.GRAD_SCENES:
+        for criterion, params in lg.GRAD_COMBOS:
+            gmax, e32, form = golden[f"{name}_{criterion}_{params}_stats"]
+            row = re.search(rf"^  {name}\s+{criterion}\s+{params}\s+{gmax:.3e}\s+{e32:.3e}\s+{form:.3e}(   form > e32)?$", text, re.M)
+            assert row and bool(row.group(1)) == bool(form > e32), (name, criterion, params)
+
+
+# ---- calculus -----------------------------------------------------------------------------------------------------------------------
+def softmax64(x, target):
+    """(p [B,C,HW], nll [B,HW], t [B,HW], onehot) in float64, written out here: independent of the module under test."""
+    B, C = x.shape[:2]
+    z = x.reshape(B, C, -1).astype(np.float64)
+    t = target.reshape(B, -1).astype(np.int64)
+    z = z - z.max(1, keepdims=True)
+    logp = z - np.log(np.exp(z).sum(1, keepdims=True))
+    onehot = np.arange(C)[None, :, None] == t[:, None, :]
+    return np.exp(logp), -(logp * onehot).sum(1), t, onehot
+
+
+REFERENCE_DEFAULTS = {                                            # src/models/losses.py:211-218, 261-271, read off the reference
+    "combined": dict(weight_ce=1.0, weight_dice=1.0, class_weights=None, dice_ignore_bg=True, dice_skip_empty=True),
+    "advanced": dict(weight_focal=0.4, weight_tversky=0.4, weight_dice=0.2, focal_gamma=2.0, tversky_alpha=0.3, tversky_beta=0.7,
+                     class_weights=None, dice_ignore_bg=True),
+}
+
+
+def exact_loss(x, target, criterion, gamma, kw):
+    """The criterion in float64 with np.exp / np.log, written from the reference's expressions (losses.py) with none of
+    the module's helpers."""
+    k = {**REFERENCE_DEFAULTS[criterion], **kw}
+    B, C = x.shape[:2]
+    p, nll, t, onehot = softmax64(x, target)
+    T, P, I = onehot.sum(2).astype(np.float64), p.sum(2), (p * onehot).sum(2)
+    w = np.ones(C) if k["class_weights"] is None else np.asarray(k["class_weights"], np.float64)
+    dice = (2 * I + 1e-5) / (P + T + 1e-5)
+    valid = np.ones((B, C), bool)
+    if k["dice_ignore_bg"]:
+        valid[:, 0] = False
+    if k.get("dice_skip_empty", True):
+        valid &= T > 0
+    assert valid.any()
+    dice_loss = 1 - ((dice * w * valid).sum() / ((w * valid).sum() + 1e-6) if k["class_weights"] is not None else dice[valid].mean())
+    if criterion == "combined":
+        ce = (w[t] * nll).sum() / w[t].sum()
+        return k["weight_ce"] * ce + k["weight_dice"] * dice_loss
+    p_t = (p * onehot).sum(1)
+    focal = (w[t] * (1 - p_t) ** gamma * nll).mean()
+    tv = (I + 1e-5) / (I + k["tversky_alpha"] * (T - I) + k["tversky_beta"] * (P - I) + 1e-5)
+    tversky = 1 - (tv[:, 1:] if k["dice_ignore_bg"] else tv).mean()
+    return k["weight_focal"] * focal + k["weight_tversky"] * tversky + k["weight_dice"] * dice_loss
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("criterion,gamma", [("combined", 0)] + [("advanced", g) for g in range(5)])
+def test_calculus(criterion, gamma, weighted):
+    """loss_grad_np(exact=True) against central differences (h = 1e-5) of the float64 loss: within 1e-7 max|g|.  The
+    quotient's own error is about h^2 + 1e-16 / h = 1e-10; a missing term would be of the order of max|g|."""
+    B, C, H, W = 2, 3, 4, 5
+    r = np.random.default_rng(70 + gamma)
+    x = r.normal(0, 1.5, (B, C, H, W))
+    target = r.integers(0, C, (B, H, W)).astype(np.uint8)
+    target.reshape(B, -1)[:, :C] = np.arange(C)
+    kw = dict(class_weights=[0.5, 1.25, 2.0] if weighted else None, dice_ignore_bg=bool(gamma % 2 == 0))
+    if criterion == "advanced":
+        kw.update(focal_gamma=gamma, weight_focal=0.5, weight_tversky=0.3, weight_dice=0.2)
+    else:
+        kw.update(weight_ce=0.7, weight_dice=1.3, dice_skip_empty=False)
+    p, _, _, onehot = softmax64(x, target)
+    coef = lg.coefficients_from_columns(onehot.sum(2), p.sum(2), (p * onehot).sum(2), H * W, criterion, **kw)
+    assert coef.dtype == np.float64
+    g = lg.loss_grad_np(x, target, coef, gamma, exact=True)
+    assert g.dtype == np.float64 and g.shape == x.shape
+    h = 1e-5
+    num = np.zeros_like(x)
+    for i in range(x.size):
+        d = np.zeros(x.size)
+        d[i] = h
+        d = d.reshape(x.shape)
+        num.reshape(-1)[i] = (exact_loss(x + d, target, criterion, gamma, kw) - exact_loss(x - d, target, criterion, gamma, kw)) / (2 * h)
+    err = np.abs(g - num).max() / np.abs(g).max()
+    print(f"{criterion} gamma {gamma} weighted {weighted}: max|g| {np.abs(g).max():.3e}, |g - quotient| / max|g| {err:.3e}")
+    assert err <= 1e-7
+
+
+# ---- properties of the float32 form ----------------------------------------------------------------------------------------------------
+def scene_coef(name, criterion, params, gamma):
+    logits, target = ls.make_scene(name)
+    C, hw = logits.shape[1], logits.shape[2] * logits.shape[3]
+    table, _ = ls.loss_sums_np(logits, target, gamma)
+    kw = lg.combo_keywords(criterion, params, C)
+    if criterion == "advanced":
+        kw["focal_gamma"] = gamma
+    return logits, target, lg.coefficients_from_sums(table, hw, criterion, **kw)
+
+
+@pytest.mark.parametrize("name,criterion,params,gamma", [("plain3", "combined", "default_w", 0), ("plain7", "advanced", "3class_w", 2),
+                                                         ("wide4", "advanced", "default", 4), ("confident8", "combined", "3class", 0)])
+def test_gradient_sums_to_zero_over_the_classes(name, criterion, params, gamma):
+    """sum_c g_c = 0 in exact arithmetic (sum_c y_c = 0, sum_c r_c = 0).  In float32, to first order in u = 2^-24 and with
+    k the pixel's factor and umax = max_c |u_c|:  sum_c p_c = 1 + d, |d| <= (2C - 1) u (C quotients, C - 1 additions in s),
+    which k and dot multiply: (2C - 1) u (|k| + umax); dot carries (2C - 1) roundings of terms <= umax: (2C - 1) u umax; y_t,
+    k y_c, u_c - dot, the products r_c and the final additions round once each on values bounded by |k|, 2 |k|, 2 umax,
+    2 umax and 2 |k| + 2 umax: u (5 |k| + 6 umax).  Together |sum_c g_c| <= u ((2C + 4) |k| + (4C + 4) umax), asserted with
+    1 % for the second-order terms."""
+    logits, target, coef = scene_coef(name, criterion, params, gamma)
+    B, C, H, W = logits.shape
+    g = lg.loss_grad_np(logits, target, coef, gamma).astype(np.float64).reshape(B, C, -1)
+    p, nll, _, t, _ = ls.pixel_terms_np(logits, target, gamma)
+    p_t = np.take_along_axis(p.astype(np.float64), t[:, None, :], 1)[:, 0]
+    phi = (1 - p_t) ** gamma + gamma * p_t * (1 - p_t) ** max(gamma - 1, 0) * np.minimum(nll, 131072.0) if gamma else np.ones_like(p_t)
+    c64 = coef.astype(np.float64)
+    k = np.abs(np.take_along_axis(c64[:, :, 2], t, 1)) + np.abs(np.take_along_axis(c64[:, :, 3], t, 1)) * phi
+    umax = (np.abs(c64[:, :, 0]) + np.abs(c64[:, :, 1])).max(1)[:, None]
+    bound = 1.01 * U * ((2 * C + 4) * k + (4 * C + 4) * umax)
+    total = np.abs(g.sum(1))
+    print(f"{name}: largest |sum_c g_c| / bound {float((total / bound).max()):.3f}")
+    assert (total <= bound).all() and total.max() > 0
+
+
+@pytest.mark.parametrize("name", ["nonfinite3", "range7", "both3"])
+def test_special_pixels_give_exact_zeros(name):
+    logits, target = ls.make_scene(name)
+    B, C, H, W = logits.shape
+    kind = ls.pixel_terms_np(logits, target)[4].reshape(B, H, W)
+    table, outside = ls.loss_sums_np(logits, target, 2)
+    assert outside.any() and (kind != 0).sum() == outside.sum()
+    coef = lg.coefficients_from_sums(table, H * W, "advanced", class_weights=ls.scene_class_weights(C))
+    for scale in (None, -3.0, np.inf):
+        g = lg.loss_grad_np(logits, target, coef, 2, scale)
+        bits = g.view(np.uint32)
+        assert (bits.transpose(0, 2, 3, 1)[kind != 0] == 0).all()                 # +0, not -0 and not NaN
+        if scale != np.inf:
+            assert np.isfinite(g).all() and (g.transpose(0, 2, 3, 1)[kind == 0] != 0).any()
+    # the other pixels do not see the special ones: the same gradient as with those pixels' logits and targets replaced
+    clean_l = np.where((kind != 0)[:, None], np.float32(1.5), logits)
+    clean_t = np.where(kind != 0, np.uint8(200), target)
+    assert np.array_equal(lg.loss_grad_np(clean_l, clean_t, coef, 2).view(np.uint32), lg.loss_grad_np(logits, target, coef, 2).view(np.uint32))
+
+
+def test_gamma_zero_is_cross_entropy():
+    """gamma = 0: phi = 1, so Focal's factor acts exactly as cross-entropy's; and the scale multiplies last."""
+    logits, target, coef = scene_coef("plain3", "advanced", "default_w", 0)
+    assert (coef[:, :, 2] == 0).all() and (coef[:, :, 3] > 0).all()
+    swapped = coef.copy()
+    swapped[:, :, 2], swapped[:, :, 3] = coef[:, :, 3], 0
+    g = lg.loss_grad_np(logits, target, coef, 0)
+    assert np.array_equal(g.view(np.uint32), lg.loss_grad_np(logits, target, swapped, 0).view(np.uint32))
+    assert not np.array_equal(g, lg.loss_grad_np(logits, target, coef, 2))
+    s = np.float32(0.2)
+    assert np.array_equal(lg.loss_grad_np(logits, target, coef, 0, s).view(np.uint32), (g * s).view(np.uint32))
+
+
+def test_extreme_logits_stay_finite():
+    """A target class 3e38 below the maximum: d = -inf, p = 0, nll clamped to 131072, 0 * nll = 0."""
+    x = np.zeros((1, 2, 1, 2), np.float32)
+    x[0, 0, 0, 0], x[0, 1, 0, 0] = -3e38, 3e38
+    t = np.uint8([[[0, 1]]])
+    for gamma in range(5):
+        table, outside = ls.loss_sums_np(x, t, gamma)
+        assert not outside.any()
+        coef = lg.coefficients_from_sums(table, 2, "advanced", focal_gamma=gamma)
+        g = lg.loss_grad_np(x, t, coef, gamma)
+        assert np.isfinite(g).all() and g[0, 0, 0, 0] < 0 < g[0, 1, 0, 0]
+
+
+def test_coefficients():
+    """Shapes, zeros and signs; the criterion that does not use a factor leaves it 0; keywords are the reference's."""
+    logits, target = ls.make_scene("absent3")
+    table, _ = ls.loss_sums_np(logits, target, 2)
+    hw = logits.shape[2] * logits.shape[3]
+    comb = lg.coefficients_from_sums(table, hw, "combined")
+    adv = lg.coefficients_from_sums(table, hw, "advanced")
+    assert comb.dtype == adv.dtype == np.float32 and comb.shape == adv.shape == (3, 3, 4)
+    assert (comb[:, :, 3] == 0).all() and (adv[:, :, 2] == 0).all() and (comb[:, :, 2] > 0).all() and (adv[:, :, 3] > 0).all()
+    T = table[:, :, 0]
+    assert (T[0, 2] == 0) and comb[0, 2, 0] == 0 and comb[0, 2, 1] == 0          # skip_empty: the absent class has no Dice term
+    assert adv[0, 2, 1] > 0                                                        # Tversky still sees it
+    assert (comb[:, 0, :2] == 0).all() and (comb[:, :, 0] <= 0).all() and (comb[:, :, 1] >= 0).all()
+    with pytest.raises(TypeError, match="unexpected keyword"):
+        lg.coefficients_from_sums(table, hw, "combined", tversky_alpha=0.5)
+    with pytest.raises(ValueError, match="criterion"):
+        lg.coefficients_from_sums(table, hw, "hinge")
+    with pytest.raises(ValueError, match="coef"):
+        lg.loss_grad_np(logits, target, comb[:2], 0)
+    with pytest.raises(ValueError, match="float32"):
+        lg.loss_grad_np(logits, target, comb.astype(np.float64), 0)
+    with pytest.raises(ValueError, match="gamma"):
+        lg.loss_grad_np(logits, target, comb, 5)
+
+
+# ---- the binding table and the header ---------------------------------------------------------------------------------------------------
+def declared(path):
+    with open(path) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return re.findall(r"\b(unetpp_\w+)\s*\(", text)
+
+
+OLDER = {"unetpp.h": "ABI", "unetpp_roi.h": "ABI_ROI", "unetpp_loss.h": "ABI_LOSS", "unetpp_contours.h": "ABI_CONTOURS",
+         "unetpp_simple_loops.h": "ABI_SIMPLE_LOOPS", "unetpp_raw.h": "ABI_RAW", "unetpp_two_stage.h": "ABI_TWO_STAGE"}
+
+
+def test_header_and_table_agree():
+    names = declared(HEADER)
+    assert set(names) == set(_lib.ABI_LOSS_GRAD) and len(names) == len(_lib.ABI_LOSS_GRAD) == 3
+    assert "loss_grad.h" in _lib.HEADERS and any(h.endswith("unetpp_loss_grad.h") for h in _lib.HEADERS)
+    with open(os.path.join(_lib.CSRC, "unetpp_postproc.hip")) as f:
+        src = f.read()
+    assert all(re.search(r"\b%s\s*\(" % n, src) for n in _lib.ABI_LOSS_GRAD)
+    assert '#include "loss_grad.h"' in src and "unetpp_loss_grad.h" in src
+    with open(os.path.join(_lib.CSRC, "loss_grad.h")) as f:
+        kernel = f.read()
+    assert '#include "loss.h"' in kernel and "ls_exp32(float" not in kernel and "ls_log32(float" not in kernel      # included, not copied
+    lib = _lib.load()
+    assert [n for n in _lib.ABI_LOSS_GRAD if getattr(lib, n).argtypes != _lib.ABI_LOSS_GRAD[n][1]] == []
+    with open(HEADER) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    for n in ("unetpp_loss_grad_f32", "unetpp_loss_narrow_target_i64"):
+        args = [a.strip() for a in re.search(r"\bint %s\s*\(([^)]*)\)" % n, text).group(1).split(",")]
+        assert len(args) == len(_lib.ABI_LOSS_GRAD[n][1]) and args[0] == "unetpp_engine* e" and args[-1] == "void* stream", n
+
+
+def test_the_seven_older_headers_and_tables_are_unchanged():
+    for header, attr in OLDER.items():
+        table = getattr(_lib, attr)
+        names = declared(os.path.join(ROOT, "include", header))
+        assert set(names) == set(table) and len(names) == len(table), header
+        assert not set(table) & set(_lib.ABI_LOSS_GRAD), header
+    assert [len(getattr(_lib, a)) for a in OLDER.values()] == [76, 8, 2, 5, 5, 2, 3]
+
+
+def test_header_is_c99(tmp_path):
+    cc_ = shutil.which("cc") or shutil.which("gcc")
+    assert cc_, "no C compiler"
+    src = tmp_path / "use.c"
+    src.write_text('#include "unetpp_loss_grad.h"\nint main(void) { float c[UNETPP_LOSS_GRAD_COEFFICIENTS] = {0}; (void)c; return UNETPP_LOSS_GRAD_COEFFICIENTS - 4; }\n')
+    subprocess.run([cc_, "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)],
+                   check=True, capture_output=True, text=True)
+
+
+def test_layout_and_null_engine():
+    import ctypes
+    lib = _lib.load()
+    span, span_sums = ctypes.c_int(-1), ctypes.c_int(-2)
+    assert lib.unetpp_loss_grad_layout(ctypes.byref(span)) == 0 and lib.unetpp_loss_layout(ctypes.byref(span_sums)) == 0
+    assert span.value == span_sums.value > 0 and lib.unetpp_loss_grad_layout(None) == -2
+    assert lib.unetpp_loss_grad_f32(None, None, None, 1, 3, 8, 8, 2, None, None, None, None) == -1
+    assert lib.unetpp_loss_narrow_target_i64(None, None, 1, None, None) == -1
+
+
+def test_guard_rows_cover_the_table():
+    """Both launching symbols of ABI_LOSS_GRAD have guard-band cases in tests/test_gpu_guarded_loss_grad.py; the third is a
+    layout query."""
+    import test_gpu_guarded_loss_grad as tgg
+    assert set(tgg.COVERED) | set(tgg.EXCLUDED_LOSS_GRAD) == set(_lib.ABI_LOSS_GRAD) and not set(tgg.COVERED) & set(tgg.EXCLUDED_LOSS_GRAD)
+    assert all(tgg.EXCLUDED_LOSS_GRAD.values())
+    assert {(lo, go) for lo, go, _ in tgg.GRAD_OFFSETS} == {(a, b) for a in range(4) for b in range(4)}
+    assert {to for _, _, to in tgg.GRAD_OFFSETS} == set(range(4))
+    assert {d for _, d in tgg.NARROW_OFFSETS} == set(range(16)) and {s for s, _ in tgg.NARROW_OFFSETS} == {0, 8}
+
+
+def test_modules_take_the_references_keywords():
+    """Constructed without a device: the reference's keywords and defaults, then check=True; wrong values are refused."""
+    import inspect
+    import torch
+    for cls, criterion in ((lg.CombinedLoss, "combined"), (lg.AdvancedCombinedLoss, "advanced")):
+        assert issubclass(cls, torch.nn.Module)
+        params = inspect.signature(cls.__init__).parameters
+        assert list(params)[:2] == ["self", "model"] and list(params)[-1] == "check" and params["check"].default is True
+        assert {k: v.default for k, v in list(params.items())[2:-1]} == lg.DEFAULTS[criterion]
+    m = lg.AdvancedCombinedLoss(None, class_weights=torch.tensor([0.5, 1.0, 2.0]), focal_gamma=3.0)
+    assert m.gamma == 3 and m.kw["class_weights"].tolist() == [0.5, 1.0, 2.0] and list(m.parameters()) == [] and m.check
+    assert lg.CombinedLoss(None, check=False).gamma == 0
+    with pytest.raises(ValueError, match="focal_gamma"):
+        lg.AdvancedCombinedLoss(None, focal_gamma=2.5)

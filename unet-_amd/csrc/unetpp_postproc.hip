@@ -15,6 +15,7 @@
 
 #include "../../include/unetpp_contours.h"
 #include "../../include/unetpp_loss.h"
+#include "../../include/unetpp_loss_grad.h"
 #include "../../include/unetpp_raw.h"
 #include "../../include/unetpp_roi.h"
 #include "../../include/unetpp_simple_loops.h"
@@ -30,6 +31,7 @@
 #include "frame_kernels.h"
 #include "geometry.h"
 #include "loss.h"
+#include "loss_grad.h"
 #include "morphology.h"
 #include "multiclass.h"
 #include "nlmeans.h"
@@ -1574,6 +1576,56 @@ int unetpp_loss_sums_f32(unetpp_engine* e, const float* dev_logits, const uint8_
     LOSS_SUMS_CASE(2); LOSS_SUMS_CASE(3); LOSS_SUMS_CASE(4); LOSS_SUMS_CASE(5); LOSS_SUMS_CASE(6); LOSS_SUMS_CASE(7); LOSS_SUMS_CASE(8);
   }
 #undef LOSS_SUMS_CASE
+  return launched(e);
+}
+
+// ---- loss gradients: one pass from logits, target and the coefficient table (loss_grad.h; include/unetpp_loss_grad.h) ------------
+int unetpp_loss_grad_layout(int* span_pixels) {
+  if (!span_pixels) return UNETPP_E_UNSUPPORTED;
+  *span_pixels = LS_SPAN;
+  return UNETPP_OK;
+}
+
+int unetpp_loss_grad_f32(unetpp_engine* e, const float* dev_logits, const uint8_t* dev_target, int batch, int classes, int h, int w, int gamma,
+                         const float* dev_coef, const float* dev_scale, float* dev_grad, void* stream) {
+  REQUIRE_ROBUST(e, dev_logits && dev_target && dev_coef && dev_grad);
+  if (batch < 1 || batch > MAX_DIM || h < 1 || w < 1 || (size_t)h * (size_t)w > LS_MAX_PIXELS)
+    return fail(e, UNETPP_E_UNSUPPORTED, "loss grad: shape %dx%dx%d outside 1 <= batch <= 65535, h, w >= 1, h * w <= 2^22", batch, h, w);
+  if (classes < 2 || classes > LS_MAX_CLASSES || gamma < 0 || gamma > LS_MAX_GAMMA)
+    return fail(e, UNETPP_E_UNSUPPORTED, "loss grad: classes %d outside 2..8 or gamma %d outside 0..4", classes, gamma);
+  if ((uintptr_t)dev_logits % 4 || (uintptr_t)dev_grad % 4 || (uintptr_t)dev_coef % 4 || (uintptr_t)dev_scale % 4)
+    return fail(e, UNETPP_E_UNSUPPORTED, "dev_logits, dev_grad, dev_coef and dev_scale must be 4-byte aligned");
+  const size_t hw = (size_t)h * w, n_logits = (size_t)batch * classes * hw * sizeof(float), n_target = (size_t)batch * hw;
+  const size_t n_coef = (size_t)batch * classes * LG_COEF * sizeof(float);
+  if (((const void*)dev_grad != (const void*)dev_logits && overlaps(dev_grad, n_logits, dev_logits, n_logits)) ||
+      overlaps(dev_grad, n_logits, dev_target, n_target) || overlaps(dev_grad, n_logits, dev_coef, n_coef) ||
+      (dev_scale && overlaps(dev_grad, n_logits, dev_scale, sizeof(float))))
+    return fail(e, UNETPP_E_UNSUPPORTED, "loss grad: dev_grad overlaps an input (only dev_grad == dev_logits is allowed)");
+  ENTER_DEVICE(e);
+  const dim3 grid((unsigned)((hw + LS_GROUP - 1 + LS_SPAN - 1) / LS_SPAN), (unsigned)batch);
+#define LOSS_GRAD_CASE(C)                                                                                                   \
+  case C:                                                                                                                   \
+    hipLaunchKernelGGL(loss_grad_kernel<C>, grid, dim3(LS_THREADS), 0, (hipStream_t)stream, dev_logits, dev_target,          \
+                       (unsigned)hw, gamma, dev_coef, dev_scale, dev_grad);                                                  \
+    break
+  switch (classes) {
+    LOSS_GRAD_CASE(2); LOSS_GRAD_CASE(3); LOSS_GRAD_CASE(4); LOSS_GRAD_CASE(5); LOSS_GRAD_CASE(6); LOSS_GRAD_CASE(7); LOSS_GRAD_CASE(8);
+  }
+#undef LOSS_GRAD_CASE
+  return launched(e);
+}
+
+int unetpp_loss_narrow_target_i64(unetpp_engine* e, const int64_t* dev_target_i64, int64_t n, uint8_t* dev_target_u8, void* stream) {
+  REQUIRE_ROBUST(e, dev_target_i64 && dev_target_u8);
+  if (n < 1 || n > (int64_t)MAX_DIM * LS_MAX_PIXELS)
+    return fail(e, UNETPP_E_UNSUPPORTED, "narrow target: n %lld outside 1 .. 65535 * 2^22", (long long)n);
+  if ((uintptr_t)dev_target_i64 % 8) return fail(e, UNETPP_E_UNSUPPORTED, "dev_target_i64 must be 8-byte aligned");
+  if (overlaps(dev_target_u8, (size_t)n, dev_target_i64, (size_t)n * sizeof(int64_t)))
+    return fail(e, UNETPP_E_UNSUPPORTED, "narrow target: the output overlaps the input");
+  ENTER_DEVICE(e);
+  const size_t groups = ((size_t)n + ((uintptr_t)dev_target_u8 & 15u) + LN_GROUP - 1) / LN_GROUP;
+  hipLaunchKernelGGL(loss_narrow_kernel, dim3((unsigned)((groups + LN_THREADS - 1) / LN_THREADS)), dim3(LN_THREADS), 0, (hipStream_t)stream,
+                     (const long long*)dev_target_i64, (long long)n, dev_target_u8);
   return launched(e);
 }
 

@@ -17,11 +17,11 @@ SOURCES = ["unetpp_abi.hip", "unetpp_postproc.hip"]      # the engine; the post-
 HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "ws_dbg_dev.h", "ws_dbg_host.h", "convt2x2_mfma.h", "aux_kernels.h",
            "frame_kernels.h", "components.h", "distance.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "nlmeans.h", "evaluation.h",
            "probmap.h", "multiclass.h", "geometry.h", "tiling.h", "roi_loop.h", "loss.h", "loss_grad.h", "contours.h", "simple_loops.h", "raw_frames.h",
-           "two_stage.h", os.path.join("..", "..", "include", "unetpp.h"),
+           "two_stage.h", "train_batch.h", os.path.join("..", "..", "include", "unetpp.h"),
            os.path.join("..", "..", "include", "unetpp_roi.h"), os.path.join("..", "..", "include", "unetpp_loss.h"),
            os.path.join("..", "..", "include", "unetpp_contours.h"), os.path.join("..", "..", "include", "unetpp_simple_loops.h"),
            os.path.join("..", "..", "include", "unetpp_raw.h"), os.path.join("..", "..", "include", "unetpp_two_stage.h"),
-           os.path.join("..", "..", "include", "unetpp_loss_grad.h")]
+           os.path.join("..", "..", "include", "unetpp_loss_grad.h"), os.path.join("..", "..", "include", "unetpp_train_batch.h")]
 
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
 PREC_EXACT, PREC_FAST, PREC_EXACT8 = 0, 1, 2
@@ -247,6 +247,13 @@ ABI_LOSS_GRAD = {
     "unetpp_loss_narrow_target_i64": (ci, [vp, vp, ctypes.c_int64, vp, vp]),
 }
 
+# every symbol include/unetpp_train_batch.h declares; load() applies all nine tables
+ABI_TRAIN_BATCH = {
+    "unetpp_train_batch_layout": (ci, [ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]),
+    "unetpp_train_crop_rects": (ci, [vp, vp, ctypes.c_int64, vp, ci, vp, ci, vp, vp]),
+    "unetpp_train_batch_u8": (ci, [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, ci, ci, vp, vp, vp]),
+}
+
 # -fno-slp-vectorize: the SLP vectoriser turns pairs of float operations into v_pk_mul_f32 / v_pk_fma_f32, and a packed
 # fp32 instruction issued beside another wave's MFMA stream on the same SIMD takes 26-58 cycles instead of 5-7
 # (scripts/microbench/valu_beside_mfma.hip) -- the loader waves of the wave-specialised kernels run exactly there.
@@ -342,7 +349,8 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
         build()
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in list(ABI.items()) + list(ABI_ROI.items()) + list(ABI_LOSS.items()) + list(ABI_CONTOURS.items()) + list(
-            ABI_SIMPLE_LOOPS.items()) + list(ABI_RAW.items()) + list(ABI_TWO_STAGE.items()) + list(ABI_LOSS_GRAD.items()):
+            ABI_SIMPLE_LOOPS.items()) + list(ABI_RAW.items()) + list(ABI_TWO_STAGE.items()) + list(ABI_LOSS_GRAD.items()) + list(
+            ABI_TRAIN_BATCH.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     ver = lib.unetpp_version().decode()

@@ -19,6 +19,7 @@
 #include "../../include/unetpp_raw.h"
 #include "../../include/unetpp_roi.h"
 #include "../../include/unetpp_simple_loops.h"
+#include "../../include/unetpp_train_batch.h"
 #include "../../include/unetpp_two_stage.h"
 #include "abi_common.h"
 #include "components.h"
@@ -40,6 +41,7 @@
 #include "roi_loop.h"
 #include "simple_loops.h"
 #include "tiling.h"
+#include "train_batch.h"
 #include "two_stage.h"
 
 using namespace unetpp;
@@ -1626,6 +1628,63 @@ int unetpp_loss_narrow_target_i64(unetpp_engine* e, const int64_t* dev_target_i6
   const size_t groups = ((size_t)n + ((uintptr_t)dev_target_u8 & 15u) + LN_GROUP - 1) / LN_GROUP;
   hipLaunchKernelGGL(loss_narrow_kernel, dim3((unsigned)((groups + LN_THREADS - 1) / LN_THREADS)), dim3(LN_THREADS), 0, (hipStream_t)stream,
                      (const long long*)dev_target_i64, (long long)n, dev_target_u8);
+  return launched(e);
+}
+
+// ---- training batches: the data-dependent crop and the assembly (train_batch.h; include/unetpp_train_batch.h) -----------------------
+int unetpp_train_batch_layout(int* tile_w, int* tile_h, int* pass_bytes, int* plan_columns) {
+  if (!tile_w || !tile_h || !pass_bytes || !plan_columns) return UNETPP_E_UNSUPPORTED;
+  *tile_w = TB_TW; *tile_h = TB_TH; *pass_bytes = TB_THREADS * TB_SEG; *plan_columns = TB_PLAN;
+  return UNETPP_OK;
+}
+
+int unetpp_train_crop_rects(unetpp_engine* e, const uint8_t* dev_masks, int64_t masks_bytes, const int64_t* dev_items, int n_items,
+                            const int32_t* dev_requests, int batch, int32_t* dev_rects, void* stream) {
+  REQUIRE_ROBUST(e, dev_masks && dev_items && dev_requests && dev_rects);
+  if (batch < 1 || batch > MAX_DIM || n_items < 1 || masks_bytes < 1)
+    return fail(e, UNETPP_E_UNSUPPORTED, "crop rects: batch %d outside 1..65535, n_items %d or masks_bytes %lld below 1", batch, n_items,
+                (long long)masks_bytes);
+  if ((uintptr_t)dev_items % 8 || (uintptr_t)dev_requests % 4 || (uintptr_t)dev_rects % 4)
+    return fail(e, UNETPP_E_UNSUPPORTED, "dev_items must be 8-byte, dev_requests and dev_rects 4-byte aligned");
+  const size_t n_rects = (size_t)batch * TB_RECT * sizeof(int32_t);
+  if (overlaps(dev_rects, n_rects, dev_masks, (size_t)masks_bytes) || overlaps(dev_rects, n_rects, dev_items, (size_t)n_items * TB_ITEM * 8) ||
+      overlaps(dev_rects, n_rects, dev_requests, (size_t)batch * TB_REQUEST * sizeof(int32_t)))
+    return fail(e, UNETPP_E_UNSUPPORTED, "crop rects: dev_rects overlaps an input");
+  ENTER_DEVICE(e);
+  hipLaunchKernelGGL(tb_crop_rects_kernel, dim3((unsigned)batch), dim3(TB_THREADS), 0, (hipStream_t)stream, dev_masks, (long long)masks_bytes,
+                     (const long long*)dev_items, n_items, dev_requests, dev_rects);
+  return launched(e);
+}
+
+int unetpp_train_batch_u8(unetpp_engine* e, const uint8_t* dev_images, int64_t images_bytes, const uint8_t* dev_masks, int64_t masks_bytes,
+                          const int64_t* dev_items, int n_items, const int32_t* dev_plan, int batch, const int32_t* dev_rects, int n_rects,
+                          const uint8_t* dev_luts, int n_luts, const uint8_t* dev_class_lut, int out_h, int out_w, int image_format,
+                          void* dev_image_out, uint8_t* dev_target_out, void* stream) {
+  REQUIRE_ROBUST(e, dev_images && dev_masks && dev_items && dev_plan && dev_image_out && dev_target_out);
+  if (batch < 1 || batch > MAX_DIM || out_h < 1 || out_h > MAX_DIM || out_w < 1 || out_w > MAX_DIM)
+    return fail(e, UNETPP_E_UNSUPPORTED, "train batch: shape %dx%dx%d outside 1..65535", batch, out_h, out_w);
+  if (n_items < 1 || images_bytes < 3 || masks_bytes < 1 || n_rects < 0 || n_luts < 0 || (n_rects > 0) != (dev_rects != nullptr) ||
+      (n_luts > 0) != (dev_luts != nullptr))
+    return fail(e, UNETPP_E_UNSUPPORTED, "train batch: n_items %d, arenas of %lld and %lld bytes, %d rects, %d look-ups: a count below its "
+                "minimum, or a table without its count", n_items, (long long)images_bytes, (long long)masks_bytes, n_rects, n_luts);
+  if (image_format != UNETPP_TRAIN_CHW_F32 && image_format != UNETPP_TRAIN_HWC_RGB && image_format != UNETPP_TRAIN_HWC_BGR)
+    return fail(e, UNETPP_E_UNSUPPORTED, "train batch: image_format %d is none of UNETPP_TRAIN_*", image_format);
+  if ((uintptr_t)dev_items % 8 || (uintptr_t)dev_plan % 4 || (uintptr_t)dev_rects % 4 ||
+      (image_format == UNETPP_TRAIN_CHW_F32 && (uintptr_t)dev_image_out % 4))
+    return fail(e, UNETPP_E_UNSUPPORTED, "dev_items must be 8-byte, dev_plan, dev_rects and a float32 dev_image_out 4-byte aligned");
+  const size_t px = (size_t)batch * out_h * out_w, n_image = px * (image_format == UNETPP_TRAIN_CHW_F32 ? 12 : 3);
+  const struct { const void* p; size_t n; } in[] = {{dev_images, (size_t)images_bytes}, {dev_masks, (size_t)masks_bytes},
+      {dev_items, (size_t)n_items * TB_ITEM * 8}, {dev_plan, (size_t)batch * TB_PLAN * sizeof(int32_t)},
+      {dev_rects, (size_t)n_rects * TB_RECT * sizeof(int32_t)}, {dev_luts, (size_t)n_luts * 256}, {dev_class_lut, dev_class_lut ? 256u : 0u}};
+  for (const auto& a : in)
+    if (a.p && a.n && (overlaps(dev_image_out, n_image, a.p, a.n) || overlaps(dev_target_out, px, a.p, a.n)))
+      return fail(e, UNETPP_E_UNSUPPORTED, "train batch: an output overlaps an input");
+  if (overlaps(dev_image_out, n_image, dev_target_out, px)) return fail(e, UNETPP_E_UNSUPPORTED, "train batch: the two outputs overlap");
+  ENTER_DEVICE(e);
+  const dim3 grid((unsigned)((out_w + TB_TW - 1) / TB_TW), (unsigned)((out_h + TB_TH - 1) / TB_TH), (unsigned)batch);
+  hipLaunchKernelGGL(tb_batch_kernel, grid, dim3(TB_THREADS), 0, (hipStream_t)stream, dev_images, (long long)images_bytes, dev_masks,
+                     (long long)masks_bytes, (const long long*)dev_items, n_items, dev_plan, dev_rects, n_rects, dev_luts, n_luts,
+                     dev_class_lut, out_h, out_w, image_format, dev_image_out, dev_target_out);
   return launched(e);
 }
 

@@ -25,7 +25,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
-from burr_bench import timed  # noqa: E402
+from bench_timing import timed  # noqa: E402
 
 
 def main():

@@ -23,7 +23,6 @@ import argparse
 import json
 import os
 import re
-import statistics
 import subprocess
 import sys
 
@@ -31,22 +30,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_timing import timed  # noqa: E402
 BYTES_PER_PIXEL = 3 + 1 + 1 + 3            # stats reads BGR and writes grey; apply reads grey and writes BGR
-
-
-def timed(torch, fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    loops = []
-    for _ in range(3):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        loops.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return round(statistics.median(loops), 1)
 
 
 def copy_bandwidth():

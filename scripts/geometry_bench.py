@@ -28,21 +28,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-
-def timed(torch, fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    loops = []
-    for _ in range(3):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        loops.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return round(statistics.median(loops), 1)
+from bench_timing import timed  # noqa: E402
 
 
 def parent_path(torch, ge, model, pred, taps):

@@ -25,30 +25,14 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_timing import timed_spread  # noqa: E402
 HBM_BYTES_PER_US = 6.3e6                                        # 6.3 TB/s
-
-
-def timed(torch, fn, iters, warmup):
-    """(median, fastest, slowest) of three loops, microseconds per call."""
-    for _ in range(warmup):
-        fn()
-    loops = []
-    for _ in range(3):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        loops.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return [round(statistics.median(loops), 1), round(min(loops), 1), round(max(loops), 1)]
 
 
 def torch_criterion(torch, logits, target, advanced):
@@ -102,7 +86,7 @@ def main():
         target = torch.from_numpy(np.concatenate([four_t] * (B // 4))).cuda()
         target64 = target.long()
         row = {"input": name, "batch": B, "h": H, "w": W, "num_classes": C, "grad_bytes": B * H * W * (8 * C + 1)}
-        t = lambda fn: timed(torch, fn, args.iters, args.warmup)
+        t = lambda fn: timed_spread(torch, fn, args.iters, args.warmup)
         pred = logits.clone().requires_grad_()
         modules = {"combined": lg.CombinedLoss(model), "advanced": lg.AdvancedCombinedLoss(model)}
 

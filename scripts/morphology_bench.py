@@ -23,7 +23,6 @@ import argparse
 import ctypes
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -31,23 +30,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_timing import timed  # noqa: E402
 
 K = 8192
-
-
-def timed(torch, fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    loops = []
-    for _ in range(3):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        loops.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return round(statistics.median(loops), 1)
 
 
 def host_ring(torch, d, mo):

@@ -30,45 +30,15 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_timing import timed, wall  # noqa: E402
 
 COLORS = {1: (255, 0, 0), 2: (0, 255, 0), 3: (0, 0, 255), 4: (255, 255, 0), 5: (255, 0, 255), 6: (0, 165, 255)}
-
-
-def timed(torch, fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    loops = []
-    for _ in range(3):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        loops.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return round(statistics.median(loops), 1)
-
-
-def wall(torch, fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    loops = []
-    for _ in range(3):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(iters):
-            fn()
-        torch.cuda.synchronize()
-        loops.append((time.perf_counter() - t0) * 1e6 / iters)
-    return round(statistics.median(loops), 1)
 
 
 def main():

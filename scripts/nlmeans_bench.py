@@ -28,7 +28,6 @@ import argparse
 import hashlib
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -36,23 +35,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_timing import timed  # noqa: E402
 OPS_PER_PIXEL = 441 * (140 + 14 * 13 + 84 + 32 * 4) // 32            # see the docstring
 VALU_LANE_OPS_PER_S = 157.3e12 / 2
-
-
-def timed(torch, fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    loops = []
-    for _ in range(3):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        loops.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return round(statistics.median(loops), 1)
 
 
 def main():

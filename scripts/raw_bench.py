@@ -34,7 +34,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
-from roi_bench import timed, wall  # noqa: E402
+from bench_timing import timed, wall  # noqa: E402
 
 S = 512
 FORMAT = "BayerRG8"

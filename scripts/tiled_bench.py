@@ -18,30 +18,15 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_timing import timed  # noqa: E402
 
 H, W, PATCH, STRIDE, TARGET, CLASSES, GATE_THR = 1080, 1920, 384, 192, 256, 2, 0.5
-
-
-def timed(torch, fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    loops = []
-    for _ in range(3):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        loops.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return round(statistics.median(loops), 1)
 
 
 def main():

@@ -40,24 +40,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from bench_timing import timed_spread  # noqa: E402
 HBM_BYTES_PER_US = 6.3e6                                        # 6.3 TB/s
 MAP_3CLASS = {0: 0, 1: 1, 2: 2, 3: 0, 4: 0, 5: 0, 6: 0}
-
-
-def timed(torch, fn, iters, warmup):
-    """(median, fastest, slowest) of three loops, microseconds per call."""
-    for _ in range(warmup):
-        fn()
-    loops = []
-    for _ in range(3):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        loops.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return [round(statistics.median(loops), 1), round(min(loops), 1), round(max(loops), 1)]
 
 
 def sources(h, w, n, distinct=4):
@@ -106,7 +91,7 @@ def main():
     print(lines[0], flush=True)
     model = NestedUNet(3, max_batch=1, max_hw=(16, 16)).to("cuda:0")              # no weights: the batches need none
     B = 16
-    t = lambda fn: timed(torch, fn, args.iters, args.warmup)
+    t = lambda fn: timed_spread(torch, fn, args.iters, args.warmup)
     for name in (args.inputs.split(",") if args.inputs else ["cable", "patch"]):
         r = np.random.RandomState(7)
         if name == "cable":

@@ -1,13 +1,9 @@
 """The Python surface that callers and the other files of the package rely on, pinned without a device: the public methods
-of NestedUNet / SimpleUNet and their signatures, the private names used outside nested_unet.py and postproc.py, the
-binding table of _lib against include/unetpp.h, and the text each method's tensor check raises for a host tensor."""
+of NestedUNet / SimpleUNet and their signatures, the private names used outside nested_unet.py and postproc.py, and
+the text each method's tensor check raises for a host tensor."""
 import inspect
-import os
-import re
 
 import pytest
-
-from conftest import ROOT
 
 # str(inspect.signature(NestedUNet.<name>)) of every public method, as the methods stood before postproc.py was split off
 SIGNATURES = {
@@ -118,15 +114,6 @@ def test_private_names_other_files_use_exist():
     from unet_amd.nested_unet import NestedUNet, SimpleUNet
     for model in (NestedUNet(3), SimpleUNet(3)):
         assert [n for n in PRIVATE if not hasattr(model, n)] == []
-
-
-def test_binding_table_covers_the_header_and_types_every_symbol():
-    from unet_amd import _lib
-    header = open(os.path.join(ROOT, "include", "unetpp.h")).read()
-    declared = set(re.findall(r"\b(unetpp_[a-z0-9_]+)\s*\(", header))          # test_host_logic.py's parser
-    assert set(_lib.ABI_SYMBOLS) == declared and len(_lib.ABI_SYMBOLS) == len(declared)
-    lib = _lib.load()
-    assert [n for n in _lib.ABI_SYMBOLS if getattr(lib, n).argtypes is None] == []
 
 
 @pytest.mark.parametrize("cls", ["NestedUNet", "SimpleUNet"])

@@ -1,10 +1,9 @@
 """Host tests of unet_amd/contours.py (no GPU): the window-sum identity the device's contour areas rest on, checked against
 the border-following restatement on every 4 x 5 mask and on random 12 x 12 masks; the restatement against the reference's
 own functions (tests/golden/contours_scenes.npz, scripts/make_golden_contours.py); the exact circle; the overlay table; the
-argument checks; the fourth header against the fourth binding table."""
+argument checks; what is particular to include/unetpp_contours.h."""
 import itertools
 import os
-import re
 import shutil
 import subprocess
 
@@ -16,7 +15,6 @@ from unet_amd import components as cc
 from unet_amd import contours as ct
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "unetpp_contours.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "contours_scenes.npz")
 
 
@@ -264,23 +262,7 @@ def test_paste_and_overlay_against_the_reference(golden):
     assert (got == golden["overlay/out"]).all()
 
 
-# ---- the fourth header and table -------------------------------------------------------------------------------------------------
-def declared(path):
-    with open(path) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return re.findall(r"\b(unetpp_\w+)\s*\(", text)
-
-
-def test_header_and_table_agree():
-    names = declared(HEADER)
-    assert set(names) == set(_lib.ABI_CONTOURS) and len(names) == len(_lib.ABI_CONTOURS)
-    assert not set(_lib.ABI_CONTOURS) & (set(_lib.ABI) | set(_lib.ABI_ROI) | set(_lib.ABI_LOSS))
-    assert "contours.h" in _lib.HEADERS and any(h.endswith("unetpp_contours.h") for h in _lib.HEADERS)
-    with open(os.path.join(_lib.CSRC, "unetpp_postproc.hip")) as f:
-        src = f.read()
-    assert all(re.search(r"\b%s\s*\(" % n, src) for n in _lib.ABI_CONTOURS)
-
-
+# ---- the header's entries (names, types, build inputs and guard coverage: tests/test_bindings_host.py) ------------------------------
 def test_header_is_c99(tmp_path):
     cc_ = shutil.which("cc") or shutil.which("gcc")
     assert cc_, "no C compiler"
@@ -300,11 +282,3 @@ def test_entries_refuse_a_null_engine_and_bad_shapes():
     assert lib.unetpp_contours_workspace_bytes(1, 8, 8, 16) > 0
     assert lib.unetpp_contours_workspace_bytes(1, 4096, 8, 16) == 0 and lib.unetpp_contours_workspace_bytes(1, 8, 4096, 16) == 0
     assert lib.unetpp_contours_workspace_bytes(1, 8, 8, 1) == 0 and lib.unetpp_contours_workspace_bytes(0, 8, 8, 16) == 0
-
-
-def test_guard_rows_cover_the_table():
-    """Every launching symbol of ABI_CONTOURS is declared by a row of tests/test_gpu_guarded_contours.py."""
-    import test_gpu_guarded_contours as tgc
-    covered = set().union(*(r.symbols for r in tgc.ROWS_CONTOURS))
-    launching = set(_lib.ABI_CONTOURS) - set(tgc.EXCLUDED_CONTOURS)
-    assert launching <= covered and set(tgc.EXCLUDED_CONTOURS) <= set(_lib.ABI_CONTOURS) and all(tgc.EXCLUDED_CONTOURS.values())

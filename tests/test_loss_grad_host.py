@@ -1,6 +1,6 @@
 """The NumPy form of the loss gradients (unet_amd/loss_grad.py) against the reference's own autograd
-(tests/golden/loss_grad_scenes.npz, scripts/make_golden_loss_grad.py), against calculus, and the eighth binding table and its
-header.  No GPU.
+(tests/golden/loss_grad_scenes.npz, scripts/make_golden_loss_grad.py), against calculus, and what is particular to
+include/unetpp_loss_grad.h.  No GPU.
 
 The bar: per scene and combination loss_grad_np lies no further from the reference's float64 gradient than the reference's
 own float32 gradient does (e32 = max |g32 - g64| / max |g64| over all positions), with no margin; asserted here at the stored
@@ -25,7 +25,6 @@ from unet_amd import _lib
 from unet_amd import loss as ls
 from unet_amd import loss_grad as lg
 
-HEADER = os.path.join(ROOT, "include", "unetpp_loss_grad.h")
 README = os.path.join(ROOT, "tests", "golden", "README_loss_grad.txt")
 U = 2.0 ** -24                                                   # float32 unit roundoff
 
@@ -276,44 +275,11 @@ def test_coefficients():
         lg.loss_grad_np(logits, target, comb, 5)
 
 
-# ---- the binding table and the header ---------------------------------------------------------------------------------------------------
-def declared(path):
-    with open(path) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return re.findall(r"\b(unetpp_\w+)\s*\(", text)
-
-
-OLDER = {"unetpp.h": "ABI", "unetpp_roi.h": "ABI_ROI", "unetpp_loss.h": "ABI_LOSS", "unetpp_contours.h": "ABI_CONTOURS",
-         "unetpp_simple_loops.h": "ABI_SIMPLE_LOOPS", "unetpp_raw.h": "ABI_RAW", "unetpp_two_stage.h": "ABI_TWO_STAGE"}
-
-
-def test_header_and_table_agree():
-    names = declared(HEADER)
-    assert set(names) == set(_lib.ABI_LOSS_GRAD) and len(names) == len(_lib.ABI_LOSS_GRAD) == 3
-    assert "loss_grad.h" in _lib.HEADERS and any(h.endswith("unetpp_loss_grad.h") for h in _lib.HEADERS)
-    with open(os.path.join(_lib.CSRC, "unetpp_postproc.hip")) as f:
-        src = f.read()
-    assert all(re.search(r"\b%s\s*\(" % n, src) for n in _lib.ABI_LOSS_GRAD)
-    assert '#include "loss_grad.h"' in src and "unetpp_loss_grad.h" in src
+# ---- the header's entries (names, types, build inputs and guard coverage: tests/test_bindings_host.py) ------------------------------------
+def test_the_kernel_includes_the_loss_primitives_and_does_not_copy_them():
     with open(os.path.join(_lib.CSRC, "loss_grad.h")) as f:
         kernel = f.read()
-    assert '#include "loss.h"' in kernel and "ls_exp32(float" not in kernel and "ls_log32(float" not in kernel      # included, not copied
-    lib = _lib.load()
-    assert [n for n in _lib.ABI_LOSS_GRAD if getattr(lib, n).argtypes != _lib.ABI_LOSS_GRAD[n][1]] == []
-    with open(HEADER) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    for n in ("unetpp_loss_grad_f32", "unetpp_loss_narrow_target_i64"):
-        args = [a.strip() for a in re.search(r"\bint %s\s*\(([^)]*)\)" % n, text).group(1).split(",")]
-        assert len(args) == len(_lib.ABI_LOSS_GRAD[n][1]) and args[0] == "unetpp_engine* e" and args[-1] == "void* stream", n
-
-
-def test_the_seven_older_headers_and_tables_are_unchanged():
-    for header, attr in OLDER.items():
-        table = getattr(_lib, attr)
-        names = declared(os.path.join(ROOT, "include", header))
-        assert set(names) == set(table) and len(names) == len(table), header
-        assert not set(table) & set(_lib.ABI_LOSS_GRAD), header
-    assert [len(getattr(_lib, a)) for a in OLDER.values()] == [76, 8, 2, 5, 5, 2, 3]
+    assert '#include "loss.h"' in kernel and "ls_exp32(float" not in kernel and "ls_log32(float" not in kernel
 
 
 def test_header_is_c99(tmp_path):
@@ -335,12 +301,8 @@ def test_layout_and_null_engine():
     assert lib.unetpp_loss_narrow_target_i64(None, None, 1, None, None) == -1
 
 
-def test_guard_rows_cover_the_table():
-    """Both launching symbols of ABI_LOSS_GRAD have guard-band cases in tests/test_gpu_guarded_loss_grad.py; the third is a
-    layout query."""
+def test_guard_cases_visit_every_offset():
     import test_gpu_guarded_loss_grad as tgg
-    assert set(tgg.COVERED) | set(tgg.EXCLUDED_LOSS_GRAD) == set(_lib.ABI_LOSS_GRAD) and not set(tgg.COVERED) & set(tgg.EXCLUDED_LOSS_GRAD)
-    assert all(tgg.EXCLUDED_LOSS_GRAD.values())
     assert {(lo, go) for lo, go, _ in tgg.GRAD_OFFSETS} == {(a, b) for a in range(4) for b in range(4)}
     assert {to for _, _, to in tgg.GRAD_OFFSETS} == set(range(4))
     assert {d for _, d in tgg.NARROW_OFFSETS} == set(range(16)) and {s for s, _ in tgg.NARROW_OFFSETS} == {0, 8}

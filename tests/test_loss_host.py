@@ -1,5 +1,5 @@
 """The NumPy form of the validation-loss sums and the float64 algebra on their table (unet_amd/loss.py) against the
-reference's own losses (tests/golden/loss_scenes.npz, scripts/make_golden_loss.py), the third binding table and its header,
+reference's own losses (tests/golden/loss_scenes.npz, scripts/make_golden_loss.py), what is particular to include/unetpp_loss.h,
 and the argument checks that need no device.  No GPU.
 
 The bar: every loss from loss_sums_np + the algebra lies no further from the reference's float64 run than the reference's
@@ -18,7 +18,6 @@ from conftest import ROOT, load_golden
 from unet_amd import _lib
 from unet_amd import loss as ls
 
-HEADER = os.path.join(ROOT, "include", "unetpp_loss.h")
 README = os.path.join(ROOT, "tests", "golden", "README_loss.txt")
 
 
@@ -31,11 +30,6 @@ def golden():
 @pytest.fixture(scope="module")
 def facts(golden):
     return ls.fixture_facts(golden)
-
-
-def declared(path):
-    with open(path) as f:
-        return re.findall(r"\b(unetpp_[a-z0-9_]+)\s*\(", f.read())              # test_host_logic.py's parser
 
 
 # ---- exp32 and log32 ------------------------------------------------------------------------------------------------------------
@@ -173,17 +167,10 @@ def test_algebra_by_hand():
         ls.dice_from_sums(table[0])
 
 
-# ---- the binding table and the header -----------------------------------------------------------------------------------------------
-def test_abi_loss_is_the_header_and_the_other_tables_are_what_they_were():
-    names = declared(HEADER)
-    assert set(names) == set(_lib.ABI_LOSS) and len(names) == len(_lib.ABI_LOSS)
-    assert set(_lib.ABI) == set(declared(os.path.join(ROOT, "include", "unetpp.h"))) == set(_lib.ABI_SYMBOLS)
-    assert set(_lib.ABI_ROI) == set(declared(os.path.join(ROOT, "include", "unetpp_roi.h")))
-    assert not set(_lib.ABI_LOSS) & (set(_lib.ABI) | set(_lib.ABI_ROI))
-    lib = _lib.load()
-    assert [n for n in _lib.ABI_LOSS if getattr(lib, n).argtypes is None] == []               # typed by load(), and exported
-    assert "loss.h" in _lib.HEADERS and any(h.endswith("unetpp_loss.h") for h in _lib.HEADERS)
+# ---- the header's entries (names, types, build inputs and guard coverage: tests/test_bindings_host.py) ----------------------------------
+def test_layout_query():
     import ctypes
+    lib = _lib.load()
     span = ctypes.c_int(-1)
     assert lib.unetpp_loss_layout(ctypes.byref(span)) == 0 and span.value > 0 and span.value % 4 == 0
     assert lib.unetpp_loss_layout(None) == -2
@@ -202,14 +189,8 @@ def test_null_engine_is_refused():
     assert _lib.load().unetpp_loss_sums_f32(None, None, None, 1, 3, 8, 8, 2, None, None, None) == -1
 
 
-def test_guard_rows_cover_the_table():
-    """Every launching symbol of ABI_LOSS is declared by a row of tests/test_gpu_guarded_loss.py; the other is a layout query."""
+def test_guard_rows_run_at_3_and_7_classes():
     import test_gpu_guarded_loss as tgl
-    covered = set().union(*(r.symbols for r in tgl.ROWS_LOSS))
-    launching = set(_lib.ABI_LOSS) - set(tgl.EXCLUDED_LOSS)
-    assert covered <= set(_lib.ABI) | set(_lib.ABI_ROI) | set(_lib.ABI_LOSS)
-    assert launching <= covered and all(tgl.EXCLUDED_LOSS[n] for n in tgl.EXCLUDED_LOSS) and set(tgl.EXCLUDED_LOSS) <= set(_lib.ABI_LOSS)
-    assert len({r.name for r in tgl.ROWS_LOSS}) == len(tgl.ROWS_LOSS)
     assert {c for r in tgl.ROWS_LOSS for c in r.classes} >= {3, 7}
 
 

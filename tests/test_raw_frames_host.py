@@ -1,6 +1,6 @@
 """Raw camera frames without a GPU: the NumPy forms of unet_amd/raw_frames.py against an independent second form, OpenCV's
-documented pattern names and the reference's own _to_bgr (tests/golden/raw_scenes.npz, README_raw.txt), and the sixth header and
-binding table (include/unetpp_raw.h, _lib.ABI_RAW) against each other, the sources and the guard rows."""
+documented pattern names and the reference's own _to_bgr (tests/golden/raw_scenes.npz, README_raw.txt), and what is particular to
+include/unetpp_raw.h: its enum, its C99 form, the null-engine codes and the guard rows the family requires."""
 import os
 import re
 import shutil
@@ -147,39 +147,12 @@ def test_raw_resize_takes_the_phase_from_the_frame():
             rf.raw_resize_np(raw, "RG", bad, (8, 8))
 
 
-# ---- 4. the sixth header and table -------------------------------------------------------------------------------------------------------
-def declared(path):
-    with open(path) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return re.findall(r"\b(unetpp_\w+)\s*\(", text)
-
-
-def test_header_and_table_agree():
-    names = declared(HEADER)
-    assert set(names) == set(_lib.ABI_RAW) and len(names) == len(_lib.ABI_RAW)
-    assert "raw_frames.h" in _lib.HEADERS and any(h.endswith("unetpp_raw.h") for h in _lib.HEADERS)
-    with open(os.path.join(_lib.CSRC, "unetpp_postproc.hip")) as f:
-        src = f.read()
-    assert all(re.search(r"\b%s\s*\(" % n, src) for n in _lib.ABI_RAW)
-    assert '#include "raw_frames.h"' in src
-    lib = _lib.load()
-    assert [n for n in _lib.ABI_RAW if getattr(lib, n).argtypes != _lib.ABI_RAW[n][1]] == []
+# ---- 4. the header's entries (names, types, build inputs and guard coverage: tests/test_bindings_host.py) -------------------------------
+def test_raw_patterns_are_the_headers_enum():
     with open(HEADER) as f:
         text = f.read()
     for name, value in _lib.RAW_PATTERNS.items():
         assert re.search(r"\bUNETPP_RAW_%s = %d\b" % (name, value), text), name
-
-
-def test_the_five_older_headers_and_tables_are_unchanged():
-    """Each older header still declares exactly its own table's symbols, and no table shares a name with the sixth."""
-    tables = {"unetpp.h": _lib.ABI, "unetpp_roi.h": _lib.ABI_ROI, "unetpp_loss.h": _lib.ABI_LOSS, "unetpp_contours.h": _lib.ABI_CONTOURS,
-              "unetpp_simple_loops.h": _lib.ABI_SIMPLE_LOOPS}
-    for header, table in tables.items():
-        names = declared(os.path.join(ROOT, "include", header))
-        assert set(names) == set(table) and len(names) == len(table), header
-        assert not set(table) & set(_lib.ABI_RAW), header
-    assert _lib.ABI_SYMBOLS == list(_lib.ABI) and not set(_lib.ABI_SYMBOLS) & set(_lib.ABI_RAW)
-    assert (len(_lib.ABI), len(_lib.ABI_ROI), len(_lib.ABI_LOSS), len(_lib.ABI_CONTOURS), len(_lib.ABI_SIMPLE_LOOPS)) == (76, 8, 2, 5, 5)
 
 
 def test_header_is_c99(tmp_path):
@@ -197,12 +170,8 @@ def test_entries_refuse_a_null_engine():
     assert lib.unetpp_raw_resize_u8(None, None, 8, 64, 1, 8, 8, 0, 0, 0, 8, 8, None, 4, 4, None) == -1
 
 
-def test_guard_rows_cover_the_table():
-    """Every symbol of ABI_RAW is declared by a row of tests/test_gpu_guarded_raw.py (both of them launch)."""
+def test_guard_rows_the_family_requires():
     import test_gpu_guarded_raw as tgr
-    covered = set().union(*(r.symbols for r in tgr.ROWS_RAW))
-    assert set(_lib.ABI_RAW) <= covered
-    assert covered <= set(_lib.ABI) | set(_lib.ABI_RAW)
     names = [r.name for r in tgr.ROWS_RAW]
-    assert len(set(names)) == len(names) and any(n.startswith("process_raw_frames") for n in names)
+    assert any(n.startswith("process_raw_frames") for n in names)
     assert {"to_bgr[BayerBG8, both]", "to_gray[RG]", "to_bgr[RG]"} <= set(names)          # BGR, grey, both

@@ -1,8 +1,7 @@
 """The NumPy forms of the ROI and full-frame 3-class loops (unet_amd/roi_loop.py) against the reference's own results
-(tests/golden/roi_scenes.npz, scripts/make_golden_roi.py), the second binding table and its header, and the argument checks
+(tests/golden/roi_scenes.npz, scripts/make_golden_roi.py), what is particular to include/unetpp_roi.h, and the argument checks
 that need no device.  No GPU."""
 import os
-import re
 import shutil
 import subprocess
 
@@ -15,18 +14,12 @@ from unet_amd import components as cc
 from unet_amd import edges as ed
 from unet_amd import roi_loop as rl
 
-HEADER = os.path.join(ROOT, "include", "unetpp_roi.h")
 
 
 @pytest.fixture(scope="module")
 def golden():
     g = load_golden("roi_scenes")
     return {k: g[k] for k in g.files}
-
-
-def declared(path):
-    with open(path) as f:
-        return re.findall(r"\b(unetpp_[a-z0-9_]+)\s*\(", f.read())              # test_host_logic.py's parser
 
 
 # ---- the fixtures ---------------------------------------------------------------------------------------------------------------
@@ -139,15 +132,9 @@ def test_crop_and_paste_forms():
     assert not rl.paste_mask_np(m, (10, 10, 1, 0), (30, 50)).any()
 
 
-# ---- the binding table and the header ---------------------------------------------------------------------------------------------
-def test_abi_roi_is_the_header_and_abi_is_what_it_was():
-    names = declared(HEADER)
-    assert set(names) == set(_lib.ABI_ROI) and len(names) == len(_lib.ABI_ROI)
-    assert set(_lib.ABI) == set(declared(os.path.join(ROOT, "include", "unetpp.h"))) == set(_lib.ABI_SYMBOLS)
-    assert not set(_lib.ABI) & set(_lib.ABI_ROI)
+# ---- the header's entries (names, types, build inputs and guard coverage: tests/test_bindings_host.py) --------------------------------
+def test_workspace_sizes():
     lib = _lib.load()
-    assert [n for n in _lib.ABI_ROI if getattr(lib, n).argtypes is None] == []               # typed by load(), and exported
-    assert "roi_loop.h" in _lib.HEADERS and any(h.endswith("unetpp_roi.h") for h in _lib.HEADERS)
     assert lib.unetpp_roi_projection_workspace_bytes(2, 100) >= 800 and lib.unetpp_roi_projection_workspace_bytes(0, 100) == 0
     assert lib.unetpp_roi_stats_workspace_bytes(4) >= 4 * 3 * 12 and lib.unetpp_roi_stats_workspace_bytes(0) == 0
 
@@ -165,16 +152,6 @@ def test_null_engine_is_refused():
     lib = _lib.load()
     assert lib.unetpp_roi_from_edges_u8(None, None, 1, 8, 8, None, None, None) == -1
     assert lib.unetpp_roi_paste_masks_u8(None, None, None, 1, 8, 8, None, None, None, 8, 8, None) == -1
-
-
-def test_guard_rows_cover_the_table():
-    """Every launching symbol of ABI_ROI is declared by a row of tests/test_gpu_guarded_roi.py; the others are size queries."""
-    import test_gpu_guarded_roi as tgr
-    covered = set().union(*(r.symbols for r in tgr.ROWS_ROI))
-    launching = set(_lib.ABI_ROI) - set(tgr.EXCLUDED_ROI)
-    assert covered <= set(_lib.ABI) | set(_lib.ABI_ROI)
-    assert launching <= covered and all(tgr.EXCLUDED_ROI[n] for n in tgr.EXCLUDED_ROI) and set(tgr.EXCLUDED_ROI) <= set(_lib.ABI_ROI)
-    assert len({r.name for r in tgr.ROWS_ROI}) == len(tgr.ROWS_ROI)
 
 
 # ---- argument checks that need no device --------------------------------------------------------------------------------------------

@@ -1,8 +1,7 @@
 """Host tests of unet_amd/simple_loops.py: every NumPy form against the reference's own results (tests/golden/
-simple_loops_scenes.npz, written by scripts/make_golden_simple_loops.py) with ==, the argument checks, and the fifth binding
-table against include/unetpp_simple_loops.h.  No GPU."""
+simple_loops_scenes.npz, written by scripts/make_golden_simple_loops.py) with ==, the argument checks, and what is particular to
+include/unetpp_simple_loops.h.  No GPU."""
 import os
-import re
 import shutil
 import subprocess
 
@@ -14,8 +13,6 @@ from unet_amd import _lib
 from unet_amd import components as cc
 from unet_amd import multiclass as mc
 from unet_amd import simple_loops as sl
-
-HEADER = os.path.join(ROOT, "include", "unetpp_simple_loops.h")
 
 
 @pytest.fixture(scope="module")
@@ -215,34 +212,7 @@ def test_argument_checks():
             pytest.fail(f"call {i} was accepted")
 
 
-# ---- the fifth header and table --------------------------------------------------------------------------------------------------------
-def declared(path):
-    with open(path) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return re.findall(r"\b(unetpp_\w+)\s*\(", text)
-
-
-def test_header_and_table_agree():
-    names = declared(HEADER)
-    assert set(names) == set(_lib.ABI_SIMPLE_LOOPS) and len(names) == len(_lib.ABI_SIMPLE_LOOPS)
-    assert "simple_loops.h" in _lib.HEADERS and any(h.endswith("unetpp_simple_loops.h") for h in _lib.HEADERS)
-    with open(os.path.join(_lib.CSRC, "unetpp_postproc.hip")) as f:
-        src = f.read()
-    assert all(re.search(r"\b%s\s*\(" % n, src) for n in _lib.ABI_SIMPLE_LOOPS)
-    assert '#include "simple_loops.h"' in src
-    lib = _lib.load()
-    assert [n for n in _lib.ABI_SIMPLE_LOOPS if getattr(lib, n).argtypes != _lib.ABI_SIMPLE_LOOPS[n][1]] == []
-
-
-def test_the_four_older_headers_and_tables_are_unchanged():
-    """Each older header still declares exactly its own table's symbols, and no two tables share a name."""
-    tables = {"unetpp.h": _lib.ABI, "unetpp_roi.h": _lib.ABI_ROI, "unetpp_loss.h": _lib.ABI_LOSS, "unetpp_contours.h": _lib.ABI_CONTOURS}
-    for header, table in tables.items():
-        names = declared(os.path.join(ROOT, "include", header))
-        assert set(names) == set(table) and len(names) == len(table), header
-        assert not set(table) & set(_lib.ABI_SIMPLE_LOOPS), header
-
-
+# ---- the header's entries (names, types, build inputs and guard coverage: tests/test_bindings_host.py) -----------------------------------
 def test_header_is_c99(tmp_path):
     cc_ = shutil.which("cc") or shutil.which("gcc")
     assert cc_, "no C compiler"
@@ -260,14 +230,6 @@ def test_entries_refuse_a_null_engine():
     assert lib.unetpp_tape_position_filter_u8(None, None, -1, None, -1, 1, 8, 8, None, None, None) == -1
     assert lib.unetpp_column_band_u8(None, None, 1, 8, 8, 2, 6, None, None) == -1
     assert lib.unetpp_mask_join_u8(None, None, 255, None, 0, None, 0, 1, 8, 8, None, None) == -1
-
-
-def test_guard_rows_cover_the_table():
-    """Every symbol of ABI_SIMPLE_LOOPS is declared by a row of tests/test_gpu_guarded_simple_loops.py (all of them launch)."""
-    import test_gpu_guarded_simple_loops as tgs
-    covered = set().union(*(r.symbols for r in tgs.ROWS_SIMPLE_LOOPS))
-    assert set(_lib.ABI_SIMPLE_LOOPS) <= covered
-    assert covered <= set(_lib.ABI) | set(_lib.ABI_SIMPLE_LOOPS)
 
 
 def test_components_np_is_the_labelling_the_rule_reads():

@@ -1,7 +1,7 @@
 """Training batches without a device (unet_amd/train_batch.py): the NumPy forms against what the reference's own dataset classes
 returned (tests/golden/train_batch_scenes.npz, scripts/make_golden_train_batch.py) with ==, float32 compared as bits (SHA-256
 of the tensor's bytes); the draw replays against the recorded draws; the two cv2-free checks of the HSV restatement over all
-2^24 colours; tape_crop_rect_np against a brute-force form; bad arguments; the ninth header and binding table."""
+2^24 colours; tape_crop_rect_np against a brute-force form; bad arguments; what is particular to include/unetpp_train_batch.h."""
 import ctypes
 import hashlib
 import os
@@ -18,7 +18,6 @@ from unet_amd import _lib
 from unet_amd import multiclass as mc
 from unet_amd import train_batch as tb
 
-HEADER = os.path.join(ROOT, "include", "unetpp_train_batch.h")
 CABLE = {"eval_native": (False, None), "eval_32x32": (False, (32, 32)), "aug_17x23": (True, (17, 23)), "aug_48x40": (True, (48, 40)),
          "aug_native": (True, None)}
 PATCH = {"p32_native": (32, None, True), "p32_to17": (32, 17, True), "p33_to40x48": (33, (40, 48), True), "p32_plain": (32, (40, 48), False)}
@@ -328,47 +327,12 @@ def test_bad_arguments_raise(items):
         tb.class_lut({3: 256})
 
 
-# ---- the binding table and the header ---------------------------------------------------------------------------------------------------
-def declared(path):
-    with open(path) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return re.findall(r"\b(unetpp_\w+)\s*\(", text)
-
-
-OLDER = {"unetpp.h": "ABI", "unetpp_roi.h": "ABI_ROI", "unetpp_loss.h": "ABI_LOSS", "unetpp_contours.h": "ABI_CONTOURS",
-         "unetpp_simple_loops.h": "ABI_SIMPLE_LOOPS", "unetpp_raw.h": "ABI_RAW", "unetpp_two_stage.h": "ABI_TWO_STAGE",
-         "unetpp_loss_grad.h": "ABI_LOSS_GRAD"}
-
-
-def test_header_and_table_agree():
-    names = declared(HEADER)
-    assert set(names) == set(_lib.ABI_TRAIN_BATCH) and len(names) == len(_lib.ABI_TRAIN_BATCH) == 3
-    assert "train_batch.h" in _lib.HEADERS and any(h.endswith("unetpp_train_batch.h") for h in _lib.HEADERS)
-    with open(os.path.join(_lib.CSRC, "unetpp_postproc.hip")) as f:
-        src = f.read()
-    assert all(re.search(r"\b%s\s*\(" % n, src) for n in _lib.ABI_TRAIN_BATCH)
-    assert '#include "train_batch.h"' in src and "unetpp_train_batch.h" in src
+# ---- the header's entries (names, types, build inputs and guard coverage: tests/test_bindings_host.py) ------------------------------------
+def test_the_kernel_reuses_the_resize_helpers_and_has_no_atomics():
     with open(os.path.join(_lib.CSRC, "train_batch.h")) as f:
         kernel = f.read()
     assert "roi_linear_coef(int" not in kernel and "rf_store_row(const" not in kernel                            # reused, not copied
     assert not re.search(r"\batomic[A-Z]\w*\s*\(", kernel)                                                      # no atomics on outputs
-    lib = _lib.load()
-    assert [n for n in _lib.ABI_TRAIN_BATCH if getattr(lib, n).argtypes != _lib.ABI_TRAIN_BATCH[n][1]] == []
-    with open(HEADER) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    for n in ("unetpp_train_crop_rects", "unetpp_train_batch_u8"):
-        args = [a.strip() for a in re.search(r"\bint %s\s*\(([^)]*)\)" % n, text).group(1).split(",")]
-        assert len(args) == len(_lib.ABI_TRAIN_BATCH[n][1]) and args[0] == "unetpp_engine* e" and args[-1] == "void* stream", n
-    assert (tb.PLAN_COLS, tb.RECT_COLS, tb.REQUEST_COLS, tb.ITEM_COLS) == (16, 6, 5, 4)
-
-
-def test_the_eight_older_headers_and_tables_are_unchanged():
-    for header, attr in OLDER.items():
-        table = getattr(_lib, attr)
-        names = declared(os.path.join(ROOT, "include", header))
-        assert set(names) == set(table) and len(names) == len(table), header
-        assert not set(table) & set(_lib.ABI_TRAIN_BATCH), header
-    assert [len(getattr(_lib, a)) for a in OLDER.values()] == [76, 8, 2, 5, 5, 2, 3, 3]
 
 
 def test_header_is_c99(tmp_path):
@@ -384,17 +348,14 @@ def test_header_is_c99(tmp_path):
 def test_layout_and_null_engine():
     lib = _lib.load()
     assert tb.layout() == (32, 32, 4096, tb.PLAN_COLS)
+    assert (tb.PLAN_COLS, tb.RECT_COLS, tb.REQUEST_COLS, tb.ITEM_COLS) == (16, 6, 5, 4)
     v = ctypes.c_int(0)
     assert lib.unetpp_train_batch_layout(ctypes.byref(v), None, ctypes.byref(v), ctypes.byref(v)) == -2
     assert lib.unetpp_train_crop_rects(None, None, 1, None, 1, None, 1, None, None) == -1
     assert lib.unetpp_train_batch_u8(None, None, 3, None, 1, None, 1, None, 1, None, 0, None, 0, None, 8, 8, 0, None, None, None) == -1
 
 
-def test_guard_rows_cover_the_table():
-    """Both launching symbols of ABI_TRAIN_BATCH have guard-band cases in tests/test_gpu_guarded_train_batch.py; the third is a
-    layout query."""
+def test_guard_cases_visit_every_offset():
     import test_gpu_guarded_train_batch as tgt
-    assert set(tgt.COVERED) | set(tgt.EXCLUDED_TRAIN_BATCH) == set(_lib.ABI_TRAIN_BATCH) and not set(tgt.COVERED) & set(tgt.EXCLUDED_TRAIN_BATCH)
-    assert all(tgt.EXCLUDED_TRAIN_BATCH.values())
     assert {a for a, _, _ in tgt.ARENA_OFFSETS} == set(range(16)) and {m for _, m, _ in tgt.ARENA_OFFSETS} == set(range(16))
     assert {o for _, _, o in tgt.ARENA_OFFSETS} == set(range(16)) and set(tgt.FLOAT_PHASES) == {0, 4, 8, 12}

@@ -1,7 +1,7 @@
 """The two-stage loop's own steps without a GPU: the NumPy forms of unet_amd/two_stage.py against the reference's own
 visualize_two_stage and map_roi_to_original (tests/golden/two_stage_scenes.npz, README_two_stage.txt), against the project's older
-NumPy forms and np.rot90; the overlay table against the form it is built from on all 16 x 256 x 3 inputs; the seventh header and
-binding table (include/unetpp_two_stage.h, _lib.ABI_TWO_STAGE) against each other, the sources and the guard rows; FrameStream's
+NumPy forms and np.rot90; the overlay table against the form it is built from on all 16 x 256 x 3 inputs; what is particular to
+include/unetpp_two_stage.h (its enum, its C99 form, the null-engine codes, the guard rows the family requires); FrameStream's
 argument checks."""
 import os
 import re
@@ -167,48 +167,12 @@ def test_ratios():
     assert ts.roi_area((140, 0, 270, 512)) == 130 * 512
 
 
-# ---- 4. the seventh header and table -------------------------------------------------------------------------------------------------------
-def declared(path):
-    with open(path) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return re.findall(r"\b(unetpp_\w+)\s*\(", text)
-
-
-OLDER = {"unetpp.h": "ABI", "unetpp_roi.h": "ABI_ROI", "unetpp_loss.h": "ABI_LOSS", "unetpp_contours.h": "ABI_CONTOURS",
-         "unetpp_simple_loops.h": "ABI_SIMPLE_LOOPS", "unetpp_raw.h": "ABI_RAW"}
-
-
-def test_header_and_table_agree():
-    names = declared(HEADER)
-    assert set(names) == set(_lib.ABI_TWO_STAGE) and len(names) == len(_lib.ABI_TWO_STAGE) == 3
-    assert "two_stage.h" in _lib.HEADERS and any(h.endswith("unetpp_two_stage.h") for h in _lib.HEADERS)
-    with open(os.path.join(_lib.CSRC, "unetpp_postproc.hip")) as f:
-        src = f.read()
-    assert all(re.search(r"\b%s\s*\(" % n, src) for n in _lib.ABI_TWO_STAGE)
-    assert '#include "two_stage.h"' in src and "unetpp_two_stage.h" in src
-    lib = _lib.load()
-    assert [n for n in _lib.ABI_TWO_STAGE if getattr(lib, n).argtypes != _lib.ABI_TWO_STAGE[n][1]] == []
+# ---- 4. the header's entries (names, types, build inputs and guard coverage: tests/test_bindings_host.py) ---------------------------------
+def test_rotate_codes_are_the_headers_enum():
     with open(HEADER) as f:
         text = f.read()
     for name, value in _lib.ROTATE_CODES.items():
         assert re.search(r"\bUNETPP_ROTATE_%s = %d\b" % (name.upper(), value), text), name
-    # the prototypes' argument counts: the engine first, the stream last
-    for n, (restype, argtypes) in _lib.ABI_TWO_STAGE.items():
-        proto = re.search(r"\bint %s\s*\(([^)]*)\)" % n, re.sub(r"/\*.*?\*/", "", text, flags=re.S)).group(1)
-        args = [a.strip() for a in proto.split(",")]
-        assert len(args) == len(argtypes) and args[0] == "unetpp_engine* e" and args[-1] == "void* stream", n
-        assert restype is _lib.ci
-
-
-def test_the_six_older_headers_and_tables_are_unchanged():
-    """Each older header still declares exactly its own table's symbols, and no table shares a name with the seventh."""
-    for header, attr in OLDER.items():
-        table = getattr(_lib, attr)
-        names = declared(os.path.join(ROOT, "include", header))
-        assert set(names) == set(table) and len(names) == len(table), header
-        assert not set(table) & set(_lib.ABI_TWO_STAGE), header
-    assert _lib.ABI_SYMBOLS == list(_lib.ABI)
-    assert [len(getattr(_lib, a)) for a in OLDER.values()] == [76, 8, 2, 5, 5, 2]
 
 
 def test_header_is_c99(tmp_path):
@@ -227,15 +191,10 @@ def test_entries_refuse_a_null_engine():
     assert lib.unetpp_rotate_u8(None, None, 1, 8, 8, 3, 0, None, None) == -1
 
 
-def test_guard_rows_cover_the_table():
-    """Every symbol of ABI_TWO_STAGE is declared by a row of tests/test_gpu_guarded_two_stage.py."""
+def test_guard_rows_the_family_requires():
+    """Both frame loops have a row, and every symbol of ABI_TWO_STAGE has a row that reaches nothing else."""
     import test_gpu_guarded_two_stage as tgt
-    covered = set().union(*(r.symbols for r in tgt.ROWS_TWO_STAGE))
-    assert set(_lib.ABI_TWO_STAGE) <= covered
-    older = set().union(*(set(getattr(_lib, a)) for a in OLDER.values()))
-    assert covered <= older | set(_lib.ABI_TWO_STAGE)
     names = [r.name for r in tgt.ROWS_TWO_STAGE]
-    assert len(set(names)) == len(names)
     assert any(n.startswith("process_frames_two_stage") for n in names) and any(n.startswith("process_raw_frames_two_stage") for n in names)
     for symbol in _lib.ABI_TWO_STAGE:
         assert any(r.symbols == {symbol} for r in tgt.ROWS_TWO_STAGE), f"{symbol} has no row of its own"

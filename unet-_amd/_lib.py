@@ -14,14 +14,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libunetpp_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["unetpp_abi.hip", "unetpp_postproc.hip"]      # the engine; the post-processing entry points
-HEADERS = ["abi_common.h", "conv3x3_mfma.h", "conv3x3_ws.h", "tapmm_ws.h", "ws_dbg_dev.h", "ws_dbg_host.h", "convt2x2_mfma.h", "aux_kernels.h",
-           "frame_kernels.h", "components.h", "distance.h", "morphology.h", "edges.h", "edges_multi.h", "enhance.h", "nlmeans.h", "evaluation.h",
-           "probmap.h", "multiclass.h", "geometry.h", "tiling.h", "roi_loop.h", "loss.h", "loss_grad.h", "contours.h", "simple_loops.h", "raw_frames.h",
-           "two_stage.h", "train_batch.h", os.path.join("..", "..", "include", "unetpp.h"),
-           os.path.join("..", "..", "include", "unetpp_roi.h"), os.path.join("..", "..", "include", "unetpp_loss.h"),
-           os.path.join("..", "..", "include", "unetpp_contours.h"), os.path.join("..", "..", "include", "unetpp_simple_loops.h"),
-           os.path.join("..", "..", "include", "unetpp_raw.h"), os.path.join("..", "..", "include", "unetpp_two_stage.h"),
-           os.path.join("..", "..", "include", "unetpp_loss_grad.h"), os.path.join("..", "..", "include", "unetpp_train_batch.h")]
+INCLUDE = os.path.join(_HERE, "..", "include")
+# every header on disk is a build input: source_hash() covers each of them, so a new header cannot leave a stale library looking current
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [
+    os.path.join("..", "..", "include", f) for f in sorted(os.listdir(INCLUDE)) if f.endswith(".h")]
 
 STATUS_OVERFLOW, STATUS_NAN = 1, 2
 PREC_EXACT, PREC_FAST, PREC_EXACT8 = 0, 1, 2
@@ -91,7 +87,8 @@ vp, ci, cs, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
 i32p, f32p, u8p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint8)
 btp = ctypes.POINTER(BilateralTables)
 
-# every symbol include/unetpp.h declares: name -> (restype, argtypes); load() applies it
+# One table per public header, each holding every symbol that header declares: name -> (restype, argtypes).  BINDINGS below
+# collects them and load() applies them.
 ABI = {
     "unetpp_create": (ci, [ctypes.POINTER(Config), ctypes.POINTER(vp)]),
     "unetpp_destroy": (None, [vp]),
@@ -185,7 +182,7 @@ class RoiCcRule(ctypes.Structure):
 
 ROI_RULES = {"geometry": 0, "primary": 1}
 
-# every symbol include/unetpp_roi.h declares, built as ABI is; load() applies both tables
+# include/unetpp_roi.h
 ABI_ROI = {
     "unetpp_roi_projection_workspace_bytes": (cs, [ci, ci]),
     "unetpp_roi_stats_workspace_bytes": (cs, [ci]),
@@ -197,13 +194,13 @@ ABI_ROI = {
     "unetpp_roi_paste_masks_u8": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, ci, ci, vp]),
 }
 
-# every symbol include/unetpp_loss.h declares; load() applies all three tables
+# include/unetpp_loss.h
 ABI_LOSS = {
     "unetpp_loss_layout": (ci, [ctypes.POINTER(ci)]),
     "unetpp_loss_sums_f32": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]),
 }
 
-# every symbol include/unetpp_contours.h declares; load() applies all four tables
+# include/unetpp_contours.h
 ABI_CONTOURS = {
     "unetpp_contours_workspace_bytes": (cs, [ci, ci, ci, ci]),
     "unetpp_contour_areas_u8": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
@@ -214,7 +211,7 @@ ABI_CONTOURS = {
 
 PIXEL_RULES = {"relative": 0, "confidence": 1}     # UNETPP_PIXEL_*
 
-# every symbol include/unetpp_simple_loops.h declares; load() applies all five tables
+# include/unetpp_simple_loops.h
 ABI_SIMPLE_LOOPS = {
     "unetpp_pixel_rules_f32": (ci, [vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, vp, vp]),
     "unetpp_components_keep": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ctypes.c_uint8, vp, vp, vp]),
@@ -225,7 +222,7 @@ ABI_SIMPLE_LOOPS = {
 
 RAW_PATTERNS = {"BG": 0, "GB": 1, "RG": 2, "GR": 3, "MONO": 4}          # UNETPP_RAW_*
 
-# every symbol include/unetpp_raw.h declares; load() applies all six tables
+# include/unetpp_raw.h
 ABI_RAW = {
     "unetpp_raw_to_bgr_u8": (ci, [vp, vp, ctypes.c_int64, ctypes.c_int64, ci, ci, ci, ci, vp, vp, vp]),
     "unetpp_raw_resize_u8": (ci, [vp, vp, ctypes.c_int64, ctypes.c_int64, ci, ci, ci, ci, ci, ci, ci, ci, vp, ci, ci, vp]),
@@ -233,26 +230,34 @@ ABI_RAW = {
 
 ROTATE_CODES = {"90_cw": 0, "180": 1, "90_ccw": 2}                      # UNETPP_ROTATE_*: cv2.ROTATE_90_CLOCKWISE, ROTATE_180, ROTATE_90_COUNTERCLOCKWISE
 
-# every symbol include/unetpp_two_stage.h declares; load() applies all seven tables
+# include/unetpp_two_stage.h
 ABI_TWO_STAGE = {
     "unetpp_two_stage_masks_u8": (ci, [vp, vp, ci, ci, ci, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]),
     "unetpp_two_stage_overlay_u8": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
     "unetpp_rotate_u8": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp]),
 }
 
-# every symbol include/unetpp_loss_grad.h declares; load() applies all eight tables
+# include/unetpp_loss_grad.h
 ABI_LOSS_GRAD = {
     "unetpp_loss_grad_layout": (ci, [ctypes.POINTER(ci)]),
     "unetpp_loss_grad_f32": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
     "unetpp_loss_narrow_target_i64": (ci, [vp, vp, ctypes.c_int64, vp, vp]),
 }
 
-# every symbol include/unetpp_train_batch.h declares; load() applies all nine tables
+# include/unetpp_train_batch.h
 ABI_TRAIN_BATCH = {
     "unetpp_train_batch_layout": (ci, [ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]),
     "unetpp_train_crop_rects": (ci, [vp, vp, ctypes.c_int64, vp, ci, vp, ci, vp, vp]),
     "unetpp_train_batch_u8": (ci, [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, ci, ci, vp, vp, vp]),
 }
+
+# public header (a file of include/) -> its table; a new entry-point family adds its table above and one line here
+BINDINGS = {"unetpp.h": ABI, "unetpp_roi.h": ABI_ROI, "unetpp_loss.h": ABI_LOSS, "unetpp_contours.h": ABI_CONTOURS,
+            "unetpp_simple_loops.h": ABI_SIMPLE_LOOPS, "unetpp_raw.h": ABI_RAW, "unetpp_two_stage.h": ABI_TWO_STAGE,
+            "unetpp_loss_grad.h": ABI_LOSS_GRAD, "unetpp_train_batch.h": ABI_TRAIN_BATCH}
+_names = [n for table in BINDINGS.values() for n in table]
+if len(set(_names)) != len(_names):
+    raise ImportError(f"bound in two tables of BINDINGS: {sorted(n for n in set(_names) if _names.count(n) > 1)}")
 
 # -fno-slp-vectorize: the SLP vectoriser turns pairs of float operations into v_pk_mul_f32 / v_pk_fma_f32, and a packed
 # fp32 instruction issued beside another wave's MFMA stream on the same SIMD takes 26-58 cycles instead of 5-7
@@ -348,11 +353,10 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
             raise RuntimeError(f"{LIB_PATH} {what}: build it with __graft_entry__.build(); there is no CPU fallback")
         build()
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(ABI.items()) + list(ABI_ROI.items()) + list(ABI_LOSS.items()) + list(ABI_CONTOURS.items()) + list(
-            ABI_SIMPLE_LOOPS.items()) + list(ABI_RAW.items()) + list(ABI_TWO_STAGE.items()) + list(ABI_LOSS_GRAD.items()) + list(
-            ABI_TRAIN_BATCH.items()):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    for table in BINDINGS.values():
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     ver = lib.unetpp_version().decode()
     if ver.endswith(" +wsdbg") and os.environ.get("UNETPP_ALLOW_DBG_LIB"):
         ver = ver[:-len(" +wsdbg")]            # measurement build with phase ablations (scripts/ws_ablate.sh)

@@ -68,8 +68,12 @@ enum {
 
 /* input formats accepted by unetpp_forward */
 enum {
-  UNETPP_IN_F32_NCHW = 0,    /* float32 [B,3,H,W] RGB in [0,1]: the tensor model(img_tensor) receives,
-                                infer_two_stage_burr.py:292-295 */
+  UNETPP_IN_F32_NCHW = 0,    /* float32 [B,3,H,W] RGB: the tensor model(img_tensor) receives,
+                                infer_two_stage_burr.py:292-295.  Any float32 value: k/255 in [0,1] as that loop feeds, signed
+                                normalised inputs (src/infer/preprocess.py:10-15), anything up to +-65504; subnormals and -0.0
+                                count as 0.  Beyond +-65504 a value is clamped there and UNETPP_STATUS_OVERFLOW is set; a NaN
+                                sets UNETPP_STATUS_NAN and reaches no output (tests/test_gpu_input_domain.py,
+                                tests/test_range_status.py) */
   UNETPP_IN_U8_NHWC_BGR = 1  /* uint8 [B,H,W,3] BGR frame at model resolution: fuses the resize-free
                                 part of preprocess_image (BGR->RGB, /255, HWC->CHW),
                                 infer_two_stage_burr.py:122-127 */

@@ -114,6 +114,20 @@ def pooled(v):
     return F.max_pool2d(v, 2)
 
 
+def layer_agreement(got, emu_v, ref_v):
+    """The per-layer criterion of tests/test_gpu_exact8.py (and of tests/test_gpu_input_domain.py): `got` is the tensor the
+    device stored, emu_v this file's fp32 values of the same layer on the same inputs, ref_v the fp32 reference's arithmetic
+    (float64 tensor).  Returns (mean |got - stored(emu_v)|, mean |got - ref_v|, both as shares of the emulation's largest value;
+    the share of elements that differ from the emulation).  The layer computes the documented arithmetic when the first is
+    10x below the second and under 12 % of the elements differ: what is left are e5m2 roundings of the residual plane that flip
+    on fp32 summation order; a dropped tap or a wrong scale puts the first figure at the level of the second or above."""
+    emu = stored(emu_v)
+    scale = float(np.abs(emu).max())
+    d_emu = float(np.abs(got - emu).mean()) / scale
+    d_ref = float(np.abs(got - ref_v.numpy()).mean()) / scale
+    return d_emu, d_ref, float((got != emu).mean())
+
+
 def _cat(acts):
     a = Act.__new__(Act)
     a.h = torch.cat([t.h for t in acts], 1); a.l8 = torch.cat([t.l8 for t in acts], 1); a.x8 = torch.cat([t.x8 for t in acts], 1)

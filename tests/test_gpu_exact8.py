@@ -335,11 +335,7 @@ def test_exact8_layers_compute_the_documented_arithmetic(torch_cuda, syn, oracle
         return torch.relu(F.conv2d(inp, w, padding=pad) + b[None, :, None, None])
 
     def check(tag, got, emu_v, ref_v):
-        emu = em.stored(emu_v)
-        scale = float(np.abs(emu).max())
-        d_emu = float(np.abs(got - emu).mean()) / scale
-        d_ref = float(np.abs(got - ref_v.numpy()).mean()) / scale
-        differ = float((got != emu).mean())
+        d_emu, d_ref, differ = em.layer_agreement(got, emu_v, ref_v)
         print(f"{tag}: mean |GPU - emulation| = {d_emu:.2e}, mean |GPU - fp32 arithmetic| = {d_ref:.2e} (of the largest value); "
               f"{differ:.2%} of the elements differ from the emulation")
         assert d_emu * 10 < d_ref, tag

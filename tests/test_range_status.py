@@ -82,27 +82,107 @@ def test_simple_unet_overflow_sets_flag(torch_cuda, syn, oracle):
         strict(xt)
 
 
-def test_nan_and_huge_input_set_flags(torch_cuda, syn):
-    """(b) a NaN pixel / a float32 input beyond the fp16 range."""
+ENGINE_KINDS = [(arch, prec) for arch in ("nested", "simple") for prec in ("exact", "exact8", "fast")]
+
+
+def _quiet_first_conv(syn, arch):
+    """(model class, classes, state dict whose first conv's weight is multiplied by 2^-10): an input of +-65504 then leaves
+    every activation far inside the range, so the input alone decides the flags"""
+    from unet_amd.nested_unet import NestedUNet, SimpleUNet
+    if arch == "nested":
+        sd, key, cls, C = syn.make_state_dict(3, 3, True, 2), "conv0_0.conv1.weight", NestedUNet, 3
+    else:
+        sd, key, cls, C = syn.make_simple_state_dict(7, 3, 0), "enc1.0.weight", SimpleUNet, 7
+    sd[key] = sd[key] * np.float32(2.0 ** -10)
+    return cls, C, sd
+
+
+@pytest.mark.parametrize("arch,prec", ENGINE_KINDS)
+def test_nan_and_huge_input_set_flags(arch, prec, torch_cuda, syn, oracle):
+    """(b) a NaN pixel / a float32 input at and beyond the fp16 range, in the six engine kinds (the four pieces of code that
+    ingest the input: conv3x3_ws.h's patch loader, convert_input_kernel<1>, <2> and <2, true>).  +-65504 is inside the range:
+    no flag, parity.  Beyond it the header promises a clamp and the OVERFLOW flag: the outputs are those of the tensor clamped
+    on the host, bit for bit.  A NaN raises NAN and reaches no output."""
+    import os
+    import sys
+    from conftest import ROOT
+    from test_input_domain_host import EXACT_BAR, FAST_TOL, NORTH_STAR, bits_equal, scale_of
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import exact8_emulation as em8
+    import fast_emulation as fe
     torch = torch_cuda
-    from unet_amd.nested_unet import NestedUNet
-    sd = syn.make_state_dict(3, 3, True, 2)
-    m = NestedUNet(3, max_batch=1, max_hw=(32, 48)).to("cuda:0")
+    B, H, W = 1, 32, 48
+    cls, C, sd = _quiet_first_conv(syn, arch)
+    kw = dict(precision=prec, max_batch=B, max_hw=(H, W))
+    m = cls(C, **kw).to("cuda:0")
     m.load_state_dict(sd, strict=True)
-    x = torch.from_numpy(syn.frames_to_chw_f32(syn.make_frames_u8(1, 32, 48, "smooth", 3))).cuda()
-    m.segment(x)
+
+    def run(a):
+        mask, logits = m.segment(a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).cuda(), return_logits=True)
+        torch.cuda.synchronize()
+        return logits.cpu().numpy(), mask.cpu().numpy()
+
+    x = syn.frames_to_chw_f32(syn.make_frames_u8(B, H, W, "smooth", 3))
+    run(x)
     assert m.status() == 0
-    xn = x.clone(); xn[0, 1, 7, 9] = float("nan")
-    m.segment(xn)
-    assert m.status(clear=True) & NAN
-    xb = x.clone(); xb[0, 2, 20, 30] = 1.0e6
-    m.segment(xb)
-    assert m.status(clear=True) & OVERFLOW
-    m.segment(x)                                   # sticky, not stuck: clean again after the clear
+
+    # exactly +-65504 at the corners and on the first block's tile seams: representable, so no flag, and parity as for any input
+    xi = syn.make_inputs_f32("impulses", B, H, W, 3) * np.float32(65504.0)
+    assert float(np.abs(xi).max()) == 65504.0 and (xi < 0).any() and (xi > 0).any()
+    fwd = oracle.torch_forward if arch == "nested" else oracle.simple_unet_torch_forward
+    ref, inter = fwd(sd, xi, return_intermediates=True)
+    assert max(float(np.abs(v).max()) for v in inter.values()) < 2.0 ** 15      # the input alone is large
+    s = scale_of(ref)
+    cap = EXACT_BAR[arch] * s
+    if prec == "exact8":
+        cap = min(2 * float(np.abs(em8.exact8_forward(sd, xi) - ref).max()) + cap, NORTH_STAR * s) if arch == "nested" else NORTH_STAR * s
+    elif prec == "fast":
+        emu = fe.fast_forward(sd, xi) if arch == "nested" else fe.fast_simple_forward(sd, xi)
+        cap = min(2 * float(np.abs(emu - ref).max()) + cap, FAST_TOL * s)
+    lg, mk = run(xi)
+    err = float(np.abs(lg - ref).max())
+    print(f"{arch} {prec}: +-65504 impulses, max|dlogit| / s = {err / s:.2e} (cap {cap / s:.2e}), s = {s:.3g}")
+    assert m.status() == 0
+    assert np.isfinite(lg).all() and err <= cap
+    assert not ((mk != oracle.masks_from_logits(ref)[0]) & (oracle.top2_margin(ref) > 2 * err + 1e-7)).any()
+
+    # a NaN: flagged, and every output stays finite -- also where only a neighbouring tile's halo reads the pixel a second time
+    for pos in ((0, 1, 7, 9), (0, 0, 16, 32)):
+        xn = x.copy(); xn[pos] = np.float32("nan")
+        lg, _ = run(xn)
+        assert m.status(clear=True) & NAN, pos
+        assert np.isfinite(lg).all(), pos
+        assert m.status() == 0
+
+    # beyond the range: OVERFLOW (and not NAN), results of the clamped tensor, bit for bit
+    for pos, v in (((0, 2, 20, 30), 1.0e6), ((0, 1, 16, 32), -1.0e6), ((0, 0, 0, 0), float("inf")), ((0, 2, H - 1, W - 1), float("-inf"))):
+        xb = x.copy(); xb[pos] = np.float32(v)
+        lg, mk = run(xb)
+        st = m.status(clear=True)
+        assert st & OVERFLOW and not st & NAN, (v, st)
+        lc, mc = run(np.clip(xb, np.float32(-65504.0), np.float32(65504.0)))
+        assert m.status() == 0, v
+        assert bits_equal(lg, lc) and np.array_equal(mk, mc), v
+    # the first float32 value that does not round to an fp16 number (values between 65504 and 65520 are left unspecified)
+    for v in (65520.0, -65520.0):
+        xb = x.copy(); xb[0, 1, 15, 31] = np.float32(v)
+        run(xb)
+        assert m.status(clear=True) & OVERFLOW, v
+
+    run(x)                                         # sticky, not stuck: clean again after the clear
     assert m.status() == 0
     # uint8 frames cannot leave the range
-    m.segment(torch.from_numpy(syn.make_frames_u8(1, 32, 48, "uniform", 4)).cuda())
+    run(torch.from_numpy(syn.make_frames_u8(B, H, W, "uniform", 4)).cuda())
     assert m.status() == 0
+
+    strict = cls(C, check_range=True, **kw).to("cuda:0")
+    strict.load_state_dict(sd, strict=True)
+    strict(torch.from_numpy(x).cuda())
+    for v in (1.0e6, float("nan")):
+        xb = x.copy(); xb[0, 2, 20, 30] = np.float32(v)
+        with pytest.raises(RuntimeError, match="value range"):
+            strict(torch.from_numpy(xb).cuda())
+    strict(torch.from_numpy(x).cuda())             # the raise cleared the flags
 
 
 def test_non_finite_weights_set_flag_at_load(torch_cuda, syn):

@@ -164,7 +164,8 @@ __global__ void conv0_pack_kernel(const float* __restrict__ w, const float* __re
 
 // ------------------------------------------------------------------------------------------------
 // Input conversion -> [N][1][H][W][P][8] fp16 (one channel block of 8, channels 3..7 zero).
-//   fmt 0: float32 NCHW RGB in [0,1]                    (model(img_tensor), infer_two_stage_burr.py:292-295)
+//   fmt 0: float32 NCHW RGB, any value: clamped to +-65504 and flagged beyond, NaN flagged
+//                                                        (model(img_tensor), infer_two_stage_burr.py:292-295)
 //   fmt 1: uint8 NHWC BGR: RGB = BGR reversed, /255.0f   (preprocess_image, infer_two_stage_burr.py:122-127)
 template <int P, bool X8 = false>
 __global__ void convert_input_kernel(const void* __restrict__ in, int fmt, int N, int H, int W,

@@ -308,7 +308,8 @@ class NestedUNet(PostProcessing):
 
     def segment(self, x, return_logits: bool = False, return_class_masks: bool = False, output: int = 0):
         """Fused model call + softmax/argmax/uint8 (+ class masks) of infer_two_stage_burr.py:294-304.
-        x: float32 [B,3,H,W] in [0,1] or uint8 [B,H,W,3] BGR frames at model resolution.
+        x: float32 [B,3,H,W] (any values up to +-65504: status() says when one was clamped) or uint8 [B,H,W,3] BGR frames at
+        model resolution.
         output=k (1..3): the same on deep-supervision output k, from a pruned pass (see forward)."""
         logits, mask, cable, tape = self._run(x, return_logits, True, return_class_masks, output=output)
         out = (mask,)

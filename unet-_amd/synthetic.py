@@ -99,6 +99,84 @@ def frames_to_chw_f32(frames_u8: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(np.transpose(x, (0, 3, 1, 2)))
 
 
+# ----------------------------------------------------------------------------- the float32 input domain
+# forward() takes any float32 [B,3,H,W]: the reference normalises with ImageNet statistics in src/infer/preprocess.py:10-15 and
+# with A.Normalize() in src/data/transforms.py:14,22, so its inputs are signed (about -2.1 ... 2.6), and nothing restricts them to
+# k/255.  The families below cover what the ingest code (the fused first block's patch loader, convert_input_kernel) has to
+# split into fp16 planes: signed, wide, full-mantissa, tiny and subnormal values, zeros of both signs
+# (tests/test_input_domain_host.py, tests/test_gpu_input_domain.py).
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+INPUT_KINDS = ("unit", "imagenet", "bytes", "wide", "normal", "mantissa", "negated", "small", "denormal", "logspan", "impulses",
+               "zeros", "signed_zeros")
+PARITY_INPUT_KINDS = INPUT_KINDS[:-2]
+
+
+def impulse_positions(h: int, w: int):
+    """(row, col) of the four corners and of the tile seams of the first block (columns 31 / 32, rows 15 / 16; the image border
+    where the image has no such row or column), crossed: 16 positions or fewer"""
+    rows = sorted({0, min(15, h - 1), min(16, h - 1), h - 1})
+    cols = sorted({0, min(31, w - 1), min(32, w - 1), w - 1})
+    return [(r, c) for r in rows for c in cols]
+
+
+def make_inputs_f32(kind: str, b: int, h: int, w: int, seed: int = 0) -> np.ndarray:
+    """float32 [b,3,h,w] of one input family (INPUT_KINDS), bit for bit the same on every machine: NumPy + PCG64 only, the draws are
+    integers or the float64 normals the weight generators use, everything after them float32 or integer arithmetic
+    (tests/test_input_domain_host.py records a sha256 per kind and shape).  Families built on frames take
+    `make_frames_u8(b, h, w, "smooth", seed)`."""
+    if kind not in INPUT_KINDS:
+        raise ValueError(f"unknown input kind {kind!r}: one of {INPUT_KINDS}")
+    rng = np.random.Generator(np.random.PCG64([int(seed), INPUT_KINDS.index(kind)]))
+    shape = (b, 3, h, w)
+    f32 = np.float32
+
+    def uniform24():
+        """uniform float32 in [0, 1) from 24 random bits: every mantissa bit is used"""
+        return (rng.integers(0, 1 << 24, shape, dtype=np.int64).astype(f32) * f32(2.0 ** -24)).astype(f32)
+
+    if kind in ("unit", "imagenet", "bytes", "negated"):
+        frames = make_frames_u8(b, h, w, "smooth", seed)
+        if kind == "bytes":
+            x = np.transpose(frames[..., ::-1].astype(f32), (0, 3, 1, 2))
+        else:
+            x = frames_to_chw_f32(frames)
+        if kind == "imagenet":
+            mean = np.array(IMAGENET_MEAN, dtype=f32)[None, :, None, None]
+            std = np.array(IMAGENET_STD, dtype=f32)[None, :, None, None]
+            x = ((x - mean) / std).astype(f32)
+        elif kind == "negated":
+            x = -x
+    elif kind == "wide":
+        x = (f32(255.0) * (f32(2.0) * uniform24() - f32(1.0))).astype(f32)
+    elif kind == "mantissa":
+        x = uniform24()
+    elif kind == "normal":
+        x = rng.standard_normal(shape).astype(f32)
+    elif kind == "small":
+        x = (f32(1e-3) * rng.standard_normal(shape).astype(f32)).astype(f32)
+    elif kind == "denormal":
+        n = rng.integers(-(1 << 22), (1 << 22) + 1, shape, dtype=np.int64)
+        bits = (np.abs(n).astype(np.uint32) | np.where(n < 0, np.uint32(0x80000000), np.uint32(0))).astype(np.uint32)
+        x = bits.view(f32)                                        # |n| 2^-149: the subnormal's bit pattern is the integer
+    elif kind == "logspan":
+        # +-2^e, e in [-30, 7): the integer part of e uniform over the 37 octaves, the position inside the octave from 23 random
+        # mantissa bits (no exp2 call: its last bit is libm's) -- every magnitude the planes hold, each with a full mantissa
+        e = rng.integers(-30, 7, shape, dtype=np.int64)
+        frac = rng.integers(0, 1 << 23, shape, dtype=np.int64).astype(np.uint32)
+        sign = rng.integers(0, 2, shape, dtype=np.int64).astype(np.uint32) << np.uint32(31)
+        x = (((e + 127).astype(np.uint32) << np.uint32(23)) | frac | sign).view(f32)
+    elif kind == "impulses":
+        x = np.zeros(shape, dtype=f32)
+        for r, c in impulse_positions(h, w):
+            x[:, :, r, c] = np.where(rng.integers(0, 2, (b, 3)) == 1, f32(1.0), f32(-1.0))
+    else:
+        x = np.zeros(shape, dtype=f32)
+        if kind == "signed_zeros":
+            x = np.where(rng.integers(0, 2, shape) == 1, f32(-0.0), f32(0.0)).astype(f32)
+    return np.ascontiguousarray(x, dtype=f32)
+
+
 def make_trained_like_state_dict(num_classes: int = 3, in_channels: int = 3, deep_supervision: bool = True,
                                  seed: int = 2, big_gain: float = 3.0) -> dict:
     """`make_state_dict` with the BatchNorm statistics a trained checkpoint shows and He-init never does
